@@ -6,11 +6,17 @@ One step = occupancy-grid ray marching (ONE-level 128^3 grid, all cel
 rays from the sphere of radius 1.5 aimed at uniform targets in [-0.5, 0.5]^3; constant step chosen so that the rays
 yield 1024 samples on average -- the actual N is reported) -> hash-grid field + fused MLPs forward -> packed volume
 rendering -> MSE(rgb, target) -> backward (incl. ray/pose gradients) -> [RCCL all-reduce of the flat gradient] -> fused
-Adam.  Synthetic rays, random-init parameters, fp32 throughout.  Extra keys of the JSON line (N = 1 only): the round-1/2
-headline workload (`m_march_inside_box`: origins inside the box, exactly 1024 samples per ray -- the friendlier input),
-SURVEY 8d's M-packed, the reference's default configuration, and the reference's real 3-bundle step compositions.
+Adam.  Synthetic rays, random-init parameters, fp32 throughout.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline, HBM roofline of the dominant hash kernel from
+the events inside the timed region, step roofline).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(collect_outputs): that step starts from the set-up state again, so its inputs are the same on every run (the training state the
+steps before it reach is not: float-atomic gradient sums, amplified by Adam).
+--full adds everything else the benchmark measures: the per-entry-point breakdown pass (kernel_ms_per_step,
+mfma), roofline.atomic and, for N = 1, the headline as a replayed graph, the round-1/2 headline workload (`m_march_inside_box`:
+origins inside the box, exactly 1024 samples per ray -- the friendlier input), SURVEY 8d's M-packed, the reference's default
+configuration, the reference's real 3-bundle step compositions and the CPU baseline.
 N > 1: one rank per GPU over RCCL; per-GPU work is fixed (weak scaling): each rank renders its own 4096 rays and the gradient
 is all-reduced once per step.  Under a launcher (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``:
 WORLD_SIZE is set) this process IS a rank.  Started bare (``python bench.py --gpus N``, no WORLD_SIZE) it is the PARENT: before
@@ -125,15 +131,19 @@ def build_workload(device, seed, kind="sphere", n_sets=1):
     return model, sets, counts()
 
 
-def train_step(model, rb, target, jitter, opt, world, exchange=None, pipeline=None, sharded=None, graphed=None, exposed=None):
+def train_step(model, rb, target, jitter, opt, world, exchange=None, pipeline=None, sharded=None, graphed=None, exposed=None,
+               keep=None):
     """One step of the headline workload.  ``exposed``: a list that collects (event, event) pairs around the blocking part of the
-    gradient exchange (the exchange modes that overlap collect theirs inside lsenerf_amd.dist)."""
+    gradient exchange (the exchange modes that overlap collect theirs inside lsenerf_amd.dist).  ``keep``: a dict that receives the
+    step's rendered outputs under "out" (--dump-outputs)."""
     from lsenerf_amd import dist as ldist
     if graphed is not None:
         # N > 1, exchange mode "graphed": everything up to the backward pass is ONE replayed HIP graph (optimizer_in_graph=False),
         # then the all-reduce of the flat gradient, then Adam -- three host calls per step (R:lse_nerf/lse_pipeline.py:95-98's DDP
         # all-reduce sits at the same place: between backward and the optimizer)
         loss = graphed(rb, None, None, {"col_batch": {"image": target}, "evs_batch": None}, jitter=jitter)["rgb_loss"]
+        if keep is not None:
+            keep["out"] = graphed.outputs["col_out"]
         ev = None
         if exposed is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -159,6 +169,8 @@ def train_step(model, rb, target, jitter, opt, world, exchange=None, pipeline=No
     #  through the estimator's after_march_hook -- dist.GradPipeline.attach)
     opt.zero_grad()
     out = model.render_packed(rb, ri, ts, te, packed, n_dev=n_dev)
+    if keep is not None:
+        keep["out"] = out
     # routing (training clamp) + rgb MSE in the fused epilogue kernel pair, as the training step does
     loss = model.fused_loss_dict({"col_out": out, "prev_out": None, "next_out": None},
                                  {"col_batch": {"image": target}, "evs_batch": None})["rgb_loss"]
@@ -606,16 +618,67 @@ def cpu_baseline(seconds_budget=25.0):
                       + f"; torch-native field (hash pytorch_fwd + nn.Linear MLPs + torch volrend + Adam), fp32, {cores} threads"}
 
 
+DUMP_SAMPLE = 1 << 20        # --dump-outputs: a parameter with more entries (the hash table) is written as this many of them
+
+
+def collect_outputs(model, flat, rb, out, loss):
+    """What the last timed step computed, copied to the host: the loss, the rendered colour / opacity / depth and the sample count of
+    every ray, the gradients w.r.t. the rays (what a pose optimiser receives) and w.r.t. every parameter (what Adam receives).  A
+    gradient larger than DUMP_SAMPLE is sampled at fixed positions (seeded permutation, ascending; stored as "<name>.index").
+    Not the parameters after Adam: Adam divides every entry by its own gradient's magnitude, so an entry whose gradient is a nearly
+    cancelling sum (float atomics: its rounding depends on the order of the additions) turns that rounding into a full-size step."""
+    import numpy as np
+    res = {"loss": loss.detach().reshape(1)}
+    for k in ("rgb", "accumulation", "depth", "num_samples_per_ray"):
+        if out is not None and k in out:
+            res[k] = out[k].detach()
+    for k, g in (("ray_origins_grad", rb.origins.grad), ("ray_directions_grad", rb.directions.grad)):
+        if g is not None:
+            res[k] = g.detach()
+    names = {id(p): n for n, p in model.named_parameters()}
+    for p in flat.params:
+        name, v = "grad." + names[id(p)], p.grad.detach().reshape(-1)
+        if v.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(96))[:DUMP_SAMPLE].sort().values
+            res[name + ".index"] = idx
+            v = v[idx.to(v.device)]
+        res[name] = v
+    # float32 stays float32; integers (counts, indices) and anything wider become float64, exactly
+    return {k: t.cpu().numpy().astype(np.float32 if t.dtype == torch.float32 else np.float64) for k, t in res.items()}
+
+
+def _restore_training_state(opt, pipeline, snap):
+    """Parameters and Adam state back to a _snapshot (the occupancy grid of the headline is never refreshed: left alone)."""
+    if pipeline is not None:
+        pipeline.flush()           # the previous step's exchange + Adam must not land on the restored state
+    with torch.no_grad():
+        opt.flat.data.copy_(snap[0]); opt.exp_avg.copy_(snap[1]); opt.exp_avg_sq.copy_(snap[2])
+    opt.step_count = snap[3]
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)         # SURVEY 8d: "Warm-up 20 steps, time 100 steps"
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-context", action="store_true", help="skip the default-config / M-packed context runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the instrumented per-kernel pass (kernel_ms_per_step, mfma), "
+                         "roofline.atomic, the graphed / context workloads and the CPU baseline (the three --no-* options below thin it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, rendered rays, ray and parameter gradients; the hash "
+                         "table's as a fixed sample) as DIR/<name>.npy; that step starts from the set-up state")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-context", action="store_true", help="with --full: skip the graphed and context workloads")
     ap.add_argument("--no-atomic-floor", action="store_true",
-                    help="skip roofline.atomic (its request count sorts 16 x 8 x N indices with torch kernels AFTER the timed region: "
-                         "left out of rocprofv3 passes so that the kernel statistics hold the step's kernels only)")
+                    help="with --full: skip roofline.atomic (its request count sorts 16 x 8 x N indices with torch kernels AFTER the "
+                         "timed region: left out of rocprofv3 passes so that the kernel statistics hold the step's kernels only)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="self-launched ranks are terminated after this many seconds")
     args = ap.parse_args()
 
@@ -668,6 +731,12 @@ def main():
         exchange = ldist.OverlappedGradExchange(flat, grid.params, grid.meta.offsets, split_level=min(6, grid.meta.n_levels - 1))
         exchange.install()
 
+    if args.dump_outputs and mode in ("sharded", "pipelined_sharded"):
+        raise SystemExit(f"bench.py: --dump-outputs restores FlatAdam's state, which exchange mode {mode} does not use")
+    # --dump-outputs: the last timed step starts again from the set-up state (parameters as initialised and broadcast, fresh Adam
+    # state), so that its inputs are the same on every run.  The steps before it cannot be: the hash and MLP backward sum gradients
+    # with float atomics, and Adam turns those last-bit differences into trajectories that part within a few dozen steps
+    setup_state = _snapshot(model, opt) if args.dump_outputs else None
     graphed = None
     if mode == "graphed":       # replay (sampler .. backward) -> all-reduce -> Adam; the pre-pass is off as SURVEY 8d prescribes
         from lsenerf_amd.graph import GraphedTrainStep
@@ -680,12 +749,12 @@ def main():
 
     step_no = 0
 
-    def one_step():
+    def one_step(keep=None):
         # every step trains on the next of the N_RAY_SETS resident (rays, targets, stratified offsets) sets
         nonlocal step_no
         rb_k, target_k, jitter_k = sets[step_no % len(sets)]
         step_no += 1
-        return train_step(model, rb_k, target_k, jitter_k, opt, world, exchange, pipeline, sharded, graphed, exposed)
+        return train_step(model, rb_k, target_k, jitter_k, opt, world, exchange, pipeline, sharded, graphed, exposed, keep)
 
     n_samples = 0
     for _ in range(args.warmup):
@@ -702,9 +771,12 @@ def main():
     if world > 1:
         tdist.barrier()
     torch.cuda.synchronize()
+    last = {} if args.dump_outputs and rank == 0 else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        n_samples, loss = one_step()
+    for i in range(args.steps):
+        if setup_state is not None and i == args.steps - 1:
+            _restore_training_state(opt, pipeline, setup_state)      # (one 150 MB device copy inside the timed region)
+        n_samples, loss = one_step(last if i == args.steps - 1 else None)
     if pipeline is not None:
         pipeline.flush()           # the K-th all-reduce + Adam belong to the timed K steps
     host_issue = time.perf_counter() - t0      # host time to ISSUE the K steps (the sampler's one sync per step included)
@@ -730,21 +802,28 @@ def main():
         exposed = None
         if pipeline is not None:
             pipeline.exposed_events = None
+    if last is not None:           # before anything else runs the model again
+        write_outputs(args.dump_outputs, collect_outputs(model, flat, sets[(step_no - 1) % len(sets)][0], last.get("out"), loss))
+        last = None                # (the outputs own their autograd graph: see _drop_autograd_graphs)
+    setup_state = None
 
     per_kernel = {}
     for name, e0, e1 in timing["events"]:
         per_kernel.setdefault(name, []).append(e0.elapsed_time(e1))
     dom_ms_all = {k: sum(v) / len(v) for k, v in per_kernel.items()}            # mean launch duration inside the timed region
-    # per-entry-point breakdown: separate instrumented pass (same workload, not part of the timed K steps)
-    bsteps = min(args.steps, 8)
     if graphed is not None:     # (a replayed graph has no host hooks between its kernels: the breakdown pass runs the eager step)
         graphed.close()
         graphed = None
         model.deferred_counts = True
-    kern_ms, launches = _event_pass(lambda i: train_step(model, *sets[i % len(sets)], opt, world, exchange, pipeline, sharded),
-                                    0, bsteps, None)
-    if pipeline is not None:
-        pipeline.flush()
+    # per-entry-point breakdown: separate instrumented pass (same workload, not part of the timed K steps); without --full only
+    # where the timed region carried no kernel events (exchange mode "graphed") and the roofline needs the pass
+    kern_ms, launches, bsteps = {}, {}, 0
+    if args.full or not dom_ms_all:
+        bsteps = min(args.steps, 8)
+        kern_ms, launches = _event_pass(lambda i: train_step(model, *sets[i % len(sets)], opt, world, exchange, pipeline, sharded),
+                                        0, bsteps, None)
+        if pipeline is not None:
+            pipeline.flush()
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -775,7 +854,7 @@ def main():
         except OSError:
             pass
         atomic = None
-        if dom == "lse_hash_bwd" and not args.no_atomic_floor and world == 1:      # (N = 1 only, like cpu_baseline: rank 0 alone would lag the others)
+        if args.full and dom == "lse_hash_bwd" and not args.no_atomic_floor and world == 1:   # (N = 1 only, like cpu_baseline: rank 0 alone would lag the others)
             # second roofline of the dominant kernel: it scatters with float atomics, which gfx950 executes at the memory side at a
             # chip-wide REQUEST rate (MI355X_MICROARCH.md "Global float atomics": ~1.3 TB/s of 64-byte requests = ~20 G requests/s;
             # tools/micro/atomic_gran.hip: 21 G/s), far below the HBM byte rate the contract's `frac` is priced against
@@ -829,28 +908,31 @@ def main():
             "step_roofline": {"algorithmic_bytes_per_step": b_step,
                               "achieved_GBps": b_step / (ms_per_step * 1e-3) / 1e9 * 1.0,
                               "frac_of_hbm_peak": b_step / (ms_per_step * 1e-3) / HBM_PEAK},
-            "mfma": (lambda t_ms: {
-                "kernels": "lse_mlp_fwd+lse_mlp_bwd", "ms": t_ms,
-                "note": "f32-equivalent arithmetic on the bf16 matrix cores (three bf16 pieces per operand, six piece products, f32 "
-                        "accumulate; the backward recomputes the hidden layers): `executed_bf16_*` prices the MFMA instructions "
-                        "actually issued against the dense bf16 peak; `matrix_core_busy` is SQ_VALU_MFMA_BUSY_CYCLES / (SIMDs x "
-                        "kernel cycles) from the committed rocprofv3 --pmc summary of the same kernels",
-                "executed_bf16_flop_per_sample": MLP_BF16_FLOP_PER_SAMPLE,
-                "executed_bf16_TFLOPs": MLP_BF16_FLOP_PER_SAMPLE * n_samples / (1e-3 * t_ms) / 1e12, "bf16_peak_TFLOPs": 2500.0,
-                "executed_bf16_frac": MLP_BF16_FLOP_PER_SAMPLE * n_samples / (1e-3 * t_ms) / 2.5e15,
-                "matrix_core_busy": sq_busy, "matrix_core_busy_stale": None if stale is None else stale["mlp"]})(
-                    kern_ms.get("lse_mlp_fwd", 0) + kern_ms.get("lse_mlp_bwd", 0) + kern_ms.get("lse_mlp_wgrad", 0) + 1e-9),
-            "kernel_ms_per_step": {k: round(v, 4) for k, v in sorted(kern_ms.items())},
-            "kernel_ms_note": "per C-ABI entry point, from a separate instrumented pass of %d steps (event pairs around every "
-                              "entry point perturb the step; the timed region instruments the two hash kernels only)" % bsteps,
             "host_issue_ms_per_step": host_issue / args.steps * 1e3,
             "host_issue_note": "host time to issue the K timed steps; no sample count is read back (device-side counts), so this is "
                                "Python + launch time and the host runs ahead of the GPU",
             "loss": float(loss.detach()),
         }
+        if args.full:
+            line.update({
+                "mfma": (lambda t_ms: {
+                    "kernels": "lse_mlp_fwd+lse_mlp_bwd", "ms": t_ms,
+                    "note": "f32-equivalent arithmetic on the bf16 matrix cores (three bf16 pieces per operand, six piece products, f32 "
+                            "accumulate; the backward recomputes the hidden layers): `executed_bf16_*` prices the MFMA instructions "
+                            "actually issued against the dense bf16 peak; `matrix_core_busy` is SQ_VALU_MFMA_BUSY_CYCLES / (SIMDs x "
+                            "kernel cycles) from the committed rocprofv3 --pmc summary of the same kernels",
+                    "executed_bf16_flop_per_sample": MLP_BF16_FLOP_PER_SAMPLE,
+                    "executed_bf16_TFLOPs": MLP_BF16_FLOP_PER_SAMPLE * n_samples / (1e-3 * t_ms) / 1e12, "bf16_peak_TFLOPs": 2500.0,
+                    "executed_bf16_frac": MLP_BF16_FLOP_PER_SAMPLE * n_samples / (1e-3 * t_ms) / 2.5e15,
+                    "matrix_core_busy": sq_busy, "matrix_core_busy_stale": None if stale is None else stale["mlp"]})(
+                        kern_ms.get("lse_mlp_fwd", 0) + kern_ms.get("lse_mlp_bwd", 0) + kern_ms.get("lse_mlp_wgrad", 0) + 1e-9),
+                "kernel_ms_per_step": {k: round(v, 4) for k, v in sorted(kern_ms.items())},
+                "kernel_ms_note": "per C-ABI entry point, from a separate instrumented pass of %d steps (event pairs around every "
+                                  "entry point perturb the step; the timed region instruments the two hash kernels only)" % bsteps,
+            })
         del loss
         _drop_autograd_graphs({})
-        if world == 1 and not args.no_context:
+        if world == 1 and args.full and not args.no_context:
             # the headline workload as one replayed graph (pre-pass off as SURVEY 8d prescribes: no density_fn on the sampler)
             model.sampler.density_fn = None
             cyc = [(rb_k, None, None, {"col_batch": {"image": t_k}, "evs_batch": None}) for rb_k, t_k, _ in sets]
@@ -874,7 +956,7 @@ def main():
             line["cfg3_composition"] = context_composition(device, "cfg3")
             torch.cuda.empty_cache()
             line["cfg4_composition"] = context_composition(device, "cfg4")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     if world > 1:

@@ -332,6 +332,43 @@ def test_bench_request_floor_counts_the_lines_the_oracle_indexing_touches():
     assert bench.hash_bwd_request_floor(x01, meta) == want
 
 
+def test_bench_dump_outputs_are_named_float_arrays_of_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: what the last timed step computed, as float32 / float64 .npy files under 64 MB in all; the hash
+    table's gradient (above bench.DUMP_SAMPLE entries) is written at the same seeded positions every time, the smaller ones in full."""
+    import types
+    import numpy as np
+    import bench
+    import lsenerf_amd as la
+    from lsenerf_amd.optim import FlatParams
+    torch.manual_seed(96)
+    m = la.LSENeRFModel(la.LSENeRFModelConfig(grid_levels=1), torch.tensor([[-1.0, -1, -1], [1, 1, 1]]), num_train_data=64)
+    flat = FlatParams(m.get_param_groups()["fields"], total_multiple=64)
+    flat.grad.copy_(torch.randn(flat.numel, generator=torch.Generator().manual_seed(3)))      # (p.grad are views of it)
+    R = 64
+    rb = types.SimpleNamespace(origins=torch.rand(R, 3, requires_grad=True), directions=torch.rand(R, 3, requires_grad=True))
+    (rb.origins.square().sum() + rb.directions.sum()).backward()
+    out = {"rgb": torch.rand(R, 3), "accumulation": torch.rand(R, 1), "depth": torch.rand(R, 1),
+           "num_samples_per_ray": torch.randint(0, 2000, (R,), dtype=torch.int32)}
+    arrays = bench.collect_outputs(m, flat, rb, out, torch.tensor(0.25))
+    bench.write_outputs(str(tmp_path / "a"), arrays)
+    table = "grad.field.mlp_base_grid.params"
+    assert {"loss", "rgb", "accumulation", "depth", "num_samples_per_ray", "ray_origins_grad", "ray_directions_grad",
+            table, table + ".index", "grad.field.mlp_base_mlp.params", "grad.field.mlp_head.params"} <= set(arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64e6
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "a" / (k + ".npy"))
+        assert b.dtype in (np.float32, np.float64) and np.array_equal(a, b), k
+    assert np.array_equal(arrays["num_samples_per_ray"], out["num_samples_per_ray"].numpy())
+    assert np.array_equal(arrays["ray_origins_grad"], 2 * rb.origins.detach().numpy())
+    idx = arrays[table + ".index"]
+    assert idx.size == bench.DUMP_SAMPLE < m.field.mlp_base_grid.params.numel() and np.all(np.diff(idx) > 0)
+    assert np.array_equal(arrays[table], m.field.mlp_base_grid.params.grad.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(arrays["grad.field.mlp_head.params"], m.field.mlp_head.params.grad.numpy())
+    assert not any(k.startswith("param.") for k in arrays)
+    again = bench.collect_outputs(m, flat, rb, out, torch.tensor(0.25))
+    assert all(np.array_equal(again[k], arrays[k]) for k in arrays)
+
+
 def test_unknown_map_mode_falls_through_like_the_reference():
     """The reference's DEFAULT map_mode is the spelling "ev_rgb" (R:lse_nerf/lsenerf.py:80), which names none of the three routes:
     its get_outputs falls through every branch (:335-363) -- no mapper runs, no "ev_out" is produced -- so with use_mapping an

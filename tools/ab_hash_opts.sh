@@ -6,7 +6,7 @@ OUT=$1; shift; mkdir -p $(dirname $OUT)
 for cfg in "$@"; do
   unset LSE_OPT_HASH_BWD_FEW_RUNS LSE_OPT_HASH_BWD_STAGE_MAX LSE_OPT_HASH_BWD_PROBES
   for kv in $cfg; do export LSE_OPT_HASH_BWD_$kv; done
-  timeout -k 10 400 python bench.py --no-cpu-baseline --steps 20 2>/dev/null | tail -1 | python -c "
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline --steps 20 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms_per_step']

@@ -4,7 +4,7 @@ export LSE_DEV=1      # LSE_OPT_* knobs exist in the development build only (lib
 OUT=$1; shift; mkdir -p $(dirname $OUT)
 for v in "$@"; do
   export LSE_OPT_HASH_BWD_PROBES=$v
-  timeout -k 10 400 python bench.py --no-cpu-baseline --steps 20 2>/dev/null | tail -1 | python -c "
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline --steps 20 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms_per_step']

@@ -3,7 +3,7 @@
 OUT=$1; mkdir -p $(dirname $OUT)
 for f in start hash_bwd; do
   export LSE_BENCH_PREFETCH_FORK=$f
-  timeout -k 10 400 python bench.py --no-cpu-baseline --steps 20 2>/dev/null | tail -1 | python -c "
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline --steps 20 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 g = lambda e: (e['graphed']['ms_per_step'], e['graphed']['marcher_prefetched']['ms_per_step'])

@@ -8,7 +8,7 @@ timeout -k 10 500 python tools/hash_bwd_variants.py "gran=6" "gran=6 nodx=1" "gr
     > $OUT/hash_bwd_variants.txt 2> $OUT/hash_bwd_variants.err
 echo "hash variants rc=$?"; tail -45 $OUT/hash_bwd_variants.txt
 for cfg in 208 204; do
-  LSE_OPT_MLP_BWD3_CFG=$cfg timeout -k 10 300 python bench.py --no-cpu-baseline --no-context --no-atomic-floor --steps 30 --warmup 10 2> $OUT/mlp_cfg$cfg.err | tail -1 | python -c "
+  LSE_OPT_MLP_BWD3_CFG=$cfg timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-context --no-atomic-floor --steps 30 --warmup 10 2> $OUT/mlp_cfg$cfg.err | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['kernel_ms_per_step']
 print('mlp_bwd3_cfg=$cfg ms/step %.3f mlp_bwd %.4f mlp_fwd %.4f hash_bwd %.4f' % (d['ms_per_step'], k['lse_mlp_bwd'], k['lse_mlp_fwd'], k['lse_hash_bwd']))" | tee -a $OUT/mlp_bwd3_cfg.txt
