@@ -353,6 +353,32 @@ int lse_render_weight_bwd(const float *t_starts, const float *t_ends, const floa
                           int32_t n_rays, const float *weights, const float *d_weights, float *d_sigmas,
                           lse_stream_t stream);
 
+/* Forward-only compositing of an EVALUATION render (no autograd, nothing kept for a backward pass): the per-ray walk and summation
+ * order of lse_volrend_depth_fwd, bit for bit, plus the renderer epilogue of LSENeRFModel.render_packed in the same call:
+ *   flags & LSE_EVAL_NAN_TO_NUM: torch.nan_to_num of the three colour columns per sample (renderers other than LinearRenderer);
+ *   depth = clip(num / (acc + 1e-10), lo, hi), (lo, hi) the min / max interval mid-point over the n_rays rays of this call (always);
+ *   flags & LSE_EVAL_BACKGROUND: rgb + background * (1 - acc)   ("black" 0 / "white" 1);
+ *   flags & LSE_EVAL_CLAMP: clamp(rgb, 0, 1), NaN propagated like torch.clamp.
+ * Sample arrays may have capacity extent: packed_info rows are authoritative.  The outputs out_rgb [n,3], out_acc [n], out_depth [n],
+ * out_nsamples [n] (int64: the packed_info counts) may be row offsets into a larger image.  workspace: 3 * n_rays floats. */
+#define LSE_EVAL_NAN_TO_NUM 1
+#define LSE_EVAL_BACKGROUND 2
+#define LSE_EVAL_CLAMP 4
+int lse_eval_composite(const float *t_starts, const float *t_ends, const float *sigmas, const float *rgb, int32_t rgb_stride,
+                       const int64_t *packed_info, int32_t n_rays, int32_t flags, float background, float *workspace, float *out_rgb,
+                       float *out_acc, float *out_depth, int64_t *out_nsamples, lse_stream_t stream);
+
+/* ---- image metrics: SSIM and MSE of preds / target, contiguous f32 [B,C,H,W] with H, W >= 11 (else LSE_E_INVALID) -----------
+ *      torchmetrics structural_similarity_index_measure(preds, target) with its defaults (R:lse_nerf/lsenerf.py:206, :512), restated
+ *      from the published algorithm (parity unpinned): data_range R = max(max p - min p, max t - min t) on the device,
+ *      C1 = (0.01 R)^2, C2 = (0.03 R)^2, h_window[11] (host) the normalised Gaussian taps used as their outer product, sigma^2 =
+ *      E[x^2] - mu^2, mean over B*C and the (H-10) x (W-10) windows that lie inside the image.  out_mse = mean (p - t)^2 over every
+ *      pixel.  Two device scalars, no host read-back, no atomics: fixed-order two-stage sums (deterministic), moments in double.
+ *      workspace: lse_image_metrics_workspace bytes (8-byte aligned), written. */
+int lse_image_metrics_workspace(int32_t B, int32_t C, int32_t H, int32_t W, int64_t *h_bytes);
+int lse_image_metrics(const float *preds, const float *target, int32_t B, int32_t C, int32_t H, int32_t W, const float *h_window,
+                      void *workspace, int64_t workspace_bytes, float *out_ssim, float *out_mse, lse_stream_t stream);
+
 /* ---- occupancy grid (nerfacc OccGridEstimator._update) --------------------------- */
 /* occs[id] = max(occs[id]*ema_decay, occ_new); duplicate ids resolve to the maximum over the duplicates (upstream:
  * an arbitrary one of them wins).  workspace: n floats. */

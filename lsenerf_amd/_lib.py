@@ -22,6 +22,7 @@ LSE_ACT_NONE, LSE_ACT_SIGMOID = 0, 1
 LSE_ABI_VERSION = 6
 LSE_MLP_ARITH_AUTO, LSE_MLP_ARITH_F32_MFMA = 0, 1
 LSE_TRAVERSE_FMA_SETUP = 1
+LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
 
 
 class GridDesc(Structure):
@@ -97,6 +98,9 @@ SIGNATURES = {
     "lse_volrend_fwd": [P, P, P, P, I32, P, I32, P, P, P, P, P],
     "lse_volrend_bwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P],
     "lse_volrend_depth_fwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P, P],
+    "lse_eval_composite": [P, P, P, P, I32, P, I32, I32, F32, P, P, P, P, P, P],
+    "lse_image_metrics_workspace": [I32, I32, I32, I32, POINTER(c_int64)],
+    "lse_image_metrics": [P, P, I32, I32, I32, I32, P, P, I64, P, P, P],
     "lse_render_weight_fwd": [P, P, P, P, I32, P, P, P, P],
     "lse_render_weight_bwd": [P, P, P, P, I32, P, P, P, P],
     "lse_loss_epilogue_fwd": [POINTER(EpilogueDesc), P, P, I32, P, P, P, P, I32, P, P, P, POINTER(MapperMlp), POINTER(MapperMlp), P, P],

@@ -115,6 +115,101 @@ __global__ __launch_bounds__(1024) void depth_finish_kernel(const float *__restr
     }
 }
 
+// torch.nan_to_num with its defaults: NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX
+__device__ __forceinline__ float nan_to_num(float v)
+{
+    if (v != v) return 0.f;
+    if (v == INFINITY) return 3.402823466e+38f;
+    if (v == -INFINITY) return -3.402823466e+38f;
+    return v;
+}
+
+// torch.clamp(v, 0, 1): NaN stays NaN
+__device__ __forceinline__ float clamp01(float v)
+{
+    if (v != v) return v;
+    return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+}
+
+// Forward-only compositing of an evaluation render (lse_eval_composite): the per-ray walk of volrend_fwd_kernel with the SAME
+// arithmetic -- contraction is off in this body and every fused step is an explicit fmaf, so that the contraction choices the
+// compiler made in volrend_fwd_kernel are reproduced, not re-decided (HIP's __fadd_rn / __fmul_rn are plain operators whose fusing
+// follows the flags of their own definition, so they cannot pin this): the first step of the sigma*dt prefix scan is a fused multiply-add there (sd + neighbour, sd = sigma * dt), the
+// accumulation sum is a plain add, the colour / depth sums are fmaf.  No per-sample weights are stored.  Lane 0 applies the
+// renderer epilogue of LSENeRFModel.render_packed per ray; the depth numerator and the ray's mid-point range go to the workspace
+// for eval_depth_finish (depth_finish_kernel: the chunk-wide clip range of DepthRenderer("expected")).
+__global__ __launch_bounds__(256) void eval_composite_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                             const float *__restrict__ sigma, const float *__restrict__ rgb,
+                                                             int rgb_stride, const int64_t *__restrict__ packed, int n_rays,
+                                                             int flags, float background, float *__restrict__ mid_range,
+                                                             float *__restrict__ num, float *__restrict__ out_rgb,
+                                                             float *__restrict__ out_acc, int64_t *__restrict__ out_nsamples)
+{
+#pragma clang fp contract(off)   // every + - * below rounds on its own; the fused steps are the explicit fmaf
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
+    const bool fix_nan = (flags & LSE_EVAL_NAN_TO_NUM) != 0;
+    float carry = 0.f, ar = 0.f, ag = 0.f, ab = 0.f, aw = 0.f, ad = 0.f;
+    float mlo = INFINITY, mhi = -INFINITY;
+    for (int64_t base = 0; base < cnt; base += 64) {
+        const int64_t i = s0 + base + lane;
+        const bool valid = base + lane < cnt;
+        float a = 0.f, b = 0.f, sg = 0.f;
+        if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
+        const float dt = b - a;
+        const float sd = sg * dt;
+        float incl = sd;
+        {
+            const float nb = __shfl_up(incl, 1, 64);
+            if (lane >= 1) incl = fmaf(sg, dt, nb);
+        }
+#pragma unroll
+        for (int off = 2; off < 64; off <<= 1) {
+            const float nb = __shfl_up(incl, off, 64);
+            if (lane >= off) incl = incl + nb;
+        }
+        const float excl = (incl - sd) + carry;
+        const float T = expf(-excl);
+        const float alpha = 1.f - expf(-sd);
+        const float w = valid ? T * alpha : 0.f;
+        if (valid) {
+            const float mid = (a + b) * 0.5f;
+            mlo = fminf(mlo, mid);
+            mhi = fmaxf(mhi, mid);
+            const float *c = rgb + i * rgb_stride;
+            float c0 = c[0], c1 = c[1], c2 = c[2];
+            if (fix_nan) { c0 = nan_to_num(c0); c1 = nan_to_num(c1); c2 = nan_to_num(c2); }
+            ar = fmaf(w, c0, ar);
+            ag = fmaf(w, c1, ag);
+            ab = fmaf(w, c2, ab);
+            aw = aw + w;
+            ad = fmaf(w, mid, ad);
+        }
+        carry = carry + __shfl(incl, 63, 64);
+    }
+    ar = lse::wave_sum(ar); ag = lse::wave_sum(ag); ab = lse::wave_sum(ab);
+    aw = lse::wave_sum(aw); ad = lse::wave_sum(ad);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mlo = fminf(mlo, __shfl_xor(mlo, off, 64));
+        mhi = fmaxf(mhi, __shfl_xor(mhi, off, 64));
+    }
+    if (lane == 0) {
+        if (flags & LSE_EVAL_BACKGROUND) {     // rgb + bg * (1 - acc)
+            const float rest = background * (1.f - aw);
+            ar = ar + rest; ag = ag + rest; ab = ab + rest;
+        }
+        if (flags & LSE_EVAL_CLAMP) { ar = clamp01(ar); ag = clamp01(ag); ab = clamp01(ab); }
+        out_rgb[ray * 3 + 0] = ar; out_rgb[ray * 3 + 1] = ag; out_rgb[ray * 3 + 2] = ab;
+        out_acc[ray] = aw;
+        num[ray] = ad;
+        mid_range[2 * ray] = mlo; mid_range[2 * ray + 1] = mhi;
+        out_nsamples[ray] = cnt;
+    }
+}
+
 __global__ __launch_bounds__(256) void volrend_bwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                           const float *__restrict__ sigma, const float *__restrict__ rgb,
                                                           int rgb_stride, const int64_t *__restrict__ packed, int n_rays,
@@ -338,6 +433,27 @@ extern "C" int lse_volrend_depth_fwd(const float *t_starts, const float *t_ends,
     hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(1024), 0, st, out_depth_num, out_acc, mid_range, n_rays,
                        out_depth, depth_range);
     return lse::check_launch("lse_volrend_depth_fwd");
+}
+
+extern "C" int lse_eval_composite(const float *t_starts, const float *t_ends, const float *sigmas, const float *rgb,
+                                  int32_t rgb_stride, const int64_t *packed_info, int32_t n_rays, int32_t flags, float background,
+                                  float *workspace, float *out_rgb, float *out_acc, float *out_depth, int64_t *out_nsamples,
+                                  lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_eval_composite: n_rays < 0");
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(t_starts && t_ends && sigmas && rgb && packed_info && workspace && out_rgb && out_acc && out_depth && out_nsamples,
+                "lse_eval_composite: null pointer");
+    LSE_REQUIRE(rgb_stride >= 3, "lse_eval_composite: rgb_stride < 3");
+    LSE_REQUIRE((flags & ~(LSE_EVAL_NAN_TO_NUM | LSE_EVAL_BACKGROUND | LSE_EVAL_CLAMP)) == 0, "lse_eval_composite: unknown flags %d",
+                flags);
+    hipStream_t st = lse::as_stream(stream);
+    float *mid_range = workspace, *num = workspace + 2 * (int64_t)n_rays;
+    hipLaunchKernelGGL(eval_composite_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, st, t_starts, t_ends, sigmas, rgb, rgb_stride,
+                       packed_info, n_rays, flags, background, mid_range, num, out_rgb, out_acc, out_nsamples);
+    hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(1024), 0, st, (const float *)num, (const float *)out_acc,
+                       (const float *)mid_range, n_rays, out_depth, (float *)nullptr);
+    return lse::check_launch("lse_eval_composite");
 }
 
 extern "C" int lse_render_weight_fwd(const float *t_starts, const float *t_ends, const float *sigmas,

@@ -1,0 +1,228 @@
+"""Whole-image evaluation: the ``Model`` surface the reference's pipeline calls at eval time.
+
+* ``render_ray_bundle`` -- nerfstudio 0.3.2 ``Model.get_outputs_for_camera_ray_bundle`` (chunks of ``eval_num_rays_per_chunk`` rays
+  through ``forward``, outputs concatenated and viewed as ``[*leading shape, C]``).  In eval mode with ``LSEField`` every chunk takes
+  the count-free route instead: deferred sampling (no sample count read back), ``density_packed`` / ``rgb_packed`` with the
+  device-side count, and ``lse_eval_composite`` writing the chunk's rows of the image buffers directly -- no host synchronisation
+  inside the loop, no per-sample ``RaySamples`` gathers, no autograd Functions.  Its values are those of the ``forward`` loop bit for
+  bit (the mapper keys, formed once over the whole image, to GEMM rounding).
+* ``image_metrics_and_images`` -- R:lse_nerf/lsenerf.py:477-530 restated: psnr / ssim from one ``lse_image_metrics`` launch, lpips
+  when torchmetrics is importable, and the image dictionary (no "overlay": it needs OpenCV's Canny).
+* ``make_lpips`` -- torchmetrics' ``LearnedPerceptualImagePatchSimilarity(normalize=True)``, or a callable that names what is missing.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+from torch import Tensor
+
+from . import ops
+from .field import LSEField
+from .rays import RayBundle
+from .renderer import LinearRenderer
+
+_BUNDLE_FIELDS = ("origins", "directions", "pixel_area", "camera_indices", "nears", "fars", "times")
+
+
+def _flatten_bundle(bundle, device=None) -> RayBundle:
+    """This package's ``RayBundle`` with every tensor of ``bundle`` (any object with nerfstudio's attribute names) as ``[R, ...]``
+    rows, row-major over its leading shape (nerfstudio's ``get_row_major_sliced_ray_bundle`` order)."""
+    lead = tuple(bundle.origins.shape[:-1])
+    n = 1
+    for s in lead:
+        n *= int(s)
+
+    def flat(t):
+        if t is None:
+            return None
+        t = t.reshape(n, *t.shape[len(lead):])
+        return t.to(device) if device is not None else t     # (a bundle built on the host goes to the model's device)
+    meta = getattr(bundle, "metadata", None) or {}
+    return RayBundle(**{k: flat(getattr(bundle, k, None)) for k in _BUNDLE_FIELDS},
+                     metadata={k: flat(v) for k, v in meta.items() if torch.is_tensor(v)})
+
+
+def _slice(rb: RayBundle, lo: int, hi: int) -> RayBundle:
+    part = lambda t: t[lo:hi] if t is not None else None
+    return RayBundle(**{k: part(getattr(rb, k)) for k in _BUNDLE_FIELDS}, metadata={k: v[lo:hi] for k, v in rb.metadata.items()})
+
+
+def uses_count_free_route(model, num_rays: int) -> bool:
+    """Whether ``render_ray_bundle`` takes the count-free route for an image of ``num_rays`` rays (else the ``forward`` loop)."""
+    fld = model.field
+    if model.training or not isinstance(fld, LSEField) or model.sampler._packed_field is not fld or model.collider is not None:
+        return False
+    base = fld.mlp_base_mlp
+    if base.in_pad != base.in_dim:          # the small-grid base MLP has no device-side count (LSEField._base_mlp)
+        return False
+    return model.use_deferred_counts(min(int(model.config.eval_num_rays_per_chunk), max(num_rays, 1)))
+
+
+def _render_loop(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
+    """nerfstudio's loop: ``forward`` per chunk, tensor outputs concatenated."""
+    lists: Dict[str, list] = {}
+    for lo in range(0, len(rb), chunk):
+        out = model.forward(ray_bundle=_slice(rb, lo, min(len(rb), lo + chunk)))
+        for k, v in out.items():
+            if torch.is_tensor(v):
+                lists.setdefault(k, []).append(v)
+    return {k: torch.cat(v) for k, v in lists.items()}
+
+
+def _render_count_free(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
+    cfg, fld = model.config, model.field
+    R = len(rb)
+    dev = rb.origins.device
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    acc = torch.empty(R, dtype=torch.float32, device=dev)
+    depth = torch.empty(R, dtype=torch.float32, device=dev)
+    nsamples = torch.empty(R, dtype=torch.int64, device=dev)
+    ws = torch.empty(3 * min(chunk, R), dtype=torch.float32, device=dev)
+    linear = isinstance(model.renderer_rgb, LinearRenderer)
+    bg = cfg.background_color
+    background = None if bg in ("random", "last_sample") else {"black": 0.0, "white": 1.0}[bg]
+    fld._prepass = None                   # pre-pass features belong to a training step, never to these samples
+    for lo in range(0, R, chunk):
+        hi = min(R, lo + chunk)
+        part = _slice(rb, lo, hi)
+        ri, ts, te, packed, n_dev = model.sampler.sample_packed(
+            part, near_plane=cfg.near_plane, far_plane=cfg.far_plane, render_step_size=cfg.render_step_size,
+            alpha_thre=cfg.alpha_thre, cone_angle=cfg.cone_angle)
+        rays_o, rays_d = part.origins.contiguous(), part.directions.contiguous()
+        sigma, h, _ = fld.density_packed(rays_o, rays_d, ri, ts, te, packed, n_dev)
+        table, eidx = fld._eval_emb(hi - lo, dev) if fld.embedding_appearance is not None else (None, None)
+        head = fld.rgb_packed(h, rays_d, eidx, ri, packed, table, n_dev)
+        ops.eval_composite(ts, te, sigma, head, packed, rgb[lo:hi], acc[lo:hi], depth[lo:hi], nsamples[lo:hi],
+                           nan_to_num=not linear, background=background, clamp=not linear, workspace=ws)
+    model.occupancy_grid.check_deferred_overflow()      # the one read-back: a truncated ray raises here
+    raw = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": nsamples}
+    return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
+
+
+@torch.no_grad()
+def render_flat(model, rb: RayBundle) -> Dict[str, Tensor]:
+    """Outputs ``[R, ...]`` for the ``[R, ...]`` bundle ``rb``, chunked by ``config.eval_num_rays_per_chunk`` on every route (the
+    chunking is observable: nerfstudio's fake sample is inserted per chunk)."""
+    chunk = int(model.config.eval_num_rays_per_chunk)
+    if chunk <= 0:
+        raise ValueError("eval_num_rays_per_chunk must be positive")
+    if len(rb) == 0:
+        raise ValueError("empty ray bundle")
+    if uses_count_free_route(model, len(rb)):
+        return _render_count_free(model, rb, chunk)
+    return _render_loop(model, rb, chunk)
+
+
+@torch.no_grad()
+def render_ray_bundle(model, camera_ray_bundle) -> Dict[str, Tensor]:
+    lead = tuple(camera_ray_bundle.origins.shape[:-1])
+    out = render_flat(model, _flatten_bundle(camera_ray_bundle, device=model.scene_aabb.device))
+    return {k: v.reshape(*lead, -1) for k, v in out.items()}
+
+
+@torch.no_grad()
+def render_camera(model, cameras, camera_index: int, camera_opt_to_camera: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Every pixel of camera ``camera_index`` of ``cameras`` (``EdCameras``): ``generate_rays`` over ``get_image_coords()``, then
+    ``render_ray_bundle``; outputs ``[H, W, C]``."""
+    coords = cameras.get_image_coords()
+    H, W = coords.shape[:2]
+    idx = torch.full((H * W,), int(camera_index), dtype=torch.long)
+    rb = cameras.generate_rays(idx, coords.reshape(-1, 2), camera_opt_to_camera=camera_opt_to_camera)
+    dev = model.scene_aabb.device
+    out = render_flat(model, _flatten_bundle(rb, device=dev))
+    return {k: v.reshape(H, W, -1) for k, v in out.items()}
+
+
+# ----------------------------------------------------------------------------------------------------
+# metrics and images
+# ----------------------------------------------------------------------------------------------------
+class _MissingLPIPS:
+    """Stands in for LPIPS where torchmetrics is absent: calling it raises ModuleNotFoundError naming what is missing."""
+    available = False
+
+    def __init__(self, missing: str):
+        self.missing = missing
+
+    def __call__(self, *args, **kwargs):
+        raise ModuleNotFoundError(
+            f"lpips needs torchmetrics' LearnedPerceptualImagePatchSimilarity(normalize=True), and '{self.missing}' is not "
+            f"installed (its network weights are not part of this package either)", name=self.missing)
+
+
+class _LPIPS:
+    """torchmetrics LPIPS, moved to the device of its first input."""
+    available = True
+
+    def __init__(self, metric):
+        self.metric = metric
+
+    def __call__(self, preds: Tensor, target: Tensor) -> Tensor:
+        if next(self.metric.parameters(), preds).device != preds.device:
+            self.metric = self.metric.to(preds.device)
+        return self.metric(preds, target)
+
+
+def make_lpips():
+    try:
+        from torchmetrics.image.lpip import LearnedPerceptualImagePatchSimilarity
+    except ModuleNotFoundError as e:
+        return _MissingLPIPS((e.name or "torchmetrics").split(".")[0])
+    return _LPIPS(LearnedPerceptualImagePatchSimilarity(normalize=True))
+
+
+def make_error_map(image: Tensor, pred: Tensor, norm_cnst: float = 6.0) -> Tensor:
+    """R:lse_nerf/lsenerf.py:442-460 restated: white where the grey levels agree; where the ground truth is brighter the green and
+    blue channels drop by ``6 * difference`` (red remains), where it is darker red and green drop (blue remains)."""
+    gray = lambda x: (x * x.new_tensor([0.2989, 0.5870, 0.1140])).sum(-1)
+    err = (gray(image) - gray(pred)) * norm_cnst
+    one = torch.ones_like(err)
+    pos, neg = err > 0, err < 0
+    r = torch.where(neg, 1 - err.abs(), one)
+    g = torch.where(pos, 1 - err, torch.where(neg, 1 - err.abs(), one))
+    b = torch.where(pos, 1 - err, one)
+    return torch.stack([r, g, b], dim=-1)
+
+
+def gray_colormap(image: Tensor, invert: bool = False) -> Tensor:
+    """nerfstudio 0.3.2 ``apply_colormap`` of a one-channel float image with ``colormap="gray"``: clip to [0, 1], optionally
+    ``1 - x``, three channels."""
+    out = torch.clip(image, 0, 1)
+    if invert:
+        out = 1 - out
+    return out.repeat(*([1] * (out.dim() - 1)), 3)
+
+
+def depth_gray_map(depth: Tensor, accumulation: Tensor) -> Tensor:
+    """nerfstudio 0.3.2 ``apply_depth_colormap(depth, accumulation, ColormapOptions(colormap="gray", invert=True))``: depth
+    normalised by its own min / max, grey map inverted (near = white), blended with the accumulation onto white.  Restated, parity
+    unpinned."""
+    near, far = torch.min(depth), torch.max(depth)
+    d = torch.clip((depth - near) / (far - near + 1e-10), 0, 1)
+    return gray_colormap(d, invert=True) * accumulation + (1 - accumulation)
+
+
+@torch.no_grad()
+def image_metrics_and_images(model, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]):
+    dev = outputs["rgb"].device
+    image = batch["image"].to(dev)
+    rgb = ori_rgb = outputs["rgb"]
+    if batch.get("msk") is not None:
+        msk = batch["msk"].to(dev)[..., None]
+        image, rgb = image * msk, rgb * msk
+    images = {"img": torch.cat([image, ori_rgb], dim=1),      # the unmasked prediction beside the (masked) ground truth
+              "accumulation": gray_colormap(outputs["accumulation"]),
+              "depth": depth_gray_map(outputs["depth"], outputs["accumulation"]),
+              "err_map": make_error_map(image, rgb)}
+    if outputs.get("ev_out") is not None:
+        images["ev_out"] = outputs["ev_out"]
+    img_b = torch.moveaxis(image, -1, 0)[None].float().contiguous()     # [H, W, C] -> [1, C, H, W]
+    rgb_b = torch.moveaxis(rgb, -1, 0)[None].float().contiguous()
+    ssim, mse = ops.image_metrics(img_b, rgb_b)
+    psnr = 10.0 * torch.log10(1.0 / mse)
+    values = torch.stack([psnr, ssim]).tolist()
+    metrics = {"psnr": float(values[0]), "ssim": float(values[1])}
+    lpips = model.lpips
+    if getattr(lpips, "available", True):
+        metrics["lpips"] = float(lpips(img_b, rgb_b))
+    return metrics, images

@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
-from . import ops
+from . import evaluation, ops
 from .field import LSEEmbeddingConfig, LSEField
 from .grid_estimator import LSEOccGridEstimator
 from .rays import Frustums, RayBundle, RaySamples, SceneBox, SceneContraction
@@ -444,6 +444,47 @@ class LSENeRFModel(nn.Module):
     def psnr(preds: Tensor, target: Tensor) -> Tensor:
         """torchmetrics ``PeakSignalNoiseRatio(data_range=1.0)`` as NGPModel holds it: 10 log10(1 / mse)."""
         return 10.0 * torch.log10(1.0 / F.mse_loss(preds, target))
+
+    def ssim(self, preds: Tensor, target: Tensor) -> Tensor:
+        """torchmetrics ``structural_similarity_index_measure(preds, target)`` with its defaults (the reference's ``self.ssim``,
+        R:lse_nerf/lsenerf.py:206) for [B,C,H,W] images, H and W >= 11: a 0-dim device tensor from one ``lse_image_metrics`` launch.
+        Restated from torchmetrics' published algorithm, which is not a dependency here: that parity is unpinned."""
+        return ops.image_metrics(preds.float().contiguous(), target.float().contiguous())[0]
+
+    @property
+    def lpips(self):
+        """torchmetrics ``LearnedPerceptualImagePatchSimilarity(normalize=True)`` (R:lse_nerf/lsenerf.py:207), built on first use.
+        Without torchmetrics a callable that raises ModuleNotFoundError naming the missing module (``.available`` is False)."""
+        fn = self.__dict__.get("_lpips_fn")
+        if fn is None:
+            fn = self.__dict__["_lpips_fn"] = evaluation.make_lpips()
+        return fn
+
+    # -- evaluation (nerfstudio 0.3.2 Model.get_outputs_for_camera_ray_bundle; R:lse_nerf/lsenerf.py:477-530) ------------------
+    @torch.no_grad()
+    def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle) -> Dict[str, Tensor]:
+        """Render a whole camera bundle (tensors of any leading shape, usually [H, W]; this package's ``RayBundle`` or nerfstudio's)
+        in chunks of ``config.eval_num_rays_per_chunk`` rays.  Returns [*leading shape, C] tensors: "rgb", "accumulation", "depth",
+        "num_samples_per_ray" and the keys ``route_outputs`` adds in eval mode.  In eval mode with ``LSEField`` the chunks take the
+        count-free route (no host synchronisation until one overflow check after the last chunk; ``lse_eval_composite`` writes the
+        image rows); otherwise -- training mode, another field, a capacity above ``deferred_max_slots`` -- ``forward`` runs per
+        chunk as in nerfstudio.  Both routes give the same values (lsenerf_amd.evaluation)."""
+        return evaluation.render_ray_bundle(self, camera_ray_bundle)
+
+    @torch.no_grad()
+    def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]):
+        """R:lse_nerf/lsenerf.py:477-530: ``(metrics, images)`` for a rendered [H, W, 3] image and ``batch["image"]`` (times
+        ``batch["msk"]`` when present).  metrics: "psnr" (10 log10(1 / mse)) and "ssim" from one ``lse_image_metrics`` launch, plus
+        "lpips" only where torchmetrics is importable -- the key is omitted otherwise.  images: "img" (ground truth beside the
+        unmasked prediction), "err_map", grey "accumulation" and "depth" maps, and "ev_out" when rendered.  The reference's
+        "overlay" needs OpenCV's Canny edges and is not produced."""
+        return evaluation.image_metrics_and_images(self, outputs, batch)
+
+    @torch.no_grad()
+    def render_camera(self, cameras, camera_index: int, camera_opt_to_camera: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """Every pixel of one camera of ``cameras`` (``EdCameras``) rendered through ``get_outputs_for_camera_ray_bundle``:
+        [H, W, C] outputs.  ``camera_opt_to_camera``: a pose correction as ``EdCameras.generate_rays`` takes it."""
+        return evaluation.render_camera(self, cameras, camera_index, camera_opt_to_camera)
 
     def _ngp_metrics_dict(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]) -> Dict[str, Tensor]:
         image = batch["image"].to(outputs["rgb"].device)

@@ -312,6 +312,8 @@ def visibility_compact_deferred(ray_indices, t_starts, t_ends, sigmas, packed_in
 def ray_planes(n_rays: int, device, near_plane: float, far_plane: float, t_min=None, t_max=None, jitter=None,
                step_size: float = 0.0):
     """(near_planes[R], far_planes[R]) of R:lse_nerf/lse_grid_estimator.py:83-92 in one launch."""
+    if torch.device(device).type != "cuda":      # the kernel writes both outputs: host memory would be written from the GPU
+        raise _lib.LseHipError(f"ray_planes: rays must live on the GPU (got {device}); the HIP path has no CPU fallback")
     near = torch.empty(n_rays, dtype=torch.float32, device=device)
     far = torch.empty(n_rays, dtype=torch.float32, device=device)
     keep = [x for x in (t_min, t_max, jitter) if x is not None]      # (contiguous views stay alive through `keep`)
@@ -997,6 +999,70 @@ def volume_render_depth(t_starts, t_ends, sigmas, rgb, packed_info):
     """``volume_render`` + the DepthRenderer("expected") epilogue (R:lse_nerf/lsenerf.py:315-317) in one call:
     returns (rgb[R,3], accumulation[R], depth[R] = clip(num / (acc + 1e-10), min mid-point, max mid-point), weights[N])."""
     return _VolRendFn.apply(t_starts, t_ends, sigmas, rgb, packed_info, True)
+
+
+@torch.no_grad()
+def eval_composite(t_starts, t_ends, sigmas, rgb, packed_info, out_rgb, out_acc, out_depth, out_nsamples,
+                   nan_to_num: bool, background: Optional[float], clamp: bool, workspace: Optional[torch.Tensor] = None):
+    """Forward-only compositing of an evaluation render (lse_eval_composite): the values ``volume_render_depth`` and the renderer
+    epilogue of ``LSENeRFModel.render_packed`` produce, bit for bit, written into ``out_rgb [n,3]``, ``out_acc [n]``, ``out_depth [n]``
+    and ``out_nsamples [n]`` (int64) -- contiguous row blocks (views) of the caller's image buffers.  Sample arrays may have capacity
+    extent (``packed_info`` rows are authoritative); ``rgb`` is the head output [N, >=3].  ``nan_to_num``: per-sample
+    torch.nan_to_num of the colour; ``background``: blend ``rgb + background * (1 - acc)`` (None: no blend); ``clamp``:
+    clamp(0, 1).  ``workspace``: float32, at least 3 n elements (allocated when absent)."""
+    n = packed_info.shape[0]
+    if n == 0:
+        return
+    if out_rgb.shape != (n, 3) or out_acc.shape != (n,) or out_depth.shape != (n,) or out_nsamples.shape != (n,):
+        raise ValueError("eval_composite: out_rgb [n,3], out_acc / out_depth / out_nsamples [n] expected")
+    if workspace is None:
+        workspace = torch.empty(3 * n, dtype=torch.float32, device=packed_info.device)
+    elif workspace.numel() < 3 * n:
+        raise ValueError(f"eval_composite: workspace of {workspace.numel()} floats, {3 * n} needed")
+    flags = (_lib.LSE_EVAL_NAN_TO_NUM if nan_to_num else 0) | (_lib.LSE_EVAL_BACKGROUND if background is not None else 0) \
+        | (_lib.LSE_EVAL_CLAMP if clamp else 0)
+    _lib.call("lse_eval_composite", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(sigmas, "sigmas"), _rgb_ptr(rgb),
+              rgb.stride(0), _chk(packed_info, torch.int64, "packed_info"), n, flags,
+              float(background) if background is not None else 0.0, _f32(workspace, "workspace"), _f32(out_rgb, "out_rgb"),
+              _f32(out_acc, "out_acc"), _f32(out_depth, "out_depth"), _chk(out_nsamples, torch.int64, "out_nsamples"), _stream())
+
+
+def ssim_window(size: int = 11, sigma: float = 1.5) -> torch.Tensor:
+    """torchmetrics' 1-D Gaussian window in float32: exp(-(d / sigma)^2 / 2) for d = -(size-1)/2 .. (size-1)/2, normalised.  The
+    image-metrics kernel takes these taps from the host (their outer product is the 2-D window), so kernel and test oracle share them."""
+    d = torch.arange((1 - size) / 2, (1 + size) / 2, 1.0, dtype=torch.float32)
+    g = torch.exp(-torch.pow(d / sigma, 2) / 2)
+    return g / g.sum()
+
+
+_SSIM_WINDOW = None
+
+
+def image_metrics_workspace_bytes(B: int, C: int, H: int, W: int) -> int:
+    v = ctypes.c_int64(0)
+    _lib.call("lse_image_metrics_workspace", int(B), int(C), int(H), int(W), ctypes.byref(v))
+    return int(v.value)
+
+
+@torch.no_grad()
+def image_metrics(preds: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ssim, mse): two 0-dim float32 device tensors for ``preds`` / ``target`` [B,C,H,W] f32 (lse_image_metrics; H, W >= 11).
+    SSIM is torchmetrics' ``structural_similarity_index_measure(preds, target)`` with its defaults (Gaussian 11-tap window, sigma 1.5,
+    data range from the inputs, K = (0.01, 0.03), mean over the valid windows), restated from the published algorithm: torchmetrics
+    is not a dependency, so that parity is UNPINNED -- the tests hold the kernel against a float64 numpy restatement.  MSE is the mean
+    squared difference over every pixel.  Nothing is read back to the host."""
+    global _SSIM_WINDOW
+    if preds.dim() != 4 or preds.shape != target.shape:
+        raise ValueError(f"image_metrics: preds and target must both be [B,C,H,W] (got {tuple(preds.shape)} and {tuple(target.shape)})")
+    B, C, H, W = preds.shape
+    nbytes = image_metrics_workspace_bytes(B, C, H, W)       # refuses H or W < 11 with the library's message
+    if _SSIM_WINDOW is None:
+        _SSIM_WINDOW = (ctypes.c_float * 11)(*ssim_window().tolist())
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=preds.device)
+    out = torch.empty(2, dtype=torch.float32, device=preds.device)
+    _lib.call("lse_image_metrics", _f32(preds, "preds"), _f32(target, "target"), B, C, H, W, _SSIM_WINDOW,
+              ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(out.data_ptr() + 4), _stream())
+    return out[0], out[1]
 
 
 # ----------------------------------------------------------------------------------------------------
