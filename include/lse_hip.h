@@ -461,6 +461,98 @@ int lse_adam_step_dev(float *params, const float *grads, float *exp_avg, float *
  * the host runs ahead, and follows a changed learning-rate schedule without being captured again. */
 int lse_adam_schedule_dev(int64_t *step, float *hyper, const double *sched, lse_stream_t stream);
 
+/* ---- batch composer: the data manager's hot loop (R:lse_nerf/lse_datamanager.py:337-372) as one launch -------------------
+ * The scene's pixels and camera tables live in device memory; one launch draws the pixels of a step, gathers their targets and
+ * writes the rays and the metadata of all three bundles (colour | previous events | next events) into caller-owned buffers.
+ *   draw     (c, y, x) of pixel i of a stream: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (step & 0xffffffff, i,
+ *            stream id (0 colour / 1 events), 0); c = mulhi32(w0, n_images), y = mulhi32(w1, H), x = mulhi32(w2, W).  This
+ *            library's own convention (uniform i.i.d. over images x pixels); no bit parity with any torch generator.
+ *   gather   colour target float(u8) / 255.0f, event target float(e) * e_scale, mask, appearance id, camera = image_idx[c].
+ *   rays     EdCameras.generate_rays (R:lse_nerf/lse_cameras.py:340-586): no half-pixel offset, the camera-frame points of
+ *            (x, y), (x+1, y), (x, y+1), the 10-step Newton undistortion, rotation by a pose read from a POSE TABLE, pixel_area,
+ *            directions_norm.  Origins are copies of the table's translation.
+ *   metadata as R:lse_nerf/utils.py:153-194 (add_metadata) and R:lse_nerf/data_components.py:70-90 (CameraIdxFixer, from a table).
+ * Ray rows: colour pixel i owns rows row_col + i*G + k (k-th virtual camera of a deblur pixel, G = 4; else G = 1), event pixel j owns
+ * row_prev + j and row_next + j.  Per-pixel batch rows are i and j. */
+#define LSE_PIX_I8 0
+#define LSE_PIX_U8 1
+#define LSE_PIX_I16 2
+#define LSE_PIX_I32 3
+#define LSE_PIX_F32 4
+#define LSE_PIX_NONE (-1)
+typedef struct lse_compose_stream {      /* one camera set: colour or events */
+    float fx, fy, cx, cy;
+    float dist[6];          /* (k1, k2, k3, k4, p1, p2); read when `distort` != 0 */
+    int32_t H, W;
+    int32_t n_images;       /* resident images: the range of the drawn c */
+    int32_t n_cameras;      /* cameras of the set = rows of its per-camera tables (pose table rows / G) */
+    int32_t n_pixels;       /* pixels sampled per step from this stream (0: stream absent) */
+    int32_t pix_type;       /* LSE_PIX_* of `images` (colour: LSE_PIX_U8, three channels) */
+    int32_t msk_type;       /* LSE_PIX_U8 | LSE_PIX_F32 | LSE_PIX_NONE */
+    int32_t distort;        /* non-zero: undistort with `dist` */
+} lse_compose_stream;
+typedef struct lse_compose_desc {
+    lse_compose_stream col, evs;
+    int32_t G;              /* rays per colour pixel: 1, or 4 (deblur) */
+    int32_t num_embd;       /* colour appearance ids with G = 4 are id + (k - 2) clipped to [0, num_embd - 1] */
+    int32_t consecutive;    /* 1: ConsecRayGenerator -- the next bundle reads the prev tables at camera + 1 (needs image_idx + 1 <
+                               evs.n_cameras); 0: PrevNextRayGenerator -- its own tables at the same camera */
+    float e_scale;          /* event target = float(e) * e_scale (the contrast threshold for integer frames; 1 for LSE_PIX_F32) */
+    float e_thresh;         /* written per event ray */
+    uint64_t seed;
+} lse_compose_desc;
+/* device pointers (the struct itself is host memory, read during the call); a stream with n_pixels == 0 may leave its rows NULL */
+typedef struct lse_compose_scene {
+    const uint8_t *col_images;        /* [n_images, H, W, 3] */
+    const void *col_msk;              /* [n_images, H, W] of msk_type, or NULL */
+    const int32_t *col_appearance_id; /* [n_images] */
+    const int32_t *col_image_idx;     /* [n_images] -> camera of the colour set */
+    const float *col_times;           /* [n_cameras] */
+    const float *col_pose;            /* [n_cameras, G, 3, 4] */
+    const void *evs_images;           /* [n_images, H, W] of pix_type */
+    const void *evs_msk;
+    const int32_t *evs_appearance_id;
+    const int32_t *evs_image_idx;
+    const float *prev_times, *next_times;            /* [n_cameras] (consecutive: the same table twice) */
+    const int32_t *prev_closest, *next_closest;      /* [n_cameras] index of the closest colour-camera time */
+    const float *prev_pose, *next_pose;              /* [n_cameras, 3, 4] */
+} lse_compose_scene;
+typedef struct lse_compose_out {
+    int32_t row_col, row_prev, row_next;   /* first ray row of each bundle in the per-ray buffers */
+    int32_t n_rows;                        /* rows of the per-ray buffers (checked against the three blocks) */
+    float *origins, *directions;           /* [n_rows, 3] */
+    float *pixel_area, *directions_norm, *times;   /* [n_rows, 1] */
+    int64_t *camera_indices;               /* [n_rows, 1] */
+    int32_t *appearance_id;                /* [n_rows, 1] */
+    int32_t *cam_type;                     /* [n_rows]    0 colour / 1 events */
+    int32_t *coords;                       /* [n_rows, 3] (camera, y, x); the colour block holds its pixel list G times over
+                                              (torch.tile, as add_metadata's fix_datashape leaves it) */
+    int32_t *ray_px;                       /* [n_rows, 3] (pose-table row, y, x) of every ray: what lse_compose_rays_bwd reads */
+    float *col_image;                      /* [col.n_pixels, 3] */
+    float *col_msk;                        /* [col.n_pixels, 1] or NULL */
+    int32_t *col_indices;                  /* [col.n_pixels, 3] (camera, y, x) */
+    int32_t *col_batch_appearance_id;      /* [col.n_pixels] */
+    float *evs_image;                      /* [evs.n_pixels, 1] */
+    float *evs_msk;
+    float *evs_e_thresh;                   /* [evs.n_pixels, 1] */
+    int32_t *evs_indices;
+    int32_t *evs_batch_appearance_id;
+} lse_compose_out;
+/* step: *step_dev (int64, device) when step_dev != NULL, else `step`; its low 32 bits enter the counter.  advance != 0 (needs
+ * step_dev): a one-thread launch behind the composer adds 1 to *step_dev, so replay k of a captured graph draws what an eager call
+ * with step k0 + k draws.  col_indices_in / evs_indices_in (int32 [n_pixels, 3] = (c, y, x), nullable): given pixels instead of the
+ * draw; values outside the scene are clamped into it. */
+int lse_compose_batch(const lse_compose_desc *desc, const lse_compose_scene *scene, const lse_compose_out *out, int64_t *step_dev,
+                      int64_t step, int32_t advance, const int32_t *col_indices_in, const int32_t *evs_indices_in,
+                      lse_stream_t stream);
+/* Gradient w.r.t. the pose tables from d_origins / d_directions [n_rows, 3] and the saved ray_px: d_col_pose [col.n_cameras, G, 3, 4],
+ * d_prev_pose / d_next_pose [evs.n_cameras, 3, 4] are OVERWRITTEN (rows no ray touched get zero).  The camera-frame point is
+ * recomputed.  One wave per table row sums its rays in a fixed order (no atomics): two runs are bit-equal.  consecutive != 0: both
+ * event bundles index ONE table, and d_prev_pose receives the sum of both (d_next_pose is ignored, NULL allowed). */
+int lse_compose_rays_bwd(const lse_compose_desc *desc, const lse_compose_scene *scene, const lse_compose_out *out,
+                         const float *d_origins, const float *d_directions, float *d_col_pose, float *d_prev_pose,
+                         float *d_next_pose, lse_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

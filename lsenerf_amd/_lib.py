@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LSE_HIP_LIB", os.path.join(_HERE, "liblse_hip.so"))   # override: A/B builds of the same ABI
@@ -57,6 +57,36 @@ LSE_EVLOSS_LOG, LSE_EVLOSS_ENERF_NORM = 0, 1
 class MlpDesc(Structure):
     _fields_ = [("n_in", c_int32), ("width", c_int32), ("n_hidden_layers", c_int32), ("out_activation", c_int32),
                 ("in_layout", c_int32), ("w0_ld", c_int32), ("w0_col", c_int32), ("w0_mask_col0", c_int32), ("arith", c_int32)]
+
+
+LSE_PIX_I8, LSE_PIX_U8, LSE_PIX_I16, LSE_PIX_I32, LSE_PIX_F32, LSE_PIX_NONE = 0, 1, 2, 3, 4, -1
+
+
+class ComposeStream(Structure):
+    """lse_compose_stream: one camera set (colour or events) of the batch composer."""
+    _fields_ = [("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("dist", c_float * 6), ("H", c_int32),
+                ("W", c_int32), ("n_images", c_int32), ("n_cameras", c_int32), ("n_pixels", c_int32), ("pix_type", c_int32),
+                ("msk_type", c_int32), ("distort", c_int32)]
+
+
+class ComposeDesc(Structure):
+    _fields_ = [("col", ComposeStream), ("evs", ComposeStream), ("G", c_int32), ("num_embd", c_int32), ("consecutive", c_int32),
+                ("e_scale", c_float), ("e_thresh", c_float), ("seed", c_uint64)]
+
+
+class ComposeScene(Structure):
+    """lse_compose_scene: device pointers of the resident scene and the pose tables."""
+    _fields_ = [(n, c_void_p) for n in (
+        "col_images", "col_msk", "col_appearance_id", "col_image_idx", "col_times", "col_pose", "evs_images", "evs_msk",
+        "evs_appearance_id", "evs_image_idx", "prev_times", "next_times", "prev_closest", "next_closest", "prev_pose", "next_pose")]
+
+
+class ComposeOut(Structure):
+    """lse_compose_out: row offsets and device pointers of the caller-owned output buffers."""
+    _fields_ = [("row_col", c_int32), ("row_prev", c_int32), ("row_next", c_int32), ("n_rows", c_int32)] + [(n, c_void_p) for n in (
+        "origins", "directions", "pixel_area", "directions_norm", "times", "camera_indices", "appearance_id", "cam_type", "coords",
+        "ray_px", "col_image", "col_msk", "col_indices", "col_batch_appearance_id", "evs_image", "evs_msk", "evs_e_thresh",
+        "evs_indices", "evs_batch_appearance_id")]
 
 
 P = c_void_p
@@ -111,6 +141,8 @@ SIGNATURES = {
     "lse_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, I32, F32, P],
     "lse_adam_step_dev": [P, P, P, P, I64, P, F32, P],
     "lse_adam_schedule_dev": [P, P, P, P],
+    "lse_compose_batch": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, I64, I32, P, P, P],
+    "lse_compose_rays_bwd": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, P, P, P, P, P],
 }
 # exported by the development build only (csrc/dev_knobs.h)
 DEV_SIGNATURES = {

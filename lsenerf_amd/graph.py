@@ -11,6 +11,8 @@ which is the capturing stream) and replayed with one call per step.
 
 What varies from step to step enters through device memory at fixed addresses:
   * the rays and targets of the step   -> copied into the static input tensors before the replay;
+    or, with ``composer=`` (lsenerf_amd.data.BatchComposer), drawn, gathered and generated INSIDE the graph by one launch
+    that writes straight into the static inputs, driven by a step counter in device memory: nothing is copied;
   * the stratified jitter              -> ``torch.rand`` inside the graph (graph-safe Philox offsets), or a static input;
   * the learning rate / bias corrections -> derived ON THE DEVICE from a step counter the graph itself advances
     (lse_adam_schedule_dev in front of lse_adam_step_dev): no per-step host -> device copy that a host running ahead could race;
@@ -219,24 +221,45 @@ class GraphedTrainStep:
     ``prefetch_march=True`` (module docstring): announce the next step's rays with ``next_bundles=(col, prev, nxt)`` (and
     ``next_jitter=`` for jitter="input") at every call and hand the next call those very tensors, unmodified.  A call whose rays are
     not the announced ones (other tensors, or the same ones written to in between) does not train on the wrong samples: the samples
-    marched ahead are dropped and the given rays marched before the replay (``remarched_unannounced`` counts these calls)."""
+    marched ahead are dropped and the given rays marched before the replay (``remarched_unannounced`` counts these calls).
+    ``composer=`` (``lsenerf_amd.data.BatchComposer``; no bundles, no batch): the static bundles and the static batch ARE the
+    composer's output buffers and the body starts with the compose launch, driven by the composer's device step counter -- replay k
+    draws what ``composer.compose(step=k0 + k)`` draws; ``step()`` takes no arguments and copies nothing.  With ``ray_grads=True`` the
+    body ends with ``lse_compose_rays_bwd`` and ``step.pose_grads`` ({"col", "prev", "next"}) holds the gradients of the composer's
+    pose tables; the caller continues with ``torch.autograd.backward(tables, grads)`` into its camera optimiser, eagerly, over
+    O(cameras) rows.  Not combined with ``prefetch_march`` (ValueError)."""
 
-    def __init__(self, model, opt: FlatAdam, col: Optional[RayBundle], prev: Optional[RayBundle], nxt: Optional[RayBundle],
-                 batch: Dict[str, object], ray_grads: bool = False, jitter: str = "graph", warmup: int = 3,
-                 grad_scale: float = 1.0, prefetch_march: bool = False, prefetch_fork: str = "hash_bwd",
-                 optimizer_in_graph: bool = True):
+    def __init__(self, model, opt: FlatAdam, col: Optional[RayBundle] = None, prev: Optional[RayBundle] = None,
+                 nxt: Optional[RayBundle] = None, batch: Optional[Dict[str, object]] = None, ray_grads: bool = False,
+                 jitter: str = "graph", warmup: int = 3, grad_scale: float = 1.0, prefetch_march: bool = False,
+                 prefetch_fork: str = "hash_bwd", optimizer_in_graph: bool = True, composer=None):
         assert jitter in ("graph", "input")
         assert model.training, "the captured step is the training step"
+        self.composer = composer
+        if composer is not None:
+            if prefetch_march:
+                raise ValueError("composer= with prefetch_march=True is not supported: the marcher of the next step would need the "
+                                 "next step's rays in a second set of buffers")
+            if col is not None or prev is not None or nxt is not None or batch is not None:
+                raise ValueError("with composer= the bundles and the batch are the composer's own buffers: pass none")
+        elif batch is None:
+            raise ValueError("example bundles and a batch fix the composition of the step (or pass composer=)")
         self.model, self.opt, self.grad_scale = model, opt, grad_scale
         # False: the graph ends with the backward pass and the caller finishes the step -- data parallel: all-reduce of
         # opt.flat.grad (lsenerf_amd.dist), then opt.step(grad_scale=1 / world) -- two more launches instead of ~25
         self.optimizer_in_graph = bool(optimizer_in_graph)
         self._deferred_before = (model.deferred_counts, model.deferred_max_slots)
         model.deferred_counts, model.deferred_max_slots = True, 1 << 62     # nothing inside the graph may wait for the host
-        self.col, self.prev, self.nxt = _static_bundles((col, prev, nxt))
+        if composer is not None:       # the static inputs ARE the composer's output buffers: nothing is copied in front of a replay
+            self.col, self.prev, self.nxt = composer.bundles
+            self.batch = composer.batch
+        else:
+            self.col, self.prev, self.nxt = _static_bundles((col, prev, nxt))
+            self.batch = self._static_batch(batch)
         self.want_ray_grads = bool(ray_grads)
         self._ray_leaves: Optional[Tuple[Tensor, Tensor]] = None      # (origins, directions) leaves of the last run of _body
-        self.batch = self._static_batch(batch)
+        # composer + ray_grads: gradients of the composer's pose tables, written by the last launch of every replay
+        self.pose_grads: Optional[Dict[str, Optional[Tensor]]] = None
         n_total = sum(len(b) for b in (self.col, self.prev, self.nxt) if b is not None)
         dev = opt.flat.data.device
         self.jitter = torch.rand(n_total, device=dev) if jitter == "input" else None
@@ -249,8 +272,13 @@ class GraphedTrainStep:
         self.replays = 0
         self._capture_stream = torch.cuda.Stream(device=dev)           # warm-up runs AND captures (capture_body)
         if not self.prefetch:
+            # (the warm-up runs advance the composer's device step counter like any eager compose(): put it back, in stream order)
+            k0 = composer.step_dev.clone() if composer is not None else None
             self.graph = capture_body(self._body, opt, model.occupancy_grid, warmup, stream=self._capture_stream,
                                       before_capture=self._drop_run)
+            if composer is not None:
+                with torch.no_grad():
+                    composer.step_dev.copy_(k0)
             return
         # -- marcher of the next step on a side stream: two graphs alternate between two sample buffers
         self.next_col, self.next_prev, self.next_nxt = _static_bundles((col, prev, nxt))
@@ -291,6 +319,8 @@ class GraphedTrainStep:
 
     def _body(self, premarched=None):
         self.opt.zero_grad()
+        if self.composer is not None:          # draw, gather, rays and metadata of this step; the device step counter ticks behind it
+            self.composer.compose()
         col, prev, nxt = self.col, self.prev, self.nxt
         if self.want_ray_grads:
             (col, prev, nxt), o, d = _fresh_ray_leaves((col, prev, nxt))
@@ -301,6 +331,10 @@ class GraphedTrainStep:
         # (the sum, its backward and the two ones_like fills were five ~5 us launches of every replay)
         vals = list(losses.values())
         torch.autograd.backward(vals, [self._one] * len(vals))
+        if self.composer is not None and self.want_ray_grads:      # d rays -> d pose tables (static tensors of the composer)
+            with torch.no_grad():
+                g = self.composer.pose_grads((o.grad, d.grad))
+            self.pose_grads = dict(zip(("col", "prev", "next"), g))
         if self.optimizer_in_graph:
             self.opt.step_staged(self.grad_scale)
         self.losses, self.outputs = losses, out
@@ -361,11 +395,15 @@ class GraphedTrainStep:
         """Gradients w.r.t. the rays of the last replayed step (each of the two alternating graphs owns its gradient tensors)."""
         return self._ray_grads_of[self._last] if self.prefetch else self._collect_ray_grads()
 
-    def __call__(self, col: Optional[RayBundle], prev: Optional[RayBundle], nxt: Optional[RayBundle], batch: Dict[str, object],
-                 jitter: Optional[Tensor] = None, next_bundles: Optional[Sequence[Optional[RayBundle]]] = None,
-                 next_jitter: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    def __call__(self, col: Optional[RayBundle] = None, prev: Optional[RayBundle] = None, nxt: Optional[RayBundle] = None,
+                 batch: Optional[Dict[str, object]] = None, jitter: Optional[Tensor] = None,
+                 next_bundles: Optional[Sequence[Optional[RayBundle]]] = None, next_jitter: Optional[Tensor] = None) -> Dict[str, Tensor]:
         if (next_bundles is not None or next_jitter is not None) and not self.prefetch:
             raise ValueError("next_bundles / next_jitter belong to a step built with prefetch_march=True")
+        if self.composer is not None:
+            return self._replay_composed(col, prev, nxt, batch, jitter)
+        if batch is None:
+            raise ValueError("this step was built from example bundles: every call brings its bundles and its batch")
         pairs: list = []
         _copy_pairs(self.col, col, pairs)
         _copy_pairs(self.prev, prev, pairs)
@@ -398,6 +436,25 @@ class GraphedTrainStep:
                 self._pm_version = None
                 self.remarched_unannounced += 1
             return self._replay_prefetch(next_bundles, next_jitter)
+        if self.optimizer_in_graph:
+            self.opt.prepare_step()
+        self.graph.replay()
+        self.replays += 1
+        return self.losses
+
+    def _replay_composed(self, col, prev, nxt, batch, jitter) -> Dict[str, Tensor]:
+        """A replay of a step built with ``composer=``: the graph composes its own batch, so nothing is copied in front of it (only
+        a ``jitter=`` tensor of a jitter="input" step, which the graphed-equals-eager tests need)."""
+        if col is not None or prev is not None or nxt is not None or batch is not None:
+            raise ValueError("a step built with composer= takes no bundles and no batch: the graph composes them")
+        if self.jitter is not None:
+            with torch.no_grad():
+                if jitter is None:
+                    self.jitter.uniform_()
+                else:
+                    self.jitter.copy_(jitter, non_blocking=True)
+        elif jitter is not None:
+            raise ValueError('this step draws its jitter inside the graph; build it with jitter="input" to pass one')
         if self.optimizer_in_graph:
             self.opt.prepare_step()
         self.graph.replay()
