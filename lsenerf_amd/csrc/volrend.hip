@@ -44,8 +44,12 @@ __global__ __launch_bounds__(256) void volrend_fwd_kernel(const float *__restric
         if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
         const float sd = sg * (b - a);
         const float incl = lse::wave_inclusive_sum(sd);
-        const float excl = (incl - sd) + carry;
-        const float T = expf(-excl);
+        // exclusive prefix = the inclusive one shifted by a lane (as in visibility_kernel), not `incl - sd`: a surface sample of a
+        // trained scene has sd = 1e2 .. 1e5 and beyond, and the subtraction would return the optical depth in front of it -- which
+        // decides that sample's weight, the largest of the ray -- to half an ulp of sd; at sd = +inf it is inf - inf = NaN
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 0.f;
+        const float T = expf(-(excl + carry));
         const float alpha = 1.f - expf(-sd);
         const float w = valid ? T * alpha : 0.f;
         if (valid) {
@@ -135,7 +139,11 @@ __device__ __forceinline__ float clamp01(float v)
 // arithmetic -- contraction is off in this body and every fused step is an explicit fmaf, so that the contraction choices the
 // compiler made in volrend_fwd_kernel are reproduced, not re-decided (HIP's __fadd_rn / __fmul_rn are plain operators whose fusing
 // follows the flags of their own definition, so they cannot pin this): the first step of the sigma*dt prefix scan is a fused multiply-add there (sd + neighbour, sd = sigma * dt), the
-// accumulation sum is a plain add, the colour / depth sums are fmaf.  No per-sample weights are stored.  Lane 0 applies the
+// accumulation sum is a plain add, the colour / depth sums are fmaf; the exclusive prefix (inclusive scan shifted one lane, + carry)
+// and w = T * alpha have nothing to fuse.  These sites are read off the gfx950 ISA of volrend_fwd_kernel (hipcc -S: one v_fmac_f32
+// after the first ds_bpermute of the scan, v_add_f32 for the other five steps, for excl + carry and for aw, v_pk_fma_f32 / v_fmac_f32
+// for rgb and depth) and were re-derived when the prefix changed from `incl - sd` to the shift; tests/test_gpu_eval.py and
+// tests/test_gpu_compositing.py hold the two kernels together bit for bit.  No per-sample weights are stored.  Lane 0 applies the
 // renderer epilogue of LSENeRFModel.render_packed per ray; the depth numerator and the ray's mid-point range go to the workspace
 // for eval_depth_finish (depth_finish_kernel: the chunk-wide clip range of DepthRenderer("expected")).
 __global__ __launch_bounds__(256) void eval_composite_kernel(const float *__restrict__ ts, const float *__restrict__ te,
@@ -170,8 +178,9 @@ __global__ __launch_bounds__(256) void eval_composite_kernel(const float *__rest
             const float nb = __shfl_up(incl, off, 64);
             if (lane >= off) incl = incl + nb;
         }
-        const float excl = (incl - sd) + carry;
-        const float T = expf(-excl);
+        float excl = __shfl_up(incl, 1, 64);     // shifted, not `incl - sd`: see volrend_fwd_kernel
+        if (lane == 0) excl = 0.f;
+        const float T = expf(-(excl + carry));
         const float alpha = 1.f - expf(-sd);
         const float w = valid ? T * alpha : 0.f;
         if (valid) {
