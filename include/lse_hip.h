@@ -386,6 +386,42 @@ int lse_occ_update_cells(float *occs, const int64_t *cell_ids, const float *occ_
                          float *workspace, lse_stream_t stream);
 int lse_occ_binarize(const float *occs, int64_t n, const float *d_threshold, uint8_t *binaries, lse_stream_t stream);
 
+/* ---- count-free occupancy refresh (csrc/occ_refresh.hip; ABI 6, additive): the index generation of `_update` on the device ----
+ * Nothing below sizes anything from a device value: every launch has a fixed grid, counts stay in device memory, so the four
+ * jobs (with the field's count-free density pass between 2 and 3, and lse_occ_binarize at the end) capture into a HIP graph.
+ *
+ * 1. Occupied-cell list.  binaries u8 [levels, cells]; list int32 [levels, cells]: per level the ASCENDING indices of the set
+ *    cells in list[l, 0 .. counts[l]) (the rest is left alone); counts int64 [levels].  == torch.nonzero(binaries[l])[:, 0].
+ *    Count per tile of LSE_OCC_LIST_TILE cells, exclusive scan of the tile counts, ordered write (ballot / popcount per wave);
+ *    no atomics.  workspace: levels * ceil(cells / LSE_OCC_LIST_TILE) int32. */
+#define LSE_OCC_LIST_TILE 4096
+int lse_occ_list_occupied(const uint8_t *binaries, int32_t levels, int64_t cells, int32_t *list, int64_t *counts,
+                          int32_t *workspace, lse_stream_t stream);
+/* 2. Cell draw and positions of ONE level (N = cells / 4, cells < 2^31, cells == res[0] * res[1] * res[2]).
+ *    warmup != 0: slot i is cell i, *n_dev = cells (cap >= cells).
+ *    warmup == 0: cnt = counts[level], m = min(cnt, N); slots [0, m): occupied cells -- list[level, i] when cnt <= N, else
+ *      list[level, mulhi32(w0, cnt)]; slots [m, m + N): uniform cells mulhi32(w0, cells); *n_dev = m + N (cap >= 2 N); slots
+ *      beyond are not written.
+ *    Per slot ONE Philox4x32-10 call, key (seed & 0xffffffff, seed >> 32), counter (*step_dev & 0xffffffff, slot, level, 0):
+ *    w0 picks the cell, w1..w3 the in-cell jitter u = (w >> 8) * 2^-24.  The library's own stream (uniform with replacement, like
+ *    torch.randint); no bit parity with any torch generator.  cell (x, y, z) = unravel(idx, res), position_k = lo_k + ((coord_k +
+ *    u_k) / res_k) * (hi_k - lo_k) in float32, every operation rounded on its own; aabbs f32 [levels, 6] in device memory.
+ *    cell_ids int64 [cap]: level * cells + idx, or -1 where occs of that cell < 0 (the position is still that cell's).
+ *    positions f32 [cap, 3]. */
+int lse_occ_draw_cells(const float *occs, const int32_t *list, const int64_t *counts, const float *aabbs, int32_t level,
+                       int64_t cells, int32_t res_x, int32_t res_y, int32_t res_z, int32_t warmup, const int64_t *step_dev,
+                       uint64_t seed, int64_t cap, int64_t *cell_ids, float *positions, int64_t *n_dev, lse_stream_t stream);
+/* 3. lse_occ_update_cells with the count in device memory: n = clamp(*n_dev, 0, cap), ids < 0 are skipped, and the new value is
+ *    sigma[i] * step_size (one float32 multiply).  Given the same cells: bit-equal to lse_occ_update_cells.  workspace: cap floats. */
+int lse_occ_update_cells_dev(float *occs, const int64_t *cell_ids, const float *sigma, float step_size, const int64_t *n_dev,
+                             int64_t cap, float ema_decay, float *workspace, lse_stream_t stream);
+/* 4. *mean_all = mean(occs) and *threshold = min(mean(occs[occs >= 0]), occ_thre) (NaN when no cell is >= 0, like torch) in one
+ *    fixed-order two-stage reduction: LSE_OCC_MEAN_BLOCKS blocks, double accumulators, no atomics -- two runs are bit-equal.
+ *    workspace: 3 * LSE_OCC_MEAN_BLOCKS doubles. */
+#define LSE_OCC_MEAN_BLOCKS 1024
+int lse_occ_mean_threshold(const float *occs, int64_t n, float occ_thre, double *workspace, float *mean_all, float *threshold,
+                           lse_stream_t stream);
+
 /* ---- training epilogue: output routing + intensity mappers + both losses, O(rays), one launch each way
  *      (R:lse_nerf/lsenerf.py:329-377 routing, :392-439 losses; R:lse_nerf/intensity_mappers.py:64-94 mappers).
  * Colour bundle:  v = rgb_mapped ? m_rgb(max(rgb, 1e-5)) : rgb;  mean over deblur_group consecutive rays (the 4 virtual

@@ -23,6 +23,7 @@ LSE_ABI_VERSION = 6
 LSE_MLP_ARITH_AUTO, LSE_MLP_ARITH_F32_MFMA = 0, 1
 LSE_TRAVERSE_FMA_SETUP = 1
 LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
+LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
 
 
 class GridDesc(Structure):
@@ -138,6 +139,10 @@ SIGNATURES = {
                               P, P, P, P, P, P, P],
     "lse_occ_update_cells": [P, P, P, I64, F32, P, P],
     "lse_occ_binarize": [P, I64, P, P, P],
+    "lse_occ_list_occupied": [P, I32, I64, P, P, P, P],
+    "lse_occ_draw_cells": [P, P, P, P, I32, I64, I32, I32, I32, I32, P, c_uint64, I64, P, P, P, P],
+    "lse_occ_update_cells_dev": [P, P, P, F32, P, I64, F32, P, P],
+    "lse_occ_mean_threshold": [P, I64, F32, P, P, P, P],
     "lse_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, I32, F32, P],
     "lse_adam_step_dev": [P, P, P, P, I64, P, F32, P],
     "lse_adam_schedule_dev": [P, P, P, P],

@@ -60,6 +60,8 @@ class LSENeRFModelConfig:
     num_levels: int = 16
     hidden_dim: int = 64
     hidden_dim_color: int = 64
+    # --- refresh the occupancy grid through occ_refresh.DeviceGridRefresher: no host synchronisation, replayable as a HIP graph
+    device_grid_refresh: bool = False
 
     def __post_init__(self):   # R:lse_nerf/lsenerf.py:86-99
         if self.evs_mapping_method is None or str(self.evs_mapping_method).lower() == "none":
@@ -403,8 +405,26 @@ class LSENeRFModel(nn.Module):
         graph-replayed training step alike, at most 16 steps after it happened."""
         if self.training and step % 16 == 0:
             self.occupancy_grid.check_deferred_overflow()
+        if self.config.device_grid_refresh:
+            # the same update rule with every count on the device (lsenerf_amd/occ_refresh.py): nothing below waits for the GPU
+            if not self.occupancy_grid.training:
+                raise RuntimeError("You should only call this function only during training. "
+                                   "Please call _update() directly if you want to update the field during inference.")
+            if step % 16 == 0:
+                self.grid_refresher().refresh(step)
+            return
         self.occupancy_grid.update_every_n_steps(
             step=step, occ_eval_fn=lambda x: self.field.density_fn(x) * self.config.render_step_size)
+
+    def grid_refresher(self):
+        """The model's ``occ_refresh.DeviceGridRefresher`` (``config.device_grid_refresh``), built on first use; call its
+        ``capture()`` to turn the refresh into one graph replay."""
+        r = self.__dict__.get("_grid_refresher")
+        if r is None or r.estimator.occs.device != self.occupancy_grid.occs.device:
+            from .occ_refresh import DeviceGridRefresher
+            r = self.__dict__["_grid_refresher"] = DeviceGridRefresher(self.occupancy_grid, self.field,
+                                                                       self.config.render_step_size)
+        return r
 
     def get_training_callbacks(self, training_callback_attributes=None) -> List[object]:
         """nerfstudio 0.3.2 ``NGPModel.get_training_callbacks(training_callback_attributes)`` (inherited by the reference,

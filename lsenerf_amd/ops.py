@@ -1313,3 +1313,55 @@ def occ_update_cells(occs, cell_ids, occ_new, ema_decay: float):
 def occ_binarize(occs, threshold: torch.Tensor, binaries_u8):
     _lib.call("lse_occ_binarize", _f32(occs, "occs"), occs.numel(), _f32(threshold, "threshold"),
               _chk(binaries_u8, torch.uint8, "binaries"), _stream())
+
+
+# ---- count-free occupancy refresh (csrc/occ_refresh.hip; driven by lsenerf_amd.occ_refresh.DeviceGridRefresher) ----
+def occ_list_tiles(cells: int) -> int:
+    return (int(cells) + _lib.LSE_OCC_LIST_TILE - 1) // _lib.LSE_OCC_LIST_TILE
+
+
+@torch.no_grad()
+def occ_list_occupied(binaries_u8, cell_list, counts, workspace):
+    """Per level the ascending indices of the set cells of ``binaries_u8`` [L, C] into ``cell_list`` (int32 [L, C]) and their number
+    into ``counts`` (int64 [L]): ``torch.nonzero(binaries[l])[:, 0]`` without a host-known size.  ``workspace``: int32
+    [L * occ_list_tiles(C)]."""
+    levels, cells = binaries_u8.shape
+    if cell_list.shape != (levels, cells) or counts.numel() != levels or workspace.numel() < levels * occ_list_tiles(cells):
+        raise ValueError("occ_list_occupied: list [L, C], counts [L] and workspace [L * tiles] do not fit binaries [L, C]")
+    _lib.call("lse_occ_list_occupied", _chk(binaries_u8, torch.uint8, "binaries"), levels, cells,
+              _chk(cell_list, torch.int32, "cell_list"), _chk(counts, torch.int64, "counts"),
+              _chk(workspace, torch.int32, "workspace"), _stream())
+
+
+@torch.no_grad()
+def occ_draw_cells(occs, cell_list, counts, aabbs, level: int, cells: int, res, warmup: bool, step_dev, seed: int, cell_ids,
+                   positions, n_dev):
+    """Cells and jittered positions of one level's refresh (lse_occ_draw_cells; spec: occ_refresh.draw_cells_host).  ``cell_ids``
+    int64 [cap], ``positions`` float32 [cap, 3], ``n_dev`` int64 [1] are written; ``step_dev`` int64 [1] is read on the device."""
+    cap = cell_ids.shape[0]
+    if positions.shape != (cap, 3) or occs.numel() < (level + 1) * cells or aabbs.shape[0] <= level:
+        raise ValueError("occ_draw_cells: positions must be [cap, 3]; occs / aabbs must cover the level")
+    _lib.call("lse_occ_draw_cells", _f32(occs, "occs"), _chk(cell_list, torch.int32, "cell_list", True),
+              _chk(counts, torch.int64, "counts", True), _f32(aabbs, "aabbs"), int(level), int(cells), int(res[0]), int(res[1]),
+              int(res[2]), int(bool(warmup)), _chk(step_dev, torch.int64, "step_dev"), int(seed) & 0xFFFFFFFFFFFFFFFF, cap,
+              _chk(cell_ids, torch.int64, "cell_ids"), _f32(positions, "positions"), _chk(n_dev, torch.int64, "n_dev"), _stream())
+
+
+@torch.no_grad()
+def occ_update_cells_dev(occs, cell_ids, sigma, step_size: float, n_dev, ema_decay: float, workspace):
+    """``occ_update_cells`` on the leading ``n_dev[0]`` entries with ``occ_new = sigma * step_size``; ids < 0 are skipped."""
+    cap = cell_ids.shape[0]
+    if sigma.numel() < cap or workspace.numel() < cap:
+        raise ValueError("occ_update_cells_dev: sigma and workspace need one entry per slot")
+    _lib.call("lse_occ_update_cells_dev", _f32(occs, "occs"), _chk(cell_ids, torch.int64, "cell_ids"), _f32(sigma, "sigma"),
+              float(step_size), _chk(n_dev, torch.int64, "n_dev"), cap, float(ema_decay), _f32(workspace, "workspace"), _stream())
+
+
+@torch.no_grad()
+def occ_mean_threshold(occs, occ_thre: float, workspace, mean_all, threshold):
+    """``mean_all[0] = occs.mean()`` and ``threshold[0] = min(occs[occs >= 0].mean(), occ_thre)``, both float32 on the device, from
+    one deterministic double-precision reduction.  ``workspace``: float64 [3 * LSE_OCC_MEAN_BLOCKS]."""
+    if workspace.numel() < 3 * _lib.LSE_OCC_MEAN_BLOCKS:
+        raise ValueError("occ_mean_threshold: workspace needs 3 * LSE_OCC_MEAN_BLOCKS doubles")
+    _lib.call("lse_occ_mean_threshold", _f32(occs, "occs"), occs.numel(), float(occ_thre), _chk(workspace, torch.float64, "workspace"),
+              _f32(mean_all, "mean_all"), _f32(threshold, "threshold"), _stream())
