@@ -589,6 +589,44 @@ int lse_compose_rays_bwd(const lse_compose_desc *desc, const lse_compose_scene *
                          const float *d_origins, const float *d_directions, float *d_col_pose, float *d_prev_pose,
                          float *d_next_pose, lse_stream_t stream);
 
+/* ---- spline camera poses: the composer's pose tables from a SplineCameraOptimizer's parameters, on the device -------------
+ * Replaces, in front of every step, SplineCameraOptimizer.get_rgb_cameras / get_evs_cameras / get_deblur_cameras of
+ * lsenerf_amd/cameras.py (with exp_map_to_quat_map, vectorized_generalized_interpolation, slerp, quat_map_to_mtx;
+ * R:lse_nerf/ns_camera_optimizer.py:130-197 over R:lse_nerf/interpolation_utils.py:56-233) -- what lsenerf_amd.data.spline_tables
+ * + BatchComposer.set_poses did with some 60 torch launches per step.
+ * A QUERY is one 3x4 row of a pose table.  Queries are numbered over up to three segments, colour | prev | next (n_query[s] rows
+ * of table s; 0 = the table is not fed).  A segment is "rgb" (evs[s] = 0: the plain spline pose; the deblur table is an "rgb"
+ * segment whose queries are the four exposure times of every camera) or "evs" (evs[s] = 1: pose @ dM', dM' = dM with its
+ * translation column times *scale, as get_evs_cameras builds it while the optimiser is on).
+ * Per query the caller gives the bracketing control index idx (searchsorted(right = True), clamped to [1, n_ctrl - 1], minus 1,
+ * after the clip of the time to the control times) and the fraction frac = (ts - t0) / (t1 - t0): they depend on buffers that
+ * never change during training, so they are computed once, with the torch expressions of cameras.py.  ctrl_tangents and scale
+ * are read from the parameters' own storage at every launch: an in-place optimiser update is seen by the next launch (or graph
+ * replay) without a copy.  Everything is evaluated in f32. */
+typedef struct lse_spline_desc {
+    int32_t n_ctrl;              /* control points K >= 2 */
+    int32_t n_query[3];          /* rows of the colour | prev | next table fed by the spline */
+    int32_t evs[3];              /* per segment: 0 "rgb", 1 "evs" */
+    int32_t csr_len;             /* entries of csr_query = 2 * (n_query[0] + n_query[1] + n_query[2]); read by the backward */
+    float dM[16];                /* row-major 4x4 relative pose rgb camera -> event camera (host values; "evs" segments) */
+    const float *ctrl_tangents;  /* [n_ctrl, 6] (translation, rotation vector) */
+    const float *scale;          /* [1] */
+    const int32_t *idx;          /* [queries] in [0, n_ctrl - 2] */
+    const float *frac;           /* [queries] */
+    const int32_t *csr_start;    /* [n_ctrl + 1]: control point k owns csr_query[csr_start[k] .. csr_start[k + 1]) */
+    const int32_t *csr_query;    /* the queries with idx == k or idx + 1 == k, ascending; read by the backward */
+} lse_spline_desc;
+/* One launch writes every row of the fed tables: col_pose [n_query[0], 3, 4] (= [cameras, G, 3, 4]), prev_pose / next_pose
+ * [n_query[1 / 2], 3, 4].  The table of a segment with n_query == 0 is not touched (NULL allowed). */
+int lse_spline_poses(const lse_spline_desc *desc, float *col_pose, float *prev_pose, float *next_pose, lse_stream_t stream);
+/* d tables (the layout lse_compose_rays_bwd writes) -> d_ctrl_tangents [n_ctrl, 6], d_scale [1], both OVERWRITTEN; one launch.
+ * The exact derivative of the expressions above as torch autograd takes it: `where` selects a branch, a clamped value passes no
+ * gradient, norm at exactly zero has gradient zero (a control point whose rotation vector is exactly zero gets a zero rotation
+ * gradient).  One wave per control point sums the queries of its list in a fixed order, one block sums d_scale over the "evs"
+ * queries in a fixed order (no atomics): two runs are bit-equal, and a control point no query brackets receives exactly zero. */
+int lse_spline_poses_bwd(const lse_spline_desc *desc, const float *d_col_pose, const float *d_prev_pose, const float *d_next_pose,
+                         float *d_ctrl_tangents, float *d_scale, lse_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

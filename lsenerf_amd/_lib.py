@@ -90,6 +90,13 @@ class ComposeOut(Structure):
         "evs_indices", "evs_batch_appearance_id")]
 
 
+class SplineDesc(Structure):
+    """lse_spline_desc: a pose spline's parameters (device pointers), the per-query brackets and the per-control-point query lists."""
+    _fields_ = [("n_ctrl", c_int32), ("n_query", c_int32 * 3), ("evs", c_int32 * 3), ("csr_len", c_int32), ("dM", c_float * 16),
+                ("ctrl_tangents", c_void_p), ("scale", c_void_p), ("idx", c_void_p), ("frac", c_void_p), ("csr_start", c_void_p),
+                ("csr_query", c_void_p)]
+
+
 P = c_void_p
 I32, I64, F32 = c_int32, c_int64, c_float
 
@@ -148,6 +155,8 @@ SIGNATURES = {
     "lse_adam_schedule_dev": [P, P, P, P],
     "lse_compose_batch": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, I64, I32, P, P, P],
     "lse_compose_rays_bwd": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, P, P, P, P, P],
+    "lse_spline_poses": [POINTER(SplineDesc), P, P, P, P],
+    "lse_spline_poses_bwd": [POINTER(SplineDesc), P, P, P, P, P, P],
 }
 # exported by the development build only (csrc/dev_knobs.h)
 DEV_SIGNATURES = {

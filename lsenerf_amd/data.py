@@ -305,6 +305,7 @@ class BatchComposer:
                 t_nxt = scene.next_cameras.camera_to_worlds.contiguous().to(dev)
         self.pose_tables: Tuple[Optional[Tensor], Optional[Tensor], Optional[Tensor]] = (t_col, t_prev, t_nxt)
         self._pose_grads = tuple(None if t is None else torch.zeros_like(t) for t in self.pose_tables)
+        self.spline = None                     # attach_spline(): a SplinePoses that fills (some of) the tables in front of every compose
         self.bundles = self._make_bundles(self._buf["origins"], self._buf["directions"])
         # C-ABI descriptors (host structs; the pointers are those of the static tensors above)
         key = "consec" if self.consec else "prev"
@@ -361,16 +362,64 @@ class BatchComposer:
     def set_poses(self, col: Optional[Tensor] = None, prev: Optional[Tensor] = None, nxt: Optional[Tensor] = None) -> None:
         """Copy new poses into the static tables, in place, in stream order (no synchronisation): ``col`` [C, G, 3, 4] (or [C, 3, 4]:
         every slot of a camera), ``prev`` / ``nxt`` [Ce, 3, 4] ("consec": ``prev`` is the one event table and ``nxt`` must be None)."""
-        for name, dst, src in zip(("col", "prev", "nxt"), self.pose_tables, (col, prev, nxt)):
+        for i, (name, dst, src) in enumerate(zip(("col", "prev", "nxt"), self.pose_tables, (col, prev, nxt))):
             if src is None:
                 continue
             if dst is None:
                 raise ValueError(f"this composer has no '{name}' pose table")
+            if self.spline is not None and self.spline.fed[i]:
+                raise ValueError(f"the '{name}' pose table is fed by the attached spline: every compose() overwrites it")
             if name == "col" and src.dim() == 3:
                 src = src[:, None].expand(-1, self.G, -1, -1)
             if tuple(src.shape) != tuple(dst.shape):
                 raise ValueError(f"'{name}' pose table is {tuple(dst.shape)}, got {tuple(src.shape)}")
             dst.copy_(src, non_blocking=True)
+
+    def attach_spline(self, spline, tables: Optional[Sequence[str]] = None):
+        """From now on the pose tables come from ``spline`` (a ``SplineCameraOptimizer`` on the composer's device) by one launch in
+        front of every ``compose()`` -- ``lse_spline_poses``, the device-side counterpart of ``spline_tables`` -- so they are always
+        those of the spline's CURRENT parameters, which the kernel reads in place.  The colour table is fed as "deblur" when G == 4,
+        else as "rgb" at the colour cameras' times; prev / nxt as "evs" at the event cameras' times of this composer's pairing.
+        ``tables``: the names ("col", "prev", "nxt") to feed; default: every table the composer has.  ``set_poses`` on a fed table
+        and ``compose(tables=...)`` then raise ValueError -- the latter also when only a subset is fed: the tables the spline does
+        not feed are then set with ``set_poses`` only, there is no differentiable eager route to them while a spline is attached.  Indices, fractions and the backward's query lists are computed here,
+        once; ``spline_grads`` / ``spline_pose_tables`` are the way back to the parameters.  A spline whose mode is "off" (frozen,
+        or "delayed" before ``turn_on()``) is refused with ValueError: its tables are constant, ``set_poses`` once is the right
+        call; attach after ``turn_on()`` and rebuild the captured step.  Returns the ``SplinePoses``."""
+        from .spline_dev import SEGMENTS, SplinePoses
+        names = [n for n, t in zip(SEGMENTS, self.pose_tables) if t is not None] if tables is None else list(tables)
+        for n in names:
+            if n not in SEGMENTS or self.pose_tables[SEGMENTS.index(n)] is None:
+                raise ValueError(f"this composer has no '{n}' pose table")
+        scene = self.scene
+        key = "consec" if self.consec else "prev"
+        times = {"col": None if not self.n_col else ("deblur" if self.G == 4 else "rgb", scene.col.times),
+                 "prev": None if not self.n_evs else ("evs", scene.evs_times[key]),
+                 "nxt": None if not self.n_evs or self.consec else ("evs", scene.evs_times["next"])}
+        if self.G == 4 and "col" in names and int(spline.n_deblur_rays) != self.G:
+            raise ValueError(f"the spline has {spline.n_deblur_rays} deblur cameras per exposure, the composer {self.G} rays per pixel")
+        segments = [times[n] if n in names else None for n in SEGMENTS]
+        shapes = [None if t is None else tuple(t.shape) for t in self.pose_tables]
+        self.spline = SplinePoses(spline, segments, shapes, scene.device)
+        return self.spline
+
+    def spline_grads(self, pose_grads) -> Dict[str, Tensor]:
+        """``{"ctrl_tangents": [K, 6], "scale": [1]}``: the gradients of the attached spline's parameters from the gradients of the
+        pose tables -- ``pose_grads`` as ``pose_grads()`` returns them or as ``GraphedTrainStep.pose_grads`` holds them (entries of
+        tables the spline does not feed are ignored).  One launch of fixed-order sums (two calls are bit-equal, control points that
+        no query brackets get exactly zero); the result lives in static tensors that the next call overwrites."""
+        if self.spline is None:
+            raise ValueError("no spline attached (attach_spline)")
+        if isinstance(pose_grads, dict):
+            pose_grads = [pose_grads.get(k) for k in ("col", "prev", "next")]
+        return self.spline.backward(list(pose_grads))
+
+    def spline_pose_tables(self):
+        """``(col, prev, nxt)`` of the attached spline as NEW tensors with autograd history back to ``ctrl_tangents`` / ``scale`` (None
+        where the spline feeds none): the eager, differentiable twin of what ``compose()`` writes into ``pose_tables``."""
+        if self.spline is None:
+            raise ValueError("no spline attached (attach_spline)")
+        return tuple(self.spline.tables())
 
     # -- launches
     def _given(self, indices):
@@ -394,8 +443,13 @@ class BatchComposer:
         ``tables=(col, prev, nxt)``: pose tables as (differentiable) torch expressions -- they are copied into the static tables and
         the returned origins / directions carry autograd history back to them (new tensors; backward = ``lse_compose_rays_bwd``)."""
         if tables is None:
+            if self.spline is not None:        # the tables of the spline's current parameters, in stream order in front of the rays
+                self.spline.forward(self.pose_tables)
             self._launch(step, indices)
             return self.bundles, self.batch
+        if self.spline is not None:
+            raise ValueError("compose(tables=...) with a spline attached: the attached spline feeds the pose tables "
+                             "(spline_pose_tables() is their differentiable twin)")
         given = [t for t, own in zip(tables, self.pose_tables) if own is not None]
         if len(given) != sum(t is not None for t in self.pose_tables) or any(t is None for t in given):
             raise ValueError("tables= takes one tensor per pose table of this composer")

@@ -227,7 +227,12 @@ class GraphedTrainStep:
     draws what ``composer.compose(step=k0 + k)`` draws; ``step()`` takes no arguments and copies nothing.  With ``ray_grads=True`` the
     body ends with ``lse_compose_rays_bwd`` and ``step.pose_grads`` ({"col", "prev", "next"}) holds the gradients of the composer's
     pose tables; the caller continues with ``torch.autograd.backward(tables, grads)`` into its camera optimiser, eagerly, over
-    O(cameras) rows.  Not combined with ``prefetch_march`` (ValueError)."""
+    O(cameras) rows.  With a spline attached (``composer.attach_spline``) the body is: spline poses -> compose -> step ->
+    ``lse_compose_rays_bwd`` -> ``lse_spline_poses_bwd``: the pose tables are evaluated inside the graph from the spline's parameters,
+    read in place, and ``step.spline_grads`` ({"ctrl_tangents", "scale"}) holds the parameters' gradients after every replay; the
+    caller finishes with ``spl.ctrl_tangents.grad = step.spline_grads["ctrl_tangents"]`` (likewise ``scale``) and its own torch
+    optimiser step (``ray_grads=False``: only the pose evaluation is captured).  Attach before building the step.
+    Not combined with ``prefetch_march`` (ValueError)."""
 
     def __init__(self, model, opt: FlatAdam, col: Optional[RayBundle] = None, prev: Optional[RayBundle] = None,
                  nxt: Optional[RayBundle] = None, batch: Optional[Dict[str, object]] = None, ray_grads: bool = False,
@@ -260,6 +265,8 @@ class GraphedTrainStep:
         self._ray_leaves: Optional[Tuple[Tensor, Tensor]] = None      # (origins, directions) leaves of the last run of _body
         # composer + ray_grads: gradients of the composer's pose tables, written by the last launch of every replay
         self.pose_grads: Optional[Dict[str, Optional[Tensor]]] = None
+        # ... and with a spline attached to the composer: the gradients of its parameters {"ctrl_tangents", "scale"}
+        self.spline_grads: Optional[Dict[str, Tensor]] = None
         n_total = sum(len(b) for b in (self.col, self.prev, self.nxt) if b is not None)
         dev = opt.flat.data.device
         self.jitter = torch.rand(n_total, device=dev) if jitter == "input" else None
@@ -335,6 +342,9 @@ class GraphedTrainStep:
             with torch.no_grad():
                 g = self.composer.pose_grads((o.grad, d.grad))
             self.pose_grads = dict(zip(("col", "prev", "next"), g))
+            if self.composer.spline is not None:                   # d pose tables -> d ctrl_tangents, d scale (static tensors too)
+                with torch.no_grad():
+                    self.spline_grads = self.composer.spline_grads(g)
         if self.optimizer_in_graph:
             self.opt.step_staged(self.grad_scale)
         self.losses, self.outputs = losses, out

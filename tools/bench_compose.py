@@ -4,8 +4,12 @@
   (a) "torch route"  indices from ``torch.randint`` on the device, targets gathered with torch indexing from resident images,
                      rays from the ``cameras.py`` generators on the device (``RayGenerator`` / ``generate_deblur_rays``,
                      ``ConsecRayGenerator``), metadata with torch ops, then ``GraphedTrainStep.__call__`` with its input copies;
-  (b) "composer"     ``GraphedTrainStep(model, opt, composer=...)``: one compose launch inside the graph, ``step()`` copies nothing.
-Both at the reference's default composition (579 x 4 + 597 + 597 rays, deblur colour bundle, poses from the spline) and at config 2
+  (b) "composer"     ``GraphedTrainStep(model, opt, composer=...)``: one compose launch inside the graph, ``step()`` copies nothing;
+                     with spline poses: ``spline_tables`` + ``set_poses`` (torch, ~60 launches) in front of every replay;
+  (c) "spline"       (b) with the spline ATTACHED (``composer.attach_spline``): the graph starts with ``lse_spline_poses``, which reads
+                     the spline's parameters in place -- nothing runs in front of a replay.  Feeds the table (b) feeds (colour).
+                     Default composition only.
+All at the reference's default composition (579 x 4 + 597 + 597 rays, deblur colour bundle, poses from the spline) and at config 2
 (2318 + 597 + 597), on a synthetic resident scene (32 colour images 480 x 640, 64 int8 event frames 260 x 346, cameras on a
 sphere around the [-1, 1]^3 box).  Per route: ms per step (median of the per-step device-event intervals, 100 steps after 20
 warm-up ones) and host ms per step (time.perf_counter around the loop, no synchronisation inside it).
@@ -13,11 +17,15 @@ warm-up ones) and host ms per step (time.perf_counter around the loop, no synchr
     python tools/bench_compose.py                            # the two compositions, both routes: one JSON line each
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_compose.py trace precomposed|composer [cfg]
     python tools/bench_compose.py analyze DIR_PRECOMPOSED_1 DIR_PRECOMPOSED_2 DIR_COMPOSER
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_compose.py trace composer_poses|spline
+    python tools/bench_compose.py analyze_spline DIR_COMPOSER_POSES_1 DIR_COMPOSER_POSES_2 DIR_SPLINE
 
 ``trace``: replays only -- the composer step, or the parent's graphed step fed the SAME batches composed beforehand -- behind a
 0.5 s pause that marks the start of the timed region in the kernel trace.  ``analyze``: summed kernel time per step of the three traces, the time of the two
 composer kernels, and the bar of the change -- (b) may exceed the mean of the two precomposed runs by no more than the composer
-kernels' own time plus twice the spread between those two runs."""
+kernels' own time plus twice the spread between those two runs.  ``trace composer_poses`` / ``trace spline``: routes (b) / (c) at the
+default composition with ``ray_grads=True`` ((c) then ends with ``lse_spline_poses_bwd``); ``analyze_spline``: the same bar with the two
+spline kernels as the change's own."""
 import csv
 import glob
 import json
@@ -29,9 +37,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 STEPS, WARMUP = 100, 20
 COMPOSE_KERNELS = ("compose_kernel", "advance_kernel", "rays_bwd_kernel")
+SPLINE_KERNELS = ("spline_fwd_kernel", "spline_bwd_kernel")
 
 
-def analyze(dirs):
+def analyze(dirs, own_kernels=COMPOSE_KERNELS):
     def load(d):
         rows = []
         for f in glob.glob(f"{d}/**/*kernel_trace.csv", recursive=True):
@@ -43,7 +52,7 @@ def analyze(dirs):
         timed = rows[last_gap:]
         per = {}
         for s, e, name in timed:
-            key = next((k for k in COMPOSE_KERNELS if k in name), "other")
+            key = next((k for k in own_kernels if k in name), "other")
             tot, n = per.get(key, (0, 0))
             per[key] = (tot + (e - s), n + 1)
         return per
@@ -51,19 +60,19 @@ def analyze(dirs):
     steps = STEPS
     total = lambda per: sum(t for t, _ in per.values()) / steps / 1e6
     a, b, c = total(pre1), total(pre2), total(comp)
-    own = sum(comp.get(k, (0, 0))[0] for k in COMPOSE_KERNELS) / steps / 1e6
+    own = sum(comp.get(k, (0, 0))[0] for k in own_kernels) / steps / 1e6
     spread = abs(a - b)
     res = {"precomposed_kernel_ms_per_step": [round(a, 5), round(b, 5)], "run_to_run_spread_ms": round(spread, 5),
            "composer_kernel_ms_per_step": round(c, 5), "composer_kernels_own_ms_per_step": round(own, 5),
-           "avg_us": {k: round(comp[k][0] / comp[k][1] / 1e3, 3) for k in COMPOSE_KERNELS if k in comp},
+           "avg_us": {k: round(comp[k][0] / comp[k][1] / 1e3, 3) for k in own_kernels if k in comp},
            "excess_ms": round(c - (a + b) / 2, 5), "allowed_excess_ms": round(own + 2 * spread, 5),
            "within_bar": bool(c - (a + b) / 2 <= own + 2 * spread)}
     print(json.dumps(res))
     return res
 
 
-if len(sys.argv) > 1 and sys.argv[1] == "analyze":
-    analyze(sys.argv[2:5])
+if len(sys.argv) > 1 and sys.argv[1] in ("analyze", "analyze_spline"):
+    analyze(sys.argv[2:5], COMPOSE_KERNELS if sys.argv[1] == "analyze" else SPLINE_KERNELS)
     sys.exit(0)
 
 import numpy as np
@@ -185,6 +194,10 @@ def run(kind):
     res_a = timed(a)
     step_a.close()
     del step_a
+    # every route starts from the same freshly built model, optimiser and occupancy grid (same seeds): the routes are compared on
+    # the same training state, not one after the other on a model the previous route has trained
+    del model, opt, route
+    model, opt, scene, n_col, n_evs, spl = build(kind)
     comp = BatchComposer(scene, n_col, n_evs, deblur=spl is not None, seed=0, num_embd=N_EMB)
     step_b = GraphedTrainStep(model, opt, composer=comp)
 
@@ -195,19 +208,41 @@ def run(kind):
         step_b()
     res_b = timed(b)
     step_b.check_overflow()
+    step_b.close()
+    del step_b, model, opt
+    res_c = {}
+    if spl is not None:          # (c): the table (b) feeds, from the attached spline
+        model, opt, scene, n_col, n_evs, spl = build(kind)
+        comp_c = BatchComposer(scene, n_col, n_evs, deblur=True, seed=0, num_embd=N_EMB)
+        comp_c.attach_spline(spl, tables=("col",))
+        step_c = GraphedTrainStep(model, opt, composer=comp_c)
+        res_c["spline"] = timed(step_c)
+        step_c.check_overflow()
+        step_c.close()
     print(json.dumps({"composition": kind, "rays": comp.n_rays, "col_pixels": n_col, "evs_pixels": n_evs, "steps": STEPS,
-                      "warmup": WARMUP, "torch_route": res_a, "composer": res_b}), flush=True)
+                      "warmup": WARMUP, "torch_route": res_a, "composer": res_b, **res_c}), flush=True)
 
 
 def trace(mode, kind):
     model, opt, scene, n_col, n_evs, spl = build(kind)
     comp = BatchComposer(scene, n_col, n_evs, deblur=spl is not None, seed=0, num_embd=N_EMB)
-    if spl is not None:
+    if mode in ("composer_poses", "spline"):
+        assert spl is not None, "the spline routes are measured at the default composition"
+    if mode == "spline":
+        comp.attach_spline(spl, tables=("col",))
+    elif spl is not None:
         with torch.no_grad():
             comp.set_poses(col=spline_tables(spl, scene.col.cameras, "deblur"))
-    if mode == "composer":
+    if mode in ("composer", "spline"):
         step = GraphedTrainStep(model, opt, composer=comp, ray_grads=True)
         fn = step
+    elif mode == "composer_poses":
+        step = GraphedTrainStep(model, opt, composer=comp, ray_grads=True)
+
+        def fn():
+            with torch.no_grad():
+                comp.set_poses(col=spline_tables(spl, scene.col.cameras, "deblur"))
+            step()
     else:       # the parent's graphed step on precomposed inputs: the batches the composer step draws (steps 0, 1, ...), composed
         #         eagerly beforehand and handed to GraphedTrainStep.__call__ with its copies -- the same work per step on both sides
         cl = lambda t: t.clone() if torch.is_tensor(t) else t
