@@ -16,8 +16,9 @@
  *   "mlp_bwd_impl"      1 = contiguous-tiles fused backward (bias gradient inside the dW0 MFMAs; default), 0 = generic kernel
  *   "mlp_bwd3_cfg"      CT * 100 + NW of the bf16-piece fused backward (default 208; 112, 108, 204 = A/B partners)
  *   "mlp_act_nt"        non-temporal stores of saved activations (default 0)
- *   "hash_bwd_probes" / "hash_bwd_few_runs" / "hash_bwd_stage_max"   defaults of lse_hash_bwd_opts.second_probe (3), .few_runs (6)
- *                       and .stage_max (16), for A/B runs of whole steps (a single call sets them in lse_hash_bwd_opts)
+ *   "hash_bwd_probes" / "hash_bwd_few_runs" / "hash_bwd_stage_max"   defaults of lse_hash_bwd_opts.second_probe (3), .few_runs (8)
+ *                       and .stage_max (48), for A/B runs of whole steps (a single call sets them in lse_hash_bwd_opts;
+ *                       lsenerf_amd/ops.py HASH_BWD_DENSE_STEPS passes few_runs 3 / stage_max 56 that way, as call arguments)
  *   "traverse_vec"      1 = 64-steps-at-once marcher for constant step sizes (default, bit-identical), 0 = serial loop only
  * Integer outputs never depend on these; floating-point results agree within rounding.  Returns LSE_E_INVALID for an unknown name.
  */
