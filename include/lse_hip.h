@@ -169,7 +169,7 @@ int lse_compact_samples(const uint8_t *mask, const int64_t *packed_info, const i
 /* ---- field ------------------------------------------------------------------------------------------- */
 
 /* Device-side sample count `n_dev` (nullable) of the PER-SAMPLE entry points
- *     lse_positions_fwd / _bwd, lse_hash_fwd, lse_hash_bwd / _levels / _ex, lse_mlp_fwd / _bwd.
+ *     lse_positions_fwd / _bwd, lse_hash_fwd, lse_hash_bwd / _levels / _ex, lse_mlp_fwd / _fwd_pair / _bwd.
  * The sampler knows the number of packed samples only on the device (lse_pack_info_from_counts); reading it back costs a host
  * synchronisation per sampler call, twice per step with the visibility pre-pass.  With n_dev != NULL the `n` argument is a
  * CAPACITY -- buffer extents, level strides and the launch grid are sized by it -- and every kernel clamps it to the int64 that
@@ -190,6 +190,14 @@ int lse_positions_bwd(const float *rays_o, const float *rays_d, const int32_t *r
 /* per-ray sums: d_o[r] = sum d_pos, d_d[r] = sum d_pos*(ts+te)/2 over the ray's packed samples. */
 int lse_ray_grad_reduce(const float *d_pos, const float *t_starts, const float *t_ends, const int64_t *packed_info,
                         int32_t n_rays, float *d_rays_o, float *d_rays_d, lse_stream_t stream);
+
+/* lse_positions_bwd -> lse_ray_grad_reduce in one launch for the ray path (one wave per ray over packed_info): d(pos) is formed
+ * per sample from d_x01 and summed on the fly, in the order lse_ray_grad_reduce sums it, so d_rays_o / d_rays_d (either nullable)
+ * carry the same bits and d_pos[N,3] is neither written nor read.  Replaces the two calls at the end of the backward of
+ * R:lse_nerf/lse_field.py:266-274 when the positions come from rays.  Per-ray entry point: counts come from packed_info. */
+int lse_ray_grad_from_dx01(const float *rays_o, const float *rays_d, const float *t_starts, const float *t_ends,
+                           const int64_t *packed_info, int32_t n_rays, int32_t contraction, const float *h_aabb,
+                           const float *d_x01, float *d_rays_o, float *d_rays_d, lse_stream_t stream);
 
 /* tcnn kernel_grid forward (R:lse_nerf/lse_field.py:279 via HashEncoding.forward): x01[N,3] -> y[L][N][F]. */
 int lse_hash_fwd(const lse_grid_desc *desc, const float *x01, const float *table, float *y, int64_t n,
@@ -273,6 +281,20 @@ int lse_mlp_fwd(const lse_mlp_desc *desc, const float *params, const float *in, 
                 const int32_t *row_bias_idx, float *out, int32_t out_cols, float *act, int32_t act_tiled,
                 float *sigma_out, const uint8_t *selector, float density_scale, int64_t n, const int64_t *n_dev,
                 lse_stream_t stream);
+/* Base MLP (R:lse_nerf/lse_field.py:280-287: mlp_base_mlp + trunc_exp density) and head MLP (R:lse_nerf/lse_field.py:347-358: mlp_head)
+ * on the same samples in ONE launch: per 32-sample tile the base output h stays in registers and is the head's k = 16 input
+ * (same lane / register layout), so h[N,16] is written once (the backward and the caller read it) and never read back.
+ * Equivalent to, and bitwise equal to,
+ *     lse_mlp_fwd(base_desc, base_params, y, NULL, NULL, h, 16, NULL, 3, sigma, selector, density_scale, n, n_dev, stream);
+ *     lse_mlp_fwd(head_desc, head_params, h, row_bias, row_bias_idx, out, out_cols, NULL, 3, NULL, NULL, 0, n, n_dev, stream);
+ * Shapes: the recompute-all production pair only -- base 32 -> 64 -> 16 (one hidden layer, level-major or row-major input, no
+ * output activation), head 16 -> 64 -> 64 -> 16 (row-major, first-layer view w0_ld / w0_col / w0_mask_col0 as in lse_mlp_fwd),
+ * both LSE_MLP_ARITH_AUTO; anything else is LSE_E_UNSUPPORTED (call lse_mlp_fwd twice).  Nothing is saved for the backward
+ * (lse_mlp_bwd with act_tiled = 3 recomputes).  selector, row_bias, row_bias_idx nullable as in lse_mlp_fwd. */
+int lse_mlp_fwd_pair(const lse_mlp_desc *base_desc, const float *base_params, const float *y, const uint8_t *selector,
+                     float density_scale, const lse_mlp_desc *head_desc, const float *head_params, const float *row_bias,
+                     const int32_t *row_bias_idx, float *h, float *sigma, float *out, int32_t out_cols, int64_t n,
+                     const int64_t *n_dev, lse_stream_t stream);
 /* backward: d_out[N,out_cols] (w.r.t. the activated output) -> d_in (layout of desc->in_layout; nullable) and, when
  * d_params is given, the weight gradients of every layer accumulated into d_params (same layout as params) in the
  * same pass (`in` = the layer-0 input is then required).  d_sigma (nullable): gradient of the fused density head, folded

@@ -116,11 +116,13 @@ SIGNATURES = {
     "lse_positions_fwd": [P, P, P, P, P, I64, P, I32, P, P, P, P],
     "lse_positions_bwd": [P, P, P, P, P, I64, P, I32, P, P, P, P],
     "lse_ray_grad_reduce": [P, P, P, P, I32, P, P, P],
+    "lse_ray_grad_from_dx01": [P, P, P, P, P, I32, I32, P, P, P, P, P],
     "lse_hash_fwd": [POINTER(GridDesc), P, P, P, I64, P, P],
     "lse_hash_bwd": [POINTER(GridDesc), P, P, P, P, P, I64, P, P],
     "lse_hash_bwd_levels": [POINTER(GridDesc), P, P, P, P, P, I32, I32, I32, I64, P, P],
     "lse_hash_bwd_ex": [POINTER(GridDesc), P, P, P, P, P, I32, I32, I32, I64, P, POINTER(HashBwdOpts), P],
     "lse_mlp_fwd": [POINTER(MlpDesc), P, P, P, P, P, I32, P, I32, P, P, F32, I64, P, P],
+    "lse_mlp_fwd_pair": [POINTER(MlpDesc), P, P, P, F32, POINTER(MlpDesc), P, P, P, P, P, P, I32, I64, P, P],
     "lse_mlp_bwd": [POINTER(MlpDesc), P, P, P, I32, P, I32, P, P, P, F32, P, P, P, P, P, P, P, P, I64, P, P],
     "lse_mlp_wgrad": [POINTER(MlpDesc), P, P, P, P, P, I64, P],
     "lse_segment_sum_rows": [P, I32, P, I32, P, P],
@@ -257,7 +259,8 @@ class dev_library:
 TIMING = None
 
 
-_TIMING_ALIAS = {"lse_hash_bwd_ex": "lse_hash_bwd", "lse_hash_bwd_levels": "lse_hash_bwd"}   # one operation, three entry points
+_TIMING_ALIAS = {"lse_hash_bwd_ex": "lse_hash_bwd", "lse_hash_bwd_levels": "lse_hash_bwd",     # one operation, three entry points
+                 "lse_mlp_fwd_pair": "lse_mlp_fwd"}                                              # base + head forward in one launch
 
 
 def call(name: str, *args):

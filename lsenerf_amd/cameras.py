@@ -11,8 +11,8 @@ Mirrors, with the same names / argument meaning / shapes:
   * deblur ray tiling            R:lse_nerf/lse_ray_generator.py:103-147
 
 These are O(rays) / O(control points) element-wise ops, so they stay in torch (device-agnostic, differentiable); what
-they consume from the HIP path are d(loss)/d(origins) and d(loss)/d(directions), which ``lse_positions_bwd`` +
-``lse_ray_grad_reduce`` + ``lse_ray_features_bwd`` produce.  Checked against scipy (Slerp / interp1d / Rotation) in
+they consume from the HIP path are d(loss)/d(origins) and d(loss)/d(directions), which ``lse_ray_grad_from_dx01``
+(= ``lse_positions_bwd`` + ``lse_ray_grad_reduce`` in one launch) + ``lse_ray_features_bwd`` produce.  Checked against scipy (Slerp / interp1d / Rotation) in
 ``tests/test_cameras_cpu.py`` -- the same oracle the reference's own self-tests use.
 """
 from __future__ import annotations

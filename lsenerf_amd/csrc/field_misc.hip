@@ -56,18 +56,12 @@ __global__ __launch_bounds__(256) void positions_fwd_kernel(const float *__restr
     sel[i] = s ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void positions_bwd_kernel(const float *__restrict__ o, const float *__restrict__ d,
-                                                            const int32_t *__restrict__ ri, const float *__restrict__ ts,
-                                                            const float *__restrict__ te, int64_t n, int contraction,
-                                                            Box box, const float *__restrict__ dx01,
-                                                            float *__restrict__ dpos, const int64_t *__restrict__ n_dev)
+// d(pos) of one sample from d(x01) = g: Jacobian of the contraction / aabb normalisation at p, selector-masked.  One body for
+// positions_bwd_kernel and ray_grad_dx01_kernel, so that both produce the same bits.
+__device__ __forceinline__ void positions_bwd_sample(const float p[3], const float g[3], int contraction, const Box &box,
+                                                     float out[3])
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= lse::clamp_count(n, n_dev)) return;
-    float p[3], t2;
-    sample_pos(o, d, ri, ts, te, i, p, t2);
-    float g[3] = {dx01[i * 3 + 0], dx01[i * 3 + 1], dx01[i * 3 + 2]};
-    float x[3], out[3];
+    float x[3];
     if (contraction) {
         const float a0 = fabsf(p[0]), a1 = fabsf(p[1]), a2 = fabsf(p[2]);
         const float mag = fmaxf(a0, fmaxf(a1, a2));
@@ -96,7 +90,24 @@ __global__ __launch_bounds__(256) void positions_bwd_kernel(const float *__restr
     }
     const bool s = x[0] > 0.f && x[0] < 1.f && x[1] > 0.f && x[1] < 1.f && x[2] > 0.f && x[2] < 1.f;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) dpos[i * 3 + k] = s ? out[k] : 0.f;
+    for (int k = 0; k < 3; ++k) out[k] = s ? out[k] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void positions_bwd_kernel(const float *__restrict__ o, const float *__restrict__ d,
+                                                            const int32_t *__restrict__ ri, const float *__restrict__ ts,
+                                                            const float *__restrict__ te, int64_t n, int contraction,
+                                                            Box box, const float *__restrict__ dx01,
+                                                            float *__restrict__ dpos, const int64_t *__restrict__ n_dev)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= lse::clamp_count(n, n_dev)) return;
+    float p[3], t2;
+    sample_pos(o, d, ri, ts, te, i, p, t2);
+    const float g[3] = {dx01[i * 3 + 0], dx01[i * 3 + 1], dx01[i * 3 + 2]};
+    float out[3];
+    positions_bwd_sample(p, g, contraction, box, out);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dpos[i * 3 + k] = out[k];
 }
 
 // one wave per ray: d_o = sum dpos, d_d = sum dpos * (ts+te)/2
@@ -117,6 +128,51 @@ __global__ __launch_bounds__(256) void ray_grad_kernel(const float *__restrict__
             const float g = dpos[i * 3 + c];
             ao[c] += g;
             ad[c] = fmaf(g, tm, ad[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { ao[c] = lse::wave_sum(ao[c]); ad[c] = lse::wave_sum(ad[c]); }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (d_o) d_o[ray * 3 + c] = ao[c];
+            if (d_d) d_d[ray * 3 + c] = ad[c];
+        }
+    }
+}
+
+// The two kernels above in one, one wave per ray: d(pos) of a sample is formed from d(x01) on the fly (positions_bwd_sample) and
+// summed like ray_grad_kernel sums it -- same lane-strided order, same wave_sum -- so d_o / d_d carry the same bits and d(pos)
+// [N,3] never exists in memory.
+__global__ __launch_bounds__(256) void ray_grad_dx01_kernel(const float *__restrict__ o, const float *__restrict__ d,
+                                                            const float *__restrict__ ts, const float *__restrict__ te,
+                                                            const int64_t *__restrict__ packed, int n_rays, int contraction,
+                                                            Box box, const float *__restrict__ dx01,
+                                                            float *__restrict__ d_o, float *__restrict__ d_d)
+{
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
+    const float ro[3] = {o[ray * 3 + 0], o[ray * 3 + 1], o[ray * 3 + 2]};
+    const float rd[3] = {d[ray * 3 + 0], d[ray * 3 + 1], d[ray * 3 + 2]};
+    float ao[3] = {0.f, 0.f, 0.f}, ad[3] = {0.f, 0.f, 0.f};
+    for (int64_t k = lane; k < cnt; k += 64) {
+        const int64_t i = s0 + k;
+        const float t0 = ts[i], t1 = te[i];
+        const float g[3] = {dx01[i * 3 + 0], dx01[i * 3 + 1], dx01[i * 3 + 2]};
+        const float s = t0 + t1;
+        float p[3], out[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = ro[c] + rd[c] * s / 2.f;       // sample_pos, ray mode
+        positions_bwd_sample(p, g, contraction, box, out);
+        const float tm = (t0 + t1) * 0.5f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v = out[c];
+            asm volatile("" : "+v"(v));     // the value positions_bwd_kernel would have stored: no contraction into the sums
+            ao[c] += v;
+            ad[c] = fmaf(v, tm, ad[c]);
         }
     }
 #pragma unroll
@@ -416,6 +472,20 @@ extern "C" int lse_ray_grad_reduce(const float *d_pos, const float *t_starts, co
     hipLaunchKernelGGL(ray_grad_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), d_pos, t_starts,
                        t_ends, packed_info, n_rays, d_rays_o, d_rays_d);
     return lse::check_launch("lse_ray_grad_reduce");
+}
+
+extern "C" int lse_ray_grad_from_dx01(const float *rays_o, const float *rays_d, const float *t_starts, const float *t_ends,
+                                      const int64_t *packed_info, int32_t n_rays, int32_t contraction, const float *h_aabb,
+                                      const float *d_x01, float *d_rays_o, float *d_rays_d, lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_ray_grad_from_dx01: n_rays < 0");
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(rays_o && rays_d && t_starts && t_ends && packed_info && d_x01, "lse_ray_grad_from_dx01: null pointer");
+    LSE_REQUIRE(contraction || h_aabb, "lse_ray_grad_from_dx01: aabb normalisation needs h_aabb");
+    if (!d_rays_o && !d_rays_d) return LSE_OK;
+    hipLaunchKernelGGL(ray_grad_dx01_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), rays_o, rays_d,
+                       t_starts, t_ends, packed_info, n_rays, contraction, make_box(h_aabb), d_x01, d_rays_o, d_rays_d);
+    return lse::check_launch("lse_ray_grad_from_dx01");
 }
 
 extern "C" int lse_density_fwd(const float *h, const uint8_t *selector, float scale, float *sigma, int64_t n,

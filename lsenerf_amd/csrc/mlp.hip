@@ -1647,6 +1647,52 @@ extern "C" int lse_mlp_fwd(const lse_mlp_desc *desc, const float *params, const 
     LSE_MLP_DISPATCH(launch_fwd, desc, a, st);
 }
 
+extern "C" int lse_mlp_fwd_pair(const lse_mlp_desc *base_desc, const float *base_params, const float *y,
+                                const uint8_t *selector, float density_scale, const lse_mlp_desc *head_desc,
+                                const float *head_params, const float *row_bias, const int32_t *row_bias_idx, float *h,
+                                float *sigma, float *out, int32_t out_cols, int64_t n, const int64_t *n_dev,
+                                lse_stream_t stream)
+{
+    int rc = check_desc(base_desc, "lse_mlp_fwd_pair (base)");
+    if (rc) return rc;
+    rc = check_desc(head_desc, "lse_mlp_fwd_pair (head)");
+    if (rc) return rc;
+    LSE_REQUIRE(n >= 0, "lse_mlp_fwd_pair: n < 0");
+    LSE_REQUIRE(out_cols == 16 || out_cols == 4, "lse_mlp_fwd_pair: out_cols must be 16 or 4");
+    const bool base_ok = base_desc->n_in == 32 && base_desc->width == 64 && base_desc->n_hidden_layers == 1 &&
+                         base_desc->out_activation == LSE_ACT_NONE && base_desc->arith == LSE_MLP_ARITH_AUTO;
+    const bool head_ok = head_desc->n_in == 16 && head_desc->width == 64 && head_desc->n_hidden_layers == 2 &&
+                         head_desc->in_layout == LSE_IN_ROWMAJOR && head_desc->arith == LSE_MLP_ARITH_AUTO;
+    if (!base_ok || !head_ok) {
+        lse::set_error("lse_mlp_fwd_pair: built for the 32->64->16 base (no output activation) and the 16->64->64->16 row-major head "
+                       "in bf16x6 arithmetic only (got base n_in=%d width=%d n_hidden_layers=%d, head n_in=%d width=%d "
+                       "n_hidden_layers=%d in_layout=%d): call lse_mlp_fwd twice",
+                       base_desc->n_in, base_desc->width, base_desc->n_hidden_layers, head_desc->n_in, head_desc->width,
+                       head_desc->n_hidden_layers, head_desc->in_layout);
+        return LSE_E_UNSUPPORTED;
+    }
+    if (n == 0) return LSE_OK;
+    LSE_REQUIRE(base_params && y && head_params && h && sigma && out, "lse_mlp_fwd_pair: null pointer");
+    MlpArgs a{}, b{};
+    a.params = base_params; a.in = y; a.out = h; a.n = n; a.n_stride = n; a.n_dev = n_dev;
+    a.out_activation = LSE_ACT_NONE; a.out_cols = 16; a.sigma_out = sigma; a.selector = selector; a.density_scale = density_scale;
+    a.act_tiled = 3;
+    fill_view(a, base_desc);
+    b.params = head_params; b.in = h; b.row_bias = row_bias; b.row_bias_idx = row_bias_idx; b.out = out; b.n = n; b.n_stride = n;
+    b.n_dev = n_dev; b.out_activation = head_desc->out_activation; b.out_cols = out_cols; b.act_tiled = 3;
+    fill_view(b, head_desc);
+    hipStream_t st = lse::as_stream(stream);
+    const int64_t tiles = (n + 31) / 32;
+    const int blocks = (int)std::min<int64_t>((tiles + 7) / 8, 512);      // the grid of mlp_fwd3_kernel: two resident workgroups per CU
+    if (base_desc->in_layout == LSE_IN_LEVELMAJOR)
+        hipLaunchKernelGGL((mlp_fwd_pair_kernel<LSE_IN_LEVELMAJOR>), dim3(blocks), dim3(512),
+                           X6FwdPair<LSE_IN_LEVELMAJOR>::lds_bytes, st, a, b);
+    else
+        hipLaunchKernelGGL((mlp_fwd_pair_kernel<LSE_IN_ROWMAJOR>), dim3(blocks), dim3(512), X6FwdPair<LSE_IN_ROWMAJOR>::lds_bytes,
+                           st, a, b);
+    return lse::check_launch("lse_mlp_fwd_pair");
+}
+
 extern "C" int lse_mlp_bwd(const lse_mlp_desc *desc, const float *params, const float *in, const float *act,
                            int32_t act_tiled, const float *out, int32_t out_cols, const float *d_out, const float *d_sigma,
                            const uint8_t *selector, float density_scale, float *d_out_pre, float *d_act, float *d_act0,

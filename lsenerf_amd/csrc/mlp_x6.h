@@ -452,6 +452,209 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 }
 
 // ------------------------------------------------------------------------------------------------------
+// forward of the base MLP <32, 1, INL> and the head MLP <16, 2, row-major> on the same samples in one launch (lse_mlp_fwd_pair).
+// The base's output accumulator o[0][ct] (C/D layout: lane (j, q) holds columns 4q .. 4q+3 of sample j) IS the head's k = 16
+// input raw[ct][0] of load_in_x6 / split_in16: per tile the base runs, stores h and sigma, and the head continues on the same
+// registers -- h is written once and never read back, one launch / weight-staging prologue / tail instead of two, and the head's
+// MFMA chains run in the waves that would otherwise wait for the next tile's y.  Both phases are the code of mlp_fwd3_kernel
+// (same pieces, same MFMA order per layer, same epilogues), so h, sigma and the head output carry the same bits as two launches
+// and the recomputing backward reproduces them.  Nothing is saved (act_tiled = 3 only).
+// ------------------------------------------------------------------------------------------------------
+template <int INL>
+struct X6FwdPair {
+    using B = X6Fwd<32, 1, INL>;
+    using H = X6Fwd<16, 2, LSE_IN_ROWMAJOR>;
+    // [base img0 | base imgO | head img0 | head imgH | head imgO | the two "minus identity" operands (shared)]
+    static constexpr int B_IMG0 = 0, B_IMGO = B_IMG0 + B::IMG0, H_IMG0 = B_IMGO + B::IMGO, H_IMGH = H_IMG0 + H::IMG0,
+                         H_IMGO = H_IMGH + H::IMGH, NEGI = H_IMGO + H::IMGO;
+    static constexpr int lds_bytes = (NEGI + 128) * 16;
+};
+
+template <int INL>
+__global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */, MlpArgs b /* head: b.in is unused */)
+{
+    using C = X6FwdPair<INL>;
+    constexpr int CT = 2, NW = 8, TS = 16 * CT, HB = 4, WIDTH = 64;
+    extern __shared__ float lds[];
+    u32x4 *img = reinterpret_cast<u32x4 *>(lds);
+    u32x4 *b_img0 = img + C::B_IMG0, *b_imgO = img + C::B_IMGO;
+    u32x4 *h_img0 = img + C::H_IMG0, *h_imgH = img + C::H_IMGH, *h_imgO = img + C::H_IMGO;
+
+    stage_in32_image<HB>(b_img0, a.params + a.w0_col, a.w0_ld, a.w0_mask0, 64 * NW);
+    stage_chain_image<1, 2>(b_imgO, a.params + a.rest_off, WIDTH, 16, 64 * NW);
+    stage_in16_image<HB>(h_img0, b.params + b.w0_col, b.w0_ld, b.w0_mask0, 64 * NW);
+    stage_chain_image<HB, 2>(h_imgH, b.params + b.rest_off, WIDTH, WIDTH, 64 * NW);
+    stage_chain_image<1, 2>(h_imgO, b.params + b.rest_off + WIDTH * WIDTH, WIDTH, 16, 64 * NW);
+    if (threadIdx.x < 64) {
+        u32x4 t[2];
+        neg_identity(threadIdx.x, t);
+        img[C::NEGI + threadIdx.x] = t[0];
+        img[C::NEGI + 64 + threadIdx.x] = t[1];
+    }
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+    a.n = lse::clamp_count(a.n, a.n_dev);
+    const int64_t n = a.n;
+    const int64_t n_tiles = (n + TS - 1) / TS;
+    const int64_t total_waves = (int64_t)gridDim.x * NW;
+    const int64_t per = (n_tiles + total_waves - 1) / total_waves;
+    const int64_t w_id = (int64_t)blockIdx.x * NW + wave;
+    const int64_t t_begin = min(n_tiles, w_id * per), t_end = min(n_tiles, t_begin + per);
+    const int oc = b.out_cols;
+    struct NegI {          // "minus identity" operands from LDS, as in mlp_fwd3_kernel
+        const u32x4 *p;
+        __device__ __forceinline__ u32x4 operator[](int k) const { return p[64 * k]; }
+    };
+    const NegI nI{img + C::NEGI + lane};
+
+    f32x4 raw_nx[CT][2];
+    if (t_begin < t_end) load_in_x6<32, INL, CT>(a, t_begin, j, q, raw_nx);
+    int idx_nx[CT] = {};
+    if (b.row_bias && b.row_bias_idx && t_begin < t_end) {
+        const int64_t b0 = t_begin * TS;
+        const int nr = (int)min((int64_t)TS, n - b0);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) idx_nx[ct] = b.row_bias_idx[b0 + min(ct * 16 + j, nr - 1)];
+    }
+    for (int64_t tile = t_begin; tile < t_end; ++tile) {
+        const int64_t tile_base = tile * TS;
+        const int n_rem = (int)min((int64_t)TS, n - tile_base);
+        int sl[CT];
+        bool valid[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            valid[ct] = ct * 16 + j < n_rem;
+            sl[ct] = valid[ct] ? ct * 16 + j : n_rem - 1;
+        }
+        f32x4 o[1][CT];
+        // ================= base: 32 -> 64 -> 16, density head =================
+        {
+            f32x4 raw[CT][2];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int k = 0; k < 2; ++k) raw[ct][k] = raw_nx[ct][k];
+            uint32_t selv[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) selv[ct] = (a.selector && q == 0) ? (uint32_t)a.selector[tile_base + sl[ct]] : 1u;
+            f32x4 h[HB][CT];
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (tile + 1 < t_end) load_in_x6<32, INL, CT>(a, tile + 1, j, q, raw_nx);
+            first_layer_x6<32, CT>(h, b_img0, raw, nI, lane);
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) h[rb][ct][r] = relu_bits(h[rb][ct][r]);
+            PiecesB<HB> x[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) split_pair(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) o[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            layer_x6_ct<1, 2, CT>(o, b_imgO, x, lane);
+            float *h_t = a.out + tile_base * 16;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+                if (valid[ct]) {
+                    *reinterpret_cast<f32x4 *>(h_t + (unsigned)(sl[ct] * 16 + 4 * q)) = o[0][ct];
+                    if (q == 0) a.sigma_out[tile_base + sl[ct]] = selv[ct] != 0u ? a.density_scale * expf(o[0][ct][0]) : 0.f;
+                }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ================= head: 16 (+ per-row bias) -> 64 -> 64 -> 16, input = o[0][ct] =================
+        {
+            f32x4 h[HB][CT];
+            if (b.row_bias) {
+                int64_t rowv[CT];
+                if (b.row_bias_idx) {      // this tile's rows were requested during the previous tile; the next tile's are requested now
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) rowv[ct] = idx_nx[ct];
+                    if (tile + 1 < t_end) {
+                        const int64_t nb_ = tile_base + TS;
+                        const int nr = (int)min((int64_t)TS, n - nb_);
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) idx_nx[ct] = b.row_bias_idx[nb_ + min(ct * 16 + j, nr - 1)];
+                    }
+                } else {
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) rowv[ct] = tile_base + sl[ct];
+                }
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    const int64_t row = rowv[ct];
+#pragma unroll
+                    for (int rb = 0; rb < HB; ++rb)
+                        h[rb][ct] = *reinterpret_cast<const f32x4 *>(b.row_bias + row * WIDTH + 16 * rb + 4 * q);
+                }
+            } else {
+#pragma unroll
+                for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+            f32x4 rawh[CT][1];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) rawh[ct][0] = o[0][ct];
+            first_layer_x6<16, CT>(h, h_img0, rawh, nI, lane);
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) h[rb][ct][r] = relu_bits(h[rb][ct][r]);
+            PiecesB<HB> x[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) split_pair(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4 h2[HB][CT];
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) h2[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            layer_x6_ct<HB, 2, CT>(h2, h_imgH, x, lane);
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) h2[rb][ct][r] = relu_bits(h2[rb][ct][r]);
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) split_pair(h2[2 * s2][ct], h2[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4 r[1][CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) r[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            layer_x6_ct<1, 2, CT>(r, h_imgO, x, lane);
+            float *out_t = b.out + tile_base * oc;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                if (b.out_activation == LSE_ACT_SIGMOID) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) r[0][ct][k] = __builtin_amdgcn_rcpf(1.f + __expf(-r[0][ct][k]));
+                }
+                if (valid[ct]) {
+                    if (oc == 16) *reinterpret_cast<f32x4 *>(out_t + (unsigned)(sl[ct] * 16 + 4 * q)) = r[0][ct];
+                    else if (q == 0) *reinterpret_cast<f32x4 *>(out_t + (unsigned)(sl[ct] * 4)) = r[0][ct];
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // backward (third generation): data + weight gradients in one pass with NOTHING saved by the forward (act_tiled = 3):
 // the hidden layers are recomputed (the matrix-core time of a recomputed layer is a quarter of the time its activation
 // took to store and load).  WIDTH = 64; head <16, 2, row-major> and base <32, 1, level-major / row-major>.

@@ -2,7 +2,7 @@
 
 * ``render_ray_bundle`` -- nerfstudio 0.3.2 ``Model.get_outputs_for_camera_ray_bundle`` (chunks of ``eval_num_rays_per_chunk`` rays
   through ``forward``, outputs concatenated and viewed as ``[*leading shape, C]``).  In eval mode with ``LSEField`` every chunk takes
-  the count-free route instead: deferred sampling (no sample count read back), ``density_packed`` / ``rgb_packed`` with the
+  the count-free route instead: deferred sampling (no sample count read back), ``density_rgb_packed`` with the
   device-side count, and ``lse_eval_composite`` writing the chunk's rows of the image buffers directly -- no host synchronisation
   inside the loop, no per-sample ``RaySamples`` gathers, no autograd Functions.  Its values are those of the ``forward`` loop bit for
   bit (the mapper keys, formed once over the whole image, to GEMM rounding).
@@ -90,9 +90,8 @@ def _render_count_free(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
             part, near_plane=cfg.near_plane, far_plane=cfg.far_plane, render_step_size=cfg.render_step_size,
             alpha_thre=cfg.alpha_thre, cone_angle=cfg.cone_angle)
         rays_o, rays_d = part.origins.contiguous(), part.directions.contiguous()
-        sigma, h, _ = fld.density_packed(rays_o, rays_d, ri, ts, te, packed, n_dev)
         table, eidx = fld._eval_emb(hi - lo, dev) if fld.embedding_appearance is not None else (None, None)
-        head = fld.rgb_packed(h, rays_d, eidx, ri, packed, table, n_dev)
+        sigma, _, _, head = fld.density_rgb_packed(rays_o, rays_d, ri, ts, te, packed, eidx, table, n_dev)
         ops.eval_composite(ts, te, sigma, head, packed, rgb[lo:hi], acc[lo:hi], depth[lo:hi], nsamples[lo:hi],
                            nan_to_num=not linear, background=background, clamp=not linear, workspace=ws)
     model.occupancy_grid.check_deferred_overflow()      # the one read-back: a truncated ray raises here

@@ -503,18 +503,54 @@ class LSEField(nn.Module):
                        ) -> Tuple[Tensor, Tensor, Tensor]:
         """Fast path of get_density on packed samples: returns (sigma[N], h[N,16] base-MLP output, selector[N]).
         ``n_dev``: device-side sample count (int64 [1]) when the arrays have capacity extent (deferred sampling)."""
+        x01, sel, y = self._encode_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, n_dev)
+        h, sigma = self._base_mlp(y, sel, x01.shape[0], n_dev)
+        return sigma, h, sel
+
+    def _encode_packed(self, rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, n_dev: Optional[Tensor] = None):
+        """(x01[N,3], selector[N], level-major hash features y) of packed samples: what the base MLP consumes."""
         pp = self._take_prepass(rays_o, rays_d, ray_idx, t_starts) if t_starts is not None else None
         if pp is not None:   # survivors of this step's visibility pre-pass: positions + hash features are already there
             x01, sel = ops.positions(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, self._contraction == "inf",
                                      None if self._contraction == "inf" else self._aabb_list(), precomputed=(pp["x01"], pp["sel"]),
                                      n_dev=n_dev)
             y = ops.hash_encode(x01, self.mlp_base_grid.params, self.mlp_base_grid.meta, precomputed=pp["y"], n_dev=n_dev)
-            h, sigma = self._base_mlp(y, sel, x01.shape[0], n_dev)
-            return sigma, h, sel
+            return x01, sel, y
         x01, sel = self._x01(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, n_dev)
         y = self.mlp_base_grid.forward_levelmajor(x01, n_dev)
-        h, sigma = self._base_mlp(y, sel, x01.shape[0], n_dev)
-        return sigma, h, sel
+        return x01, sel, y
+
+    def density_rgb_packed(self, rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, emb_idx: Optional[Tensor],
+                           emb_table: Optional[Tensor], n_dev: Optional[Tensor] = None
+                           ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """``density_packed`` followed by ``rgb_packed`` on the same samples: returns (sigma[N], h[N,16], selector[N], compact head
+        output [N,4]).  With ``ops.MLP_FWD_PAIR`` and the production shapes the two MLP forwards are ONE launch (``ops.fused_mlp_pair``:
+        h stays in registers between them); otherwise the two calls, with the same bits."""
+        x01, sel, y = self._encode_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, n_dev)
+        n = x01.shape[0]
+        base, head = self.mlp_base_mlp, self.mlp_head
+        row_bias, head_meta = self._head_row_bias(rays_d, emb_idx, emb_table)
+        if base.in_pad == base.in_dim and ops.mlp_pair_usable(base.params, y, base.meta(), head.params, head_meta, row_bias,
+                                                              ray_idx, packed_info):
+            h, sigma, out = ops.fused_mlp_pair(base.params, y, sel, self.average_init_density, base.meta(), head.params, head_meta,
+                                               n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev)
+            return sigma, h, sel, out
+        h, sigma = self._base_mlp(y, sel, n, n_dev)
+        out = ops.fused_mlp(head.params, h, head_meta, n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev)
+        return sigma, h, sel, out
+
+    def _head_row_bias(self, rays_d: Tensor, emb_idx: Optional[Tensor], emb_table: Optional[Tensor]):
+        """(row_bias[R, W], head MlpMeta with the in-place first-layer view) -- see ``rgb_packed``."""
+        head = self.mlp_head
+        emb_dim = 0 if emb_table is None else emb_table.shape[1]
+        if emb_dim != self.appearance_embedding_dim:        # eval mode "zero": the embedding columns meet zeros
+            emb_table = torch.zeros((1, self.appearance_embedding_dim), dtype=torch.float32, device=rays_d.device) \
+                if self.appearance_embedding_dim > 0 else None
+            emb_idx = torch.zeros(rays_d.shape[0], dtype=torch.int32, device=rays_d.device) if emb_table is not None else None
+        row_bias = ops.ray_bias(rays_d, emb_table, emb_idx, head.params, head.layer_width)        # [R, W]
+        meta = ops.MlpMeta(16, head.layer_width, head.n_hidden_layers, head.out_act, _lib.LSE_IN_ROWMAJOR,
+                           w0_ld=head.in_pad, w0_col=15, w0_mask_col0=1)
+        return row_bias, meta
 
     def rgb_packed(self, h: Tensor, rays_d: Tensor, emb_idx: Optional[Tensor], ray_idx: Optional[Tensor],
                    packed_info: Optional[Tensor], emb_table: Optional[Tensor], n_dev: Optional[Tensor] = None) -> Tensor:
@@ -526,17 +562,8 @@ class LSEField(nn.Module):
         geometry columns are per sample: the fused MLP reads h[N,16] (column 0 = density logit) against columns 15..30 of
         W_in IN PLACE (first-layer view: leading dimension in_pad, column offset 15, column 0 masked) -- the parameter
         vector is never split or copied, and both kernels accumulate their weight gradients straight into its .grad."""
-        head = self.mlp_head
-        n = h.shape[0]
-        emb_dim = 0 if emb_table is None else emb_table.shape[1]
-        if emb_dim != self.appearance_embedding_dim:        # eval mode "zero": the embedding columns meet zeros
-            emb_table = torch.zeros((1, self.appearance_embedding_dim), dtype=h.dtype, device=h.device) \
-                if self.appearance_embedding_dim > 0 else None
-            emb_idx = torch.zeros(rays_d.shape[0], dtype=torch.int32, device=h.device) if emb_table is not None else None
-        row_bias = ops.ray_bias(rays_d, emb_table, emb_idx, head.params, head.layer_width)        # [R, W]
-        meta = ops.MlpMeta(16, head.layer_width, head.n_hidden_layers, head.out_act, _lib.LSE_IN_ROWMAJOR,
-                           w0_ld=head.in_pad, w0_col=15, w0_mask_col0=1)
-        return ops.fused_mlp(head.params, h, meta, n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev)
+        row_bias, meta = self._head_row_bias(rays_d, emb_idx, emb_table)
+        return ops.fused_mlp(self.mlp_head.params, h, meta, h.shape[0], row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev)
 
     def _train_emb_table(self):
         if self.embedding_appearance is None:

@@ -565,7 +565,6 @@ class LSENeRFModel(nn.Module):
         grid = getattr(fld, "mlp_base_grid", None)
         if grid is not None and hasattr(grid, "dense_steps"):      # regime hint for the hash backward's path thresholds
             grid.dense_steps = not (self.config.cone_angle and self.config.cone_angle > 0)
-        sigma, h, _ = fld.density_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, n_dev)
         if fld.embedding_appearance is None:
             table, eidx = None, None
         elif fld.training:
@@ -574,7 +573,8 @@ class LSENeRFModel(nn.Module):
                                                         rays_o.device).contiguous()
         else:
             table, eidx = fld._eval_emb(num_rays, rays_o.device)
-        rgb16 = fld.rgb_packed(h, rays_d, eidx, ray_idx, packed_info, table, n_dev)
+        # density_packed -> rgb_packed on the same samples (the two MLP forwards are one launch where the shapes allow)
+        sigma, _, _, rgb16 = fld.density_rgb_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, eidx, table, n_dev)
         linear = isinstance(self.renderer_rgb, LinearRenderer)
         if not (self.training or linear):
             rgb16 = torch.nan_to_num(rgb16)

@@ -402,8 +402,18 @@ class _PositionsFn(torch.autograd.Function):
         rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info = ctx.saved_tensors
         n = ctx.n
         d_x01 = _c(d_x01)
-        d_pos = torch.empty((n, 3), dtype=torch.float32, device=d_x01.device)
         aabb_arr = (ctypes.c_float * 6)(*ctx.aabb6) if ctx.aabb6 is not None else None
+        if FUSED_RAY_GRAD and ray_idx is not None and packed_info is not None:
+            # ray path: d(pos) is formed and summed per ray in one launch, it never exists in memory (same bits as the two launches)
+            d_o = torch.empty_like(rays_o) if ctx.needs_input_grad[0] else None
+            d_d = torch.empty_like(rays_d) if ctx.needs_input_grad[1] else None
+            if d_o is not None or d_d is not None:
+                _lib.call("lse_ray_grad_from_dx01", _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(t_starts, "t_starts"),
+                          _f32(t_ends, "t_ends"), _chk(packed_info, torch.int64, "packed_info"), rays_o.shape[0],
+                          int(ctx.contraction), aabb_arr, _f32(d_x01, "d_x01"), _f32(d_o, "d_o", True), _f32(d_d, "d_d", True),
+                          _stream())
+            return d_o, d_d, None, None, None, None, None, None, None, None
+        d_pos = torch.empty((n, 3), dtype=torch.float32, device=d_x01.device)
         _call_n("lse_positions_bwd", ctx.n_dev, _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d", True),
                   _chk(ray_idx, torch.int32, "ray_idx", True), _f32(t_starts, "t_starts", True),
                   _f32(t_ends, "t_ends", True), n, int(ctx.contraction), aabb_arr, _f32(d_x01, "d_x01"),
@@ -667,6 +677,103 @@ class _MlpFn(torch.autograd.Function):
         return (None if direct is not None else d_params), d_in, d_bias, None, None, None, None, None, None, None, None
 
 
+def _mlp_pair_shapes(base_meta: MlpMeta, head_meta: MlpMeta) -> bool:
+    """The shapes lse_mlp_fwd_pair is built for: the recompute-all production pair (base 32 -> 64 -> 16, head 16 -> 64 -> 64 -> 16)."""
+    return (base_meta.n_in == 32 and base_meta.width == 64 and base_meta.n_hidden_layers == 1
+            and base_meta.out_activation == _lib.LSE_ACT_NONE
+            and head_meta.n_in == 16 and head_meta.width == 64 and head_meta.n_hidden_layers == 2
+            and head_meta.in_layout == _lib.LSE_IN_ROWMAJOR
+            and base_meta.arith == _lib.LSE_MLP_ARITH_AUTO and head_meta.arith == _lib.LSE_MLP_ARITH_AUTO)
+
+
+class _MlpPairFn(torch.autograd.Function):
+    """Base MLP (+ density head) and head MLP on the same samples: ONE forward launch (lse_mlp_fwd_pair), the two recomputing
+    backward launches of ``_MlpFn`` (act_tiled = 3) with the same arguments -- head first, its d_in (plus any gradient that reaches
+    ``h`` from elsewhere) is the base's d_out."""
+
+    @staticmethod
+    def forward(ctx, base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, base_meta: MlpMeta,
+                head_meta: MlpMeta, n: int, out_cols: int, density_scale, n_dev=None):
+        dev = base_params.device
+        h = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        sigma = torch.empty(n, dtype=torch.float32, device=dev)
+        out = torch.empty((n, out_cols), dtype=torch.float32, device=dev)
+        bdesc, hdesc = base_meta.desc(), head_meta.desc()
+        _call_n("lse_mlp_fwd_pair", n_dev, ctypes.byref(bdesc), _f32(base_params, "base params"), _f32(y, "mlp input"),
+                _chk(selector, torch.uint8, "selector", True), float(density_scale), ctypes.byref(hdesc),
+                _f32(head_params, "head params"), _f32(row_bias, "row_bias", True),
+                _chk(row_bias_idx, torch.int32, "row_bias_idx", True), ctypes.c_void_p(h.data_ptr()),
+                ctypes.c_void_p(sigma.data_ptr()), ctypes.c_void_p(out.data_ptr()), out_cols, n, _stream())
+        ctx.save_for_backward(base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, h, out)
+        ctx.base_meta, ctx.head_meta, ctx.n, ctx.out_cols, ctx.density_scale, ctx.n_dev = \
+            base_meta, head_meta, n, out_cols, density_scale, n_dev
+        ctx.set_materialize_grads(False)
+        return h, sigma, out
+
+    @staticmethod
+    def backward(ctx, d_h, d_sigma, d_out):
+        base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, h, out = ctx.saved_tensors
+        n, out_cols, dev = ctx.n, ctx.out_cols, base_params.device
+        # ---- head (the call of _MlpFn.backward at act_tiled = 3)
+        d_in_head, d_bias, d_hp_ret = None, None, None
+        if d_out is not None:
+            d_out = _c(d_out)
+            need_bias = row_bias is not None and ctx.needs_input_grad[4]
+            d_bias = torch.zeros_like(row_bias) if need_bias else None
+            d_in_head = torch.empty_like(h)
+            direct = _direct_grad(head_params)
+            d_hp = direct if direct is not None else torch.zeros_like(head_params)
+            d_hp_ret = None if direct is not None else d_hp
+            hdesc = ctx.head_meta.desc()
+            _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(hdesc), _f32(head_params, "params"), _f32(h, "mlp input"), None, 3,
+                    _f32(out, "out"), out_cols, _f32(d_out, "d_out"), None, None, 0.0, None, None, None,
+                    _f32(d_in_head, "d_in"), _f32(d_hp, "d_params"), _f32(row_bias, "row_bias", True),
+                    _chk(row_bias_idx, torch.int32, "row_bias_idx", True), _f32(d_bias, "d_bias", True), n, _stream())
+        # ---- base: d_out = the head's d_in + whatever else consumed h
+        if d_h is not None and d_in_head is not None:
+            d_base = d_in_head + d_h
+        else:
+            d_base = d_in_head if d_in_head is not None else d_h
+        d_y, d_bp_ret = None, None
+        if d_base is not None or d_sigma is not None:
+            d_base = _c(d_base) if d_base is not None else torch.zeros((n, 16), dtype=torch.float32, device=dev)
+            d_sigma = _c(d_sigma) if d_sigma is not None else None
+            d_y = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+            direct = _direct_grad(base_params)
+            d_bp = direct if direct is not None else torch.zeros_like(base_params)
+            d_bp_ret = None if direct is not None else d_bp
+            bdesc = ctx.base_meta.desc()
+            _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(bdesc), _f32(base_params, "params"), _f32(y, "mlp input"), None, 3,
+                    _f32(h, "out"), 16, _f32(d_base, "d_out"), _f32(d_sigma, "d_sigma", True),
+                    _chk(selector, torch.uint8, "selector", True), float(ctx.density_scale), None, None, None,
+                    _f32(d_y, "d_in", True), _f32(d_bp, "d_params"), None, None, None, n, _stream())
+        return d_bp_ret, d_y, None, d_hp_ret, d_bias, None, None, None, None, None, None, None, None
+
+
+def mlp_pair_usable(base_params, y, base_meta: MlpMeta, head_params, head_meta: MlpMeta, row_bias, row_bias_idx,
+                    bias_packed_info) -> bool:
+    """Whether ``fused_mlp_pair`` may replace ``fused_mlp`` (base, density head) followed by ``fused_mlp`` (head) on the same
+    samples: the switch is on, the shapes are the pair's, and either nothing needs a gradient or both calls would take the
+    recompute-all path (``_MlpFn.forward``: nothing saved, act_tiled = 3)."""
+    if not (MLP_FWD_PAIR and _mlp_pair_shapes(base_meta, head_meta)):
+        return False
+    need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
+    if not need_grad:
+        return True
+    return bool(FUSED_WGRAD and ACT_TILED and RECOMPUTE_ALL and base_params.requires_grad and head_params.requires_grad
+                and (row_bias is None or not row_bias.requires_grad
+                     or (FUSED_BIAS_GRAD and row_bias_idx is not None and bias_packed_info is not None)))
+
+
+def fused_mlp_pair(base_params, y, selector, density_scale, base_meta: MlpMeta, head_params, head_meta: MlpMeta, n: int,
+                   row_bias=None, row_bias_idx=None, bias_packed_info=None, out_cols: int = 4, n_dev=None):
+    """``fused_mlp(base_params, y, base_meta, n, density=(selector, density_scale))`` followed by ``fused_mlp(head_params, h,
+    head_meta, n, row_bias, row_bias_idx, bias_packed_info, out_cols)`` with one forward launch; returns ``(h[n,16], sigma[n],
+    out[n,out_cols])`` with the same bits.  Callers check ``mlp_pair_usable`` first."""
+    return _MlpPairFn.apply(base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, base_meta, head_meta,
+                            n, out_cols, density_scale, n_dev)
+
+
 # Hooks into the hash backward, keyed by the TABLE they belong to (its storage address): a second model in the same process -- an
 # evaluation copy, the viewer thread nerfstudio runs beside training -- never sees the hooks of the model being trained.  (Until round
 # 3 these were two process-global variables.)
@@ -715,6 +822,8 @@ FUSED_BIAS_GRAD = True   # per-row bias gradient reduced inside lse_mlp_bwd (Fal
 RECOMPUTE_ALL = True   # head + base MLPs: save no activations at all, third-generation backward (bf16 pieces) recomputes them
 RECOMPUTE_FIRST_LAYER = True   # head MLP: the backward recomputes the first hidden layer instead of reading 1 KiB/sample back
 ACT_TILED = True      # tile-major saved activations (1 KiB contiguous per store/load instruction); fused path only
+MLP_FWD_PAIR = True   # base + head MLP forward on the same samples in one launch (lse_mlp_fwd_pair); False: two lse_mlp_fwd launches
+FUSED_RAY_GRAD = True   # ray path of the positions backward: one launch (lse_ray_grad_from_dx01); False: lse_positions_bwd + lse_ray_grad_reduce
 
 
 def fused_mlp(params, x, meta: MlpMeta, n: int, row_bias=None, row_bias_idx=None, bias_packed_info=None,
