@@ -503,14 +503,26 @@ int lse_loss_epilogue_bwd(const lse_epilogue_desc *desc, const float *col_rgb, c
                           const lse_mapper_mlp *mlp_evs, const float *g_rgb_loss, const float *g_event_loss, float *d_col,
                           float *d_prev, float *d_next, float *d_scalars, lse_stream_t stream);
 
-/* ---- optimiser: torch.optim.Adam semantics on a flat buffer (R:lse_nerf/lse_config.py:29-33) ----------- */
+/* ---- optimiser: torch.optim.Adam semantics on a flat buffer (R:lse_nerf/lse_config.py:29-33) -----------
+ * lse_adam_step and lse_adam_step_dev are kept for ABI compatibility only (they take 1 - beta from the float betas, see below);
+ * this package calls lse_adam_step_f64 and lse_adam_step_dev_sched. */
 int lse_adam_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
                   float beta1, float beta2, float eps, int32_t step, float grad_scale, lse_stream_t stream);
+/* The same with the scalars as doubles.  A float cannot hold 1 - beta next to beta: 0.999 rounds to 0.999000013 and 1.f - that is
+ * 1.3e-5 short of 0.001, which exp_avg_sq then is too.  Here 1 - beta and the bias corrections come from the double betas, each
+ * rounded once -- torch.optim.Adam's arithmetic.  (lse_adam_step is Adam for the betas AS ROUNDED, exact in itself.) */
+int lse_adam_step_f64(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, double lr,
+                      double beta1, double beta2, double eps, int32_t step, float grad_scale, lse_stream_t stream);
 /* The same with EVERY scalar of the step in device memory: hyper[6] = {lr, 1 - beta1^step, 1 / sqrt(1 - beta2^step), beta1, beta2,
  * eps}.  A launch captured into a HIP graph cannot carry new scalar arguments; lse_adam_schedule_dev (captured in front of it)
  * writes all six. */
 int lse_adam_step_dev(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, const float *hyper,
                       float grad_scale, lse_stream_t stream);
+/* lse_adam_step_dev with 1 - beta1 and 1 - beta2 taken from the schedule's double constants (sched[6] of lse_adam_schedule_dev, in
+ * device memory) instead of from the rounded betas in hyper: the bias corrections in hyper come from the double betas too, and
+ * lse_adam_step_dev's float differences do not match them (the step is 6e-6 too long while the moments are young). */
+int lse_adam_step_dev_sched(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, const float *hyper,
+                            const double *sched, float grad_scale, lse_stream_t stream);
 /* Device-side optimizer clock: *step (optimizer steps taken so far, int64 in device memory) is advanced by one and hyper[6] of
  * the NEW step is written, with nerfstudio's ExponentialDecayScheduler lr = lr_init * (lr_final / lr_init)^(min(steps taken /
  * max_steps, 1)) (max_steps <= 0 or lr_final <= 0: constant lr_init; R:lse_nerf/lse_config.py:29-38).  The schedule's constants

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LSE_HIP_LIB", os.path.join(_HERE, "liblse_hip.so"))   # override: A/B builds of the same ABI
@@ -153,7 +153,9 @@ SIGNATURES = {
     "lse_occ_update_cells_dev": [P, P, P, F32, P, I64, F32, P, P],
     "lse_occ_mean_threshold": [P, I64, F32, P, P, P, P],
     "lse_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, I32, F32, P],
+    "lse_adam_step_f64": [P, P, P, P, I64, c_double, c_double, c_double, c_double, I32, F32, P],
     "lse_adam_step_dev": [P, P, P, P, I64, P, F32, P],
+    "lse_adam_step_dev_sched": [P, P, P, P, I64, P, P, F32, P],
     "lse_adam_schedule_dev": [P, P, P, P],
     "lse_compose_batch": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, I64, I32, P, P, P],
     "lse_compose_rays_bwd": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, P, P, P, P, P],
@@ -260,7 +262,8 @@ TIMING = None
 
 
 _TIMING_ALIAS = {"lse_hash_bwd_ex": "lse_hash_bwd", "lse_hash_bwd_levels": "lse_hash_bwd",     # one operation, three entry points
-                 "lse_mlp_fwd_pair": "lse_mlp_fwd"}                                              # base + head forward in one launch
+                 "lse_mlp_fwd_pair": "lse_mlp_fwd",                                              # base + head forward in one launch
+                 "lse_adam_step_f64": "lse_adam_step", "lse_adam_step_dev_sched": "lse_adam_step_dev"}     # the same kernel
 
 
 def call(name: str, *args):

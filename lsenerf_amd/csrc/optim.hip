@@ -10,8 +10,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                    float *__restrict__ m, float *__restrict__ v, int64_t n, float lr,
                                                    float b1, float b2, float eps, float bc1, float inv_sqrt_bc2,
-                                                   float gscale, const float *__restrict__ hyper)
+                                                   float gscale, const float *__restrict__ hyper, float omb1, float omb2,
+                                                   const double *__restrict__ sched)
 {
+    // omb = 1 - beta.  beta2 = 0.999 rounded to float is 0.999000013, and 1.f - that is 0.000999987: 1.3e-5 short of 0.001.  The
+    // entry points that know the betas as doubles take the difference in double and round once (what torch.optim.Adam does).
     if (hyper != nullptr) {      // every scalar of the step from device memory (a captured launch cannot carry new ones)
         lr = hyper[0];
         bc1 = hyper[1];
@@ -19,6 +22,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
         b1 = hyper[3];
         b2 = hyper[4];
         eps = hyper[5];
+        omb1 = 1.f - b1;
+        omb2 = 1.f - b2;
+        if (sched != nullptr) {  // the schedule's constants: {lr_init, lr_final, max_steps, beta1, beta2, eps} as doubles
+            omb1 = (float)(1.0 - sched[3]);
+            omb2 = (float)(1.0 - sched[4]);
+        }
     }
     const int64_t n4 = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -31,8 +40,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float gk = gv[k] * gscale;
-            mv[k] = b1 * mv[k] + (1.f - b1) * gk;
-            vv[k] = b2 * vv[k] + (1.f - b2) * gk * gk;
+            mv[k] = b1 * mv[k] + omb1 * gk;
+            vv[k] = b2 * vv[k] + omb2 * gk * gk;
             const float denom = sqrtf(vv[k]) * inv_sqrt_bc2 + eps;
             pv[k] -= step * (mv[k] / denom);
         }
@@ -44,8 +53,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
     const int64_t t = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n) {
         const float gk = g[t] * gscale;
-        const float mk = b1 * m[t] + (1.f - b1) * gk;
-        const float vk = b2 * v[t] + (1.f - b2) * gk * gk;
+        const float mk = b1 * m[t] + omb1 * gk;
+        const float vk = b2 * v[t] + omb2 * gk * gk;
         m[t] = mk;
         v[t] = vk;
         p[t] -= step * (mk / (sqrtf(vk) * inv_sqrt_bc2 + eps));
@@ -110,21 +119,45 @@ __global__ void occ_binarize_kernel(const float *__restrict__ occs, int64_t n, c
 
 }  // namespace
 
+namespace {
+
+int adam_launch(const char *who, float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float b1,
+                float b2, float eps, float bc1, float inv_sqrt_bc2, float grad_scale, const float *hyper, float omb1, float omb2,
+                const double *sched, lse_stream_t stream)
+{
+    LSE_REQUIRE(params && grads && exp_avg && exp_avg_sq, "%s: null pointer", who);
+    LSE_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
+                "%s: buffers must be 16-byte aligned", who);
+    const int64_t n4 = (n + 3) / 4;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n4 + 255) / 256, 2048));
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, lse::as_stream(stream), params, grads, exp_avg, exp_avg_sq,
+                       n, lr, b1, b2, eps, bc1, inv_sqrt_bc2, grad_scale, hyper, omb1, omb2, sched);
+    return lse::check_launch(who);
+}
+
+}  // namespace
+
 extern "C" int lse_adam_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
                              float beta1, float beta2, float eps, int32_t step, float grad_scale, lse_stream_t stream)
 {
     LSE_REQUIRE(n >= 0 && step >= 1, "lse_adam_step: need n >= 0 and step >= 1");
     if (n == 0) return LSE_OK;
-    LSE_REQUIRE(params && grads && exp_avg && exp_avg_sq, "lse_adam_step: null pointer");
-    LSE_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
-                "lse_adam_step: buffers must be 16-byte aligned");
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const int64_t n4 = (n + 3) / 4;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n4 + 255) / 256, 2048));
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, lse::as_stream(stream), params, grads, exp_avg, exp_avg_sq,
-                       n, lr, beta1, beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, (const float *)nullptr);
-    return lse::check_launch("lse_adam_step");
+    return adam_launch("lse_adam_step", params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, (float)bc1,
+                       (float)(1.0 / sqrt(bc2)), grad_scale, nullptr, 1.f - beta1, 1.f - beta2, nullptr, stream);
+}
+
+extern "C" int lse_adam_step_f64(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, double lr,
+                                 double beta1, double beta2, double eps, int32_t step, float grad_scale, lse_stream_t stream)
+{
+    LSE_REQUIRE(n >= 0 && step >= 1, "lse_adam_step_f64: need n >= 0 and step >= 1");
+    if (n == 0) return LSE_OK;
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    return adam_launch("lse_adam_step_f64", params, grads, exp_avg, exp_avg_sq, n, (float)lr, (float)beta1, (float)beta2, (float)eps,
+                       (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, nullptr, (float)(1.0 - beta1), (float)(1.0 - beta2), nullptr,
+                       stream);
 }
 
 extern "C" int lse_adam_step_dev(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,
@@ -132,14 +165,19 @@ extern "C" int lse_adam_step_dev(float *params, const float *grads, float *exp_a
 {
     LSE_REQUIRE(n >= 0, "lse_adam_step_dev: n < 0");
     if (n == 0) return LSE_OK;
-    LSE_REQUIRE(params && grads && exp_avg && exp_avg_sq && hyper, "lse_adam_step_dev: null pointer");
-    LSE_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
-                "lse_adam_step_dev: buffers must be 16-byte aligned");
-    const int64_t n4 = (n + 3) / 4;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n4 + 255) / 256, 2048));
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, lse::as_stream(stream), params, grads, exp_avg, exp_avg_sq,
-                       n, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, grad_scale, hyper);
-    return lse::check_launch("lse_adam_step_dev");
+    LSE_REQUIRE(hyper, "lse_adam_step_dev: null pointer");
+    return adam_launch("lse_adam_step_dev", params, grads, exp_avg, exp_avg_sq, n, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, grad_scale, hyper,
+                       0.f, 0.f, nullptr, stream);
+}
+
+extern "C" int lse_adam_step_dev_sched(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                       const float *hyper, const double *sched, float grad_scale, lse_stream_t stream)
+{
+    LSE_REQUIRE(n >= 0, "lse_adam_step_dev_sched: n < 0");
+    if (n == 0) return LSE_OK;
+    LSE_REQUIRE(hyper && sched, "lse_adam_step_dev_sched: null pointer");
+    return adam_launch("lse_adam_step_dev_sched", params, grads, exp_avg, exp_avg_sq, n, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, grad_scale,
+                       hyper, 0.f, 0.f, sched, stream);
 }
 
 extern "C" int lse_adam_schedule_dev(int64_t *step, float *hyper, const double *sched, lse_stream_t stream)

@@ -15,7 +15,7 @@ What varies from step to step enters through device memory at fixed addresses:
     that writes straight into the static inputs, driven by a step counter in device memory: nothing is copied;
   * the stratified jitter              -> ``torch.rand`` inside the graph (graph-safe Philox offsets), or a static input;
   * the learning rate / bias corrections -> derived ON THE DEVICE from a step counter the graph itself advances
-    (lse_adam_schedule_dev in front of lse_adam_step_dev): no per-step host -> device copy that a host running ahead could race;
+    (lse_adam_schedule_dev in front of lse_adam_step_dev_sched): no per-step host -> device copy that a host running ahead could race;
   * the occupancy grid and ``occs.mean()`` (the cap of the alpha threshold) -> refreshed in place, outside the graph, by
     ``LSENeRFModel.update_occupancy_grid`` between replays (lse_visibility_mask_cap reads the mean on the device).
 Everything else (step size, cone angle, shapes, capacities) is constant for a given model and batch composition.

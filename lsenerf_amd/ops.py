@@ -1388,17 +1388,26 @@ def loss_epilogue(desc_fields: tuple, col_rgb, col_gt, prev_rgb, next_rgb, evs_g
 # ----------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step: int, grad_scale: float = 1.0):
-    _lib.call("lse_adam_step", _f32(params, "params"), _f32(grads, "grads"), _f32(exp_avg, "exp_avg"),
+    # (the scalars go as doubles: 1 - beta2 taken from a float beta2 is 1.3e-5 off, and exp_avg_sq with it -- lse_hip.h)
+    _lib.call("lse_adam_step_f64", _f32(params, "params"), _f32(grads, "grads"), _f32(exp_avg, "exp_avg"),
               _f32(exp_avg_sq, "exp_avg_sq"), params.numel(), float(lr), float(beta1), float(beta2), float(eps),
               int(step), float(grad_scale), _stream())
 
 
 @torch.no_grad()
-def adam_step_dev(params, grads, exp_avg, exp_avg_sq, hyper, grad_scale: float = 1.0):
+def adam_step_dev(params, grads, exp_avg, exp_avg_sq, hyper, grad_scale: float = 1.0, sched=None):
     """Adam with every scalar of the step -- lr, 1 - beta1^t, 1 / sqrt(1 - beta2^t), beta1, beta2, eps -- in ``hyper`` (float32 [6]
-    on the device, written by ``adam_schedule_dev``)."""
-    _lib.call("lse_adam_step_dev", _f32(params, "params"), _f32(grads, "grads"), _f32(exp_avg, "exp_avg"),
-              _f32(exp_avg_sq, "exp_avg_sq"), params.numel(), _f32(hyper, "hyper"), float(grad_scale), _stream())
+    on the device, written by ``adam_schedule_dev``).  ``sched``: the float64 [6] constants ``adam_schedule_dev`` read; 1 - beta
+    is then taken from its double betas (lse_adam_step_dev_sched), as the bias corrections in ``hyper`` were."""
+    if sched is None:
+        _lib.call("lse_adam_step_dev", _f32(params, "params"), _f32(grads, "grads"), _f32(exp_avg, "exp_avg"),
+                  _f32(exp_avg_sq, "exp_avg_sq"), params.numel(), _f32(hyper, "hyper"), float(grad_scale), _stream())
+        return
+    if sched.numel() < 6:
+        raise ValueError("adam_step_dev: sched holds six doubles")
+    _lib.call("lse_adam_step_dev_sched", _f32(params, "params"), _f32(grads, "grads"), _f32(exp_avg, "exp_avg"),
+              _f32(exp_avg_sq, "exp_avg_sq"), params.numel(), _f32(hyper, "hyper"), _chk(sched, torch.float64, "sched"),
+              float(grad_scale), _stream())
 
 
 @torch.no_grad()

@@ -3,7 +3,7 @@
 All trainable tensors of a model are re-pointed into ONE contiguous fp32 buffer (``FlatParams``): their ``.data``
 and ``.grad`` become views, so that
   * the gradient of the whole model is one tensor -> one RCCL all-reduce per step over xGMI (lsenerf_amd.dist),
-  * Adam is one streaming HIP kernel over (p, g, m, v)  (lse_adam_step),
+  * Adam is one streaming HIP kernel over (p, g, m, v)  (lse_adam_step_f64),
   * zeroing gradients is one memset.
 Semantics are torch.optim.Adam's with the reference's hyper-parameters (lr 1e-2, eps 1e-15, exponential decay to
 1e-4 over 200k steps: R:lse_nerf/lse_config.py:29-33).
@@ -116,11 +116,11 @@ class FlatAdam:
         self._step_dev_expected = self.step_count
 
     def step_staged(self, grad_scale: float = 1.0) -> None:
-        """Device clock tick + the Adam update with the scalars it derived (lse_adam_schedule_dev, lse_adam_step_dev): capturable.
+        """Device clock tick + the Adam update with the scalars it derived (lse_adam_schedule_dev, lse_adam_step_dev_sched): capturable.
         Nothing step- or schedule-dependent is a launch argument: a captured pair follows ``prepare_step``'s device-side state."""
         step_dev, hyper = self._device_clock()
         ops.adam_schedule_dev(step_dev, hyper, self._sched_dev)
-        ops.adam_step_dev(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, hyper, grad_scale)
+        ops.adam_step_dev(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, hyper, grad_scale, sched=self._sched_dev)
 
     # -- resume (nerfstudio saves ``optimizers: {"fields": optimizer.state_dict()}``, R:lse_nerf/lse_trainer.py:85-122) ------
     def state_dict(self) -> dict:
