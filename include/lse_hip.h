@@ -390,6 +390,34 @@ int lse_eval_composite(const float *t_starts, const float *t_ends, const float *
                        const int64_t *packed_info, int32_t n_rays, int32_t flags, float background, float *workspace, float *out_rgb,
                        float *out_acc, float *out_depth, int64_t *out_nsamples, lse_stream_t stream);
 
+/* The same compositing walked in SEGMENTS of the ray, for early ray termination: between two segments the caller evaluates the field
+ * only on the rays that are still alive.  Ray sample k meets lane k mod 64 in lse_eval_composite; every segment but the last ends
+ * at a multiple of 64 samples, the lane accumulators are carried un-reduced, and the arithmetic is that kernel's operation by
+ * operation -- so a ray that composited its first m samples here has, bit for bit, the outputs lse_eval_composite gives for a
+ * packed_info count of m.  The library keeps nothing: the caller owns `state`.
+ *   lse_eval_segment_state_bytes: size of `state` for n_rays rays (1312 bytes per ray: 5 x 64 lane accumulators, the scan's carry,
+ *      the mid-point range, the composited count, the alive flag); the buffer is 16-byte aligned.
+ *   lse_eval_segment_begin: resets the state of every ray and writes the sample counts of segment 0,
+ *      seg_cnts[r] = min(ray_cnts[r], first_len).
+ *   lse_eval_composite_segment: continues every ray over the samples seg_packed [R,2] = (start, count) assigns it in the packed arrays
+ *      of THIS segment (t_starts / t_ends / sigmas / rgb [*, rgb_stride]; seg_packed counts are authoritative, so nerfstudio's fake
+ *      sample composites on segment 0).  ray_cnts [R]: the rays' full counts; seg_end: samples of a ray covered once this segment is
+ *      done (offset + length, a multiple of 64 unless next_len == 0).  A ray is finished when ray_cnts[r] <= seg_end or its carried
+ *      optical depth (f32, as lse_eval_composite carries it between 64-sample groups) is >= tau_stop; +inf finishes it, NaN never
+ *      does.  next_seg_cnts [R] (nullable when next_len == 0) = finished ? 0 : min(ray_cnts[r] - seg_end, next_len): the counts of
+ *      the next segment, ready for lse_pack_info_from_counts.  Of `flags` only LSE_EVAL_NAN_TO_NUM acts here.
+ *   lse_eval_composite_finish: the wave reductions and the epilogue of lse_eval_composite (background, clamp, depth clipped to the
+ *      mid-point range of the samples that were composited over the n_rays rays); out_nsamples = samples composited per ray.
+ *      Outputs may be row offsets into an image; workspace: 3 * n_rays floats. */
+int lse_eval_segment_state_bytes(int32_t n_rays, int64_t *h_bytes);
+int lse_eval_segment_begin(const int64_t *ray_cnts, int32_t n_rays, int64_t first_len, void *state, int64_t *seg_cnts,
+                           lse_stream_t stream);
+int lse_eval_composite_segment(const float *t_starts, const float *t_ends, const float *sigmas, const float *rgb, int32_t rgb_stride,
+                               const int64_t *seg_packed, const int64_t *ray_cnts, int32_t n_rays, int32_t flags, int64_t seg_end,
+                               int64_t next_len, float tau_stop, void *state, int64_t *next_seg_cnts, lse_stream_t stream);
+int lse_eval_composite_finish(const void *state, int32_t n_rays, int32_t flags, float background, float *workspace, float *out_rgb,
+                              float *out_acc, float *out_depth, int64_t *out_nsamples, lse_stream_t stream);
+
 /* ---- image metrics: SSIM and MSE of preds / target, contiguous f32 [B,C,H,W] with H, W >= 11 (else LSE_E_INVALID) -----------
  *      torchmetrics structural_similarity_index_measure(preds, target) with its defaults (R:lse_nerf/lsenerf.py:206, :512), restated
  *      from the published algorithm (parity unpinned): data_range R = max(max p - min p, max t - min t) on the device,

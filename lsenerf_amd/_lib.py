@@ -139,6 +139,10 @@ SIGNATURES = {
     "lse_volrend_bwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P],
     "lse_volrend_depth_fwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P, P],
     "lse_eval_composite": [P, P, P, P, I32, P, I32, I32, F32, P, P, P, P, P, P],
+    "lse_eval_segment_state_bytes": [I32, POINTER(c_int64)],
+    "lse_eval_segment_begin": [P, I32, I64, P, P, P],
+    "lse_eval_composite_segment": [P, P, P, P, I32, P, P, I32, I32, I64, I64, F32, P, P, P],
+    "lse_eval_composite_finish": [P, I32, I32, F32, P, P, P, P, P, P],
     "lse_image_metrics_workspace": [I32, I32, I32, I32, POINTER(c_int64)],
     "lse_image_metrics": [P, P, I32, I32, I32, I32, P, P, I64, P, P, P],
     "lse_render_weight_fwd": [P, P, P, P, I32, P, P, P, P],

@@ -219,6 +219,152 @@ __global__ __launch_bounds__(256) void eval_composite_kernel(const float *__rest
     }
 }
 
+// Early ray termination of the eval render (lse_eval_segment_begin / lse_eval_composite_segment / lse_eval_composite_finish): the
+// walk of eval_composite_kernel cut into segments of the ray, with the field evaluated between two segments only for the rays that
+// are still alive.  Sample k of a ray goes to lane k mod 64 there; every segment starts at a multiple of 64, so here the same lane
+// meets the same samples, and the body below is a COPY of that kernel's body (contraction off, the same explicit fmaf sites, the
+// exclusive prefix as the shifted inclusive one): compositing the first m samples of a ray in segments gives the bits
+// eval_composite_kernel gives for a ray of m samples.  That needs the lane accumulators carried as they are -- the wave reduction
+// happens once, in the finishing kernel, in eval_composite_kernel's order.  State of one ray (kSegStateFloats floats, 1312 bytes):
+//   [a * 64 + lane], a = 0..4   lane accumulators: r, g, b, weight, depth numerator
+//   [320] carry                 the optical depth in front of the next 64-sample group (the very value the scan carries)
+//   [321], [322]                smallest / largest interval mid-point composited so far (min / max are exact: reduced per segment)
+//   [323], [324] as int32       samples composited so far; alive (1 while the ray still takes part)
+constexpr int kSegStateFloats = 328;     // padded to a multiple of 4 floats: every ray's row is 16-byte aligned
+constexpr int kSegCarry = 320, kSegMidLo = 321, kSegMidHi = 322, kSegInts = 323;
+
+__global__ __launch_bounds__(256) void eval_segment_begin_kernel(const int64_t *__restrict__ ray_cnts, int n_rays, int64_t first_len,
+                                                                 float *__restrict__ state, int64_t *__restrict__ seg_cnts)
+{
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    float *st = state + (int64_t)ray * kSegStateFloats;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) st[a * 64 + lane] = 0.f;
+    if (lane == 0) {
+        st[kSegCarry] = 0.f;
+        st[kSegMidLo] = INFINITY;
+        st[kSegMidHi] = -INFINITY;
+        int32_t *si = reinterpret_cast<int32_t *>(st + kSegInts);
+        si[0] = 0;
+        si[1] = 1;
+        st[325] = 0.f; st[326] = 0.f; st[327] = 0.f;
+        const int64_t c = ray_cnts[ray];
+        seg_cnts[ray] = c < 0 ? 0 : (c < first_len ? c : first_len);
+    }
+}
+
+__global__ __launch_bounds__(256) void eval_composite_segment_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                                     const float *__restrict__ sigma, const float *__restrict__ rgb,
+                                                                     int rgb_stride, const int64_t *__restrict__ seg_packed,
+                                                                     const int64_t *__restrict__ ray_cnts, int n_rays, int flags,
+                                                                     int64_t seg_end, int64_t next_len, float tau_stop,
+                                                                     float *state, int64_t *__restrict__ next_seg_cnts)
+{
+#pragma clang fp contract(off)   // as in eval_composite_kernel
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    float *st = state + (int64_t)ray * kSegStateFloats;
+    int32_t *si = reinterpret_cast<int32_t *>(st + kSegInts);
+    // (the packed count is authoritative for what is composited: on segment 0 it may hold nerfstudio's fake sample of a ray
+    // whose own count is 0; a finished ray has 0 here and touches none of its accumulators)
+    const int64_t s0 = seg_packed[2 * ray], cnt = seg_packed[2 * ray + 1];
+    const bool fix_nan = (flags & LSE_EVAL_NAN_TO_NUM) != 0;
+    const bool alive = si[1] != 0;
+    float carry = st[kSegCarry];
+    if (cnt > 0) {
+        float ar = st[lane], ag = st[64 + lane], ab = st[128 + lane], aw = st[192 + lane], ad = st[256 + lane];
+        float mlo = st[kSegMidLo], mhi = st[kSegMidHi];
+        for (int64_t base = 0; base < cnt; base += 64) {
+            const int64_t i = s0 + base + lane;
+            const bool valid = base + lane < cnt;
+            float a = 0.f, b = 0.f, sg = 0.f;
+            if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
+            const float dt = b - a;
+            const float sd = sg * dt;
+            float incl = sd;
+            {
+                const float nb = __shfl_up(incl, 1, 64);
+                if (lane >= 1) incl = fmaf(sg, dt, nb);
+            }
+#pragma unroll
+            for (int off = 2; off < 64; off <<= 1) {
+                const float nb = __shfl_up(incl, off, 64);
+                if (lane >= off) incl = incl + nb;
+            }
+            float excl = __shfl_up(incl, 1, 64);     // shifted, not `incl - sd`: see volrend_fwd_kernel
+            if (lane == 0) excl = 0.f;
+            const float T = expf(-(excl + carry));
+            const float alpha = 1.f - expf(-sd);
+            const float w = valid ? T * alpha : 0.f;
+            if (valid) {
+                const float mid = (a + b) * 0.5f;
+                mlo = fminf(mlo, mid);
+                mhi = fmaxf(mhi, mid);
+                const float *c = rgb + i * rgb_stride;
+                float c0 = c[0], c1 = c[1], c2 = c[2];
+                if (fix_nan) { c0 = nan_to_num(c0); c1 = nan_to_num(c1); c2 = nan_to_num(c2); }
+                ar = fmaf(w, c0, ar);
+                ag = fmaf(w, c1, ag);
+                ab = fmaf(w, c2, ab);
+                aw = aw + w;
+                ad = fmaf(w, mid, ad);
+            }
+            carry = carry + __shfl(incl, 63, 64);
+        }
+        st[lane] = ar; st[64 + lane] = ag; st[128 + lane] = ab; st[192 + lane] = aw; st[256 + lane] = ad;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            mlo = fminf(mlo, __shfl_xor(mlo, off, 64));
+            mhi = fmaxf(mhi, __shfl_xor(mhi, off, 64));
+        }
+        if (lane == 0) {
+            st[kSegCarry] = carry;
+            st[kSegMidLo] = mlo;
+            st[kSegMidHi] = mhi;
+            si[0] += (int32_t)cnt;
+        }
+    }
+    if (lane == 0) {
+        // finished: no sample left, or the optical depth so far has reached tau_stop (+inf does; a NaN never compares true, so
+        // that ray is rendered in full)
+        const int64_t left = ray_cnts[ray] - seg_end;
+        const bool go = alive && left > 0 && !(carry >= tau_stop);
+        si[1] = go ? 1 : 0;
+        if (next_seg_cnts) next_seg_cnts[ray] = go ? (left < next_len ? left : next_len) : 0;
+    }
+}
+
+// The end of eval_composite_kernel for a segmented ray: the wave reductions in that kernel's order, then its lane-0 epilogue.
+__global__ __launch_bounds__(256) void eval_segment_finish_kernel(const float *__restrict__ state, int n_rays, int flags,
+                                                                  float background, float *__restrict__ mid_range,
+                                                                  float *__restrict__ num, float *__restrict__ out_rgb,
+                                                                  float *__restrict__ out_acc, int64_t *__restrict__ out_nsamples)
+{
+#pragma clang fp contract(off)
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const float *st = state + (int64_t)ray * kSegStateFloats;
+    float ar = st[lane], ag = st[64 + lane], ab = st[128 + lane], aw = st[192 + lane], ad = st[256 + lane];
+    ar = lse::wave_sum(ar); ag = lse::wave_sum(ag); ab = lse::wave_sum(ab);
+    aw = lse::wave_sum(aw); ad = lse::wave_sum(ad);
+    if (lane == 0) {
+        if (flags & LSE_EVAL_BACKGROUND) {     // rgb + bg * (1 - acc)
+            const float rest = background * (1.f - aw);
+            ar = ar + rest; ag = ag + rest; ab = ab + rest;
+        }
+        if (flags & LSE_EVAL_CLAMP) { ar = clamp01(ar); ag = clamp01(ag); ab = clamp01(ab); }
+        out_rgb[ray * 3 + 0] = ar; out_rgb[ray * 3 + 1] = ag; out_rgb[ray * 3 + 2] = ab;
+        out_acc[ray] = aw;
+        num[ray] = ad;
+        mid_range[2 * ray] = st[kSegMidLo]; mid_range[2 * ray + 1] = st[kSegMidHi];
+        out_nsamples[ray] = reinterpret_cast<const int32_t *>(st + kSegInts)[0];
+    }
+}
+
 __global__ __launch_bounds__(256) void volrend_bwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                           const float *__restrict__ sigma, const float *__restrict__ rgb,
                                                           int rgb_stride, const int64_t *__restrict__ packed, int n_rays,
@@ -463,6 +609,68 @@ extern "C" int lse_eval_composite(const float *t_starts, const float *t_ends, co
     hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(1024), 0, st, (const float *)num, (const float *)out_acc,
                        (const float *)mid_range, n_rays, out_depth, (float *)nullptr);
     return lse::check_launch("lse_eval_composite");
+}
+
+extern "C" int lse_eval_segment_state_bytes(int32_t n_rays, int64_t *h_bytes)
+{
+    LSE_REQUIRE(n_rays >= 0 && h_bytes, "lse_eval_segment_state_bytes: n_rays < 0 or null pointer");
+    *h_bytes = (int64_t)n_rays * kSegStateFloats * (int64_t)sizeof(float);
+    return LSE_OK;
+}
+
+extern "C" int lse_eval_segment_begin(const int64_t *ray_cnts, int32_t n_rays, int64_t first_len, void *state, int64_t *seg_cnts,
+                                      lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_eval_segment_begin: n_rays < 0");
+    LSE_REQUIRE(first_len >= 1, "lse_eval_segment_begin: first_len < 1");
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(ray_cnts && state && seg_cnts, "lse_eval_segment_begin: null pointer");
+    LSE_REQUIRE(((uintptr_t)state & 15) == 0, "lse_eval_segment_begin: state is not 16-byte aligned");
+    hipLaunchKernelGGL(eval_segment_begin_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), ray_cnts, n_rays,
+                       first_len, static_cast<float *>(state), seg_cnts);
+    return lse::check_launch("lse_eval_segment_begin");
+}
+
+extern "C" int lse_eval_composite_segment(const float *t_starts, const float *t_ends, const float *sigmas, const float *rgb,
+                                          int32_t rgb_stride, const int64_t *seg_packed, const int64_t *ray_cnts, int32_t n_rays,
+                                          int32_t flags, int64_t seg_end, int64_t next_len, float tau_stop, void *state,
+                                          int64_t *next_seg_cnts, lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_eval_composite_segment: n_rays < 0");
+    LSE_REQUIRE(seg_end >= 1 && next_len >= 0, "lse_eval_composite_segment: seg_end < 1 or next_len < 0");
+    LSE_REQUIRE(next_len == 0 || (seg_end & 63) == 0,
+                "lse_eval_composite_segment: seg_end %lld is not a multiple of 64 and a segment follows (next_len %lld)",
+                (long long)seg_end, (long long)next_len);
+    LSE_REQUIRE((flags & ~(LSE_EVAL_NAN_TO_NUM | LSE_EVAL_BACKGROUND | LSE_EVAL_CLAMP)) == 0,
+                "lse_eval_composite_segment: unknown flags %d", flags);
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(t_starts && t_ends && sigmas && rgb && seg_packed && ray_cnts && state, "lse_eval_composite_segment: null pointer");
+    LSE_REQUIRE(next_len == 0 || next_seg_cnts, "lse_eval_composite_segment: null pointer (next_seg_cnts with a segment to follow)");
+    LSE_REQUIRE(rgb_stride >= 3, "lse_eval_composite_segment: rgb_stride < 3");
+    LSE_REQUIRE(((uintptr_t)state & 15) == 0, "lse_eval_composite_segment: state is not 16-byte aligned");
+    hipLaunchKernelGGL(eval_composite_segment_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), t_starts, t_ends,
+                       sigmas, rgb, rgb_stride, seg_packed, ray_cnts, n_rays, flags, seg_end, next_len, tau_stop,
+                       static_cast<float *>(state), next_seg_cnts);
+    return lse::check_launch("lse_eval_composite_segment");
+}
+
+extern "C" int lse_eval_composite_finish(const void *state, int32_t n_rays, int32_t flags, float background, float *workspace,
+                                         float *out_rgb, float *out_acc, float *out_depth, int64_t *out_nsamples,
+                                         lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_eval_composite_finish: n_rays < 0");
+    LSE_REQUIRE((flags & ~(LSE_EVAL_NAN_TO_NUM | LSE_EVAL_BACKGROUND | LSE_EVAL_CLAMP)) == 0,
+                "lse_eval_composite_finish: unknown flags %d", flags);
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(state && workspace && out_rgb && out_acc && out_depth && out_nsamples, "lse_eval_composite_finish: null pointer");
+    LSE_REQUIRE(((uintptr_t)state & 15) == 0, "lse_eval_composite_finish: state is not 16-byte aligned");
+    hipStream_t st = lse::as_stream(stream);
+    float *mid_range = workspace, *num = workspace + 2 * (int64_t)n_rays;
+    hipLaunchKernelGGL(eval_segment_finish_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, st, static_cast<const float *>(state),
+                       n_rays, flags, background, mid_range, num, out_rgb, out_acc, out_nsamples);
+    hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(1024), 0, st, (const float *)num, (const float *)out_acc,
+                       (const float *)mid_range, n_rays, out_depth, (float *)nullptr);
+    return lse::check_launch("lse_eval_composite_finish");
 }
 
 extern "C" int lse_render_weight_fwd(const float *t_starts, const float *t_ends, const float *sigmas,

@@ -5,14 +5,16 @@
   the count-free route instead: deferred sampling (no sample count read back), ``density_rgb_packed`` with the
   device-side count, and ``lse_eval_composite`` writing the chunk's rows of the image buffers directly -- no host synchronisation
   inside the loop, no per-sample ``RaySamples`` gathers, no autograd Functions.  Its values are those of the ``forward`` loop bit for
-  bit (the mapper keys, formed once over the whole image, to GEMM rounding).
+  bit (the mapper keys, formed once over the whole image, to GEMM rounding).  With ``config.eval_early_stop_eps > 0`` the count-free
+  route composites each chunk in segments of the ray and stops evaluating the field on rays that have become opaque
+  (``_render_early_stop``; opt-in, still without a host synchronisation inside the loops).
 * ``image_metrics_and_images`` -- R:lse_nerf/lsenerf.py:477-530 restated: psnr / ssim from one ``lse_image_metrics`` launch, lpips
   when torchmetrics is importable, and the image dictionary (no "overlay": it needs OpenCV's Canny).
 * ``make_lpips`` -- torchmetrics' ``LearnedPerceptualImagePatchSimilarity(normalize=True)``, or a callable that names what is missing.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -99,6 +101,99 @@ def _render_count_free(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
     return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
 
 
+def segment_schedule(cap: int, base: int) -> List[Tuple[int, int]]:
+    """The segments ``[(offset, length), ...]`` the early-stop route cuts a ray of at most ``cap`` samples into: lengths ``base``,
+    ``base``, ``2 base``, ``4 base``, ... with the last one cut so that they sum to ``cap``.  ``base`` is a positive multiple of 64,
+    so every offset is one too: sample k of a ray meets lane k mod 64 of the compositing kernels whichever segment it falls into.
+    Short segments first (most rays of a trained scene are opaque within a few dozen samples), doubling ones behind them (the
+    number of segments, each a fixed set of launches, grows with log cap)."""
+    cap, base = int(cap), int(base)
+    if cap < 1:
+        raise ValueError(f"segment_schedule: cap must be positive, got {cap}")
+    if base <= 0 or base % 64 != 0:
+        raise ValueError(f"segment_schedule: the base segment length must be a positive multiple of 64, got {base}")
+    out, off, length = [], 0, base
+    while off < cap:
+        out.append((off, min(length, cap - off)))
+        off += out[-1][1]
+        if len(out) >= 2:
+            length *= 2
+    return out
+
+
+def early_stop_settings(config) -> Tuple[float, int]:
+    """(eps, base segment length) of ``config``, validated: ValueError unless 0 <= eps < 1 and the length is a positive multiple of
+    64.  Pure host code: nothing touches a device."""
+    eps, base = float(config.eval_early_stop_eps), config.eval_segment_samples
+    if not (0.0 <= eps < 1.0):          # (a NaN fails this too)
+        raise ValueError(f"eval_early_stop_eps must satisfy 0 <= eps < 1, got {config.eval_early_stop_eps}")
+    if isinstance(base, bool) or int(base) != base or int(base) <= 0 or int(base) % 64 != 0:
+        raise ValueError(f"eval_segment_samples must be a positive multiple of 64, got {config.eval_segment_samples}")
+    return eps, int(base)
+
+
+def _render_early_stop(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
+    """The count-free route with early ray termination: a chunk is marched as in ``_render_count_free`` but its samples stay in the
+    marcher's per-ray slots; per segment of ``segment_schedule`` the live rays' samples are packed, the field evaluates them and
+    ``lse_eval_composite_segment`` continues every ray from its saved state, finishing those whose optical depth has reached
+    -ln(eps).  The segment count is known on the host (from the capacity); which rays are alive never is: a segment without a live
+    ray is the same launches over a device-side count of 0."""
+    cfg, fld = model.config, model.field
+    eps, base = early_stop_settings(cfg)
+    tau_stop = ops.eval_tau_stop(eps)
+    R = len(rb)
+    n = min(chunk, R)
+    dev = rb.origins.device
+    cap = model.occupancy_grid._cap_per_ray(cfg.near_plane, cfg.far_plane, cfg.render_step_size, cfg.cone_angle)
+    sched = segment_schedule(cap, base)
+    longest = max(length for _, length in sched)
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    acc = torch.empty(R, dtype=torch.float32, device=dev)
+    depth = torch.empty(R, dtype=torch.float32, device=dev)
+    nsamples = torch.empty(R, dtype=torch.int64, device=dev)
+    ws = torch.empty(3 * n, dtype=torch.float32, device=dev)
+    # per image, sized by the longest segment: the packed sample arrays, the per-ray state and the segment bookkeeping
+    state = torch.empty(ops.eval_segment_state_bytes(n), dtype=torch.uint8, device=dev)
+    seg_cnts = torch.empty(n, dtype=torch.int64, device=dev)
+    seg_packed = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    n_dev = torch.empty(1, dtype=torch.int64, device=dev)
+    ri_buf = torch.empty(n * longest, dtype=torch.int32, device=dev)
+    ts_buf = torch.empty(n * longest, dtype=torch.float32, device=dev)
+    te_buf = torch.empty(n * longest, dtype=torch.float32, device=dev)
+    linear = isinstance(model.renderer_rgb, LinearRenderer)
+    bg = cfg.background_color
+    background = None if bg in ("random", "last_sample") else {"black": 0.0, "white": 1.0}[bg]
+    fld._prepass = None
+    for lo in range(0, R, chunk):
+        hi = min(R, lo + chunk)
+        m = hi - lo
+        part = _slice(rb, lo, hi)
+        cnts, ts_slots, te_slots, cap_marched = model.sampler.march_slots(
+            part, near_plane=cfg.near_plane, far_plane=cfg.far_plane, render_step_size=cfg.render_step_size,
+            cone_angle=cfg.cone_angle)
+        assert cap_marched == cap
+        rays_o, rays_d = part.origins.contiguous(), part.directions.contiguous()
+        table, eidx = fld._eval_emb(m, dev) if fld.embedding_appearance is not None else (None, None)
+        packed = seg_packed[:m]
+        ops.eval_segment_begin(cnts, sched[0][1], state, seg_cnts[:m])
+        for k, (off, length) in enumerate(sched):
+            ops.pack_info_from_counts(seg_cnts[:m], out=(packed, n_dev))
+            C = m * length
+            ri, ts, te = ri_buf[:C], ts_buf[:C], te_buf[:C]
+            ops.compact_ray_slots(ts_slots, te_slots, cap, packed, ri, ts, te, slot_offset=off)
+            if k == 0:           # nerfstudio's fake sample belongs to the chunk: a chunk without any sample gets it here
+                ops.fake_sample_if_empty(packed, n_dev, ri, ts, te)
+            sigma, _, _, head = fld.density_rgb_packed(rays_o, rays_d, ri, ts, te, packed, eidx, table, n_dev)
+            next_len = sched[k + 1][1] if k + 1 < len(sched) else 0
+            ops.eval_composite_segment(ts, te, sigma, head, packed, cnts, off + length, next_len, tau_stop, state,
+                                       seg_cnts[:m] if next_len else None, nan_to_num=not linear)
+        ops.eval_composite_finish(state, rgb[lo:hi], acc[lo:hi], depth[lo:hi], nsamples[lo:hi], background=background,
+                                  clamp=not linear, workspace=ws)
+    model.occupancy_grid.check_deferred_overflow()      # the one read-back, as on the full route
+    raw = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": nsamples}
+    return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
+
+
 @torch.no_grad()
 def render_flat(model, rb: RayBundle) -> Dict[str, Tensor]:
     """Outputs ``[R, ...]`` for the ``[R, ...]`` bundle ``rb``, chunked by ``config.eval_num_rays_per_chunk`` on every route (the
@@ -106,9 +201,12 @@ def render_flat(model, rb: RayBundle) -> Dict[str, Tensor]:
     chunk = int(model.config.eval_num_rays_per_chunk)
     if chunk <= 0:
         raise ValueError("eval_num_rays_per_chunk must be positive")
+    eps, _ = early_stop_settings(model.config)
     if len(rb) == 0:
         raise ValueError("empty ray bundle")
     if uses_count_free_route(model, len(rb)):
+        if eps > 0.0:
+            return _render_early_stop(model, rb, chunk)
         return _render_count_free(model, rb, chunk)
     return _render_loop(model, rb, chunk)
 

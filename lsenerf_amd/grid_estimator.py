@@ -250,6 +250,24 @@ class LSEOccGridEstimator(nn.Module):
             fma_setup=self.traverse_fma)
         return Premarched(*res, self.grid_version, rays_o.shape[0])
 
+    @torch.no_grad()
+    def march_slots(self, rays_o: Tensor, rays_d: Tensor, near_plane: float = 0.0, far_plane: float = 1e10,
+                    t_min: Optional[Tensor] = None, t_max: Optional[Tensor] = None, render_step_size: float = 1e-3,
+                    stratified: bool = False, cone_angle: float = 0.0, jitter: Optional[Tensor] = None):
+        """``march_deferred`` without the packing: the same planes, the same marcher call, the same capacity and overflow
+        accumulator.  Returns (cnts int64 [R], t_start_slots [R * cap], t_end_slots [R * cap], cap): ray r's samples are the first
+        cnts[r] entries of its row of ``cap`` slots (the early-stop eval route packs them a segment at a time)."""
+        u = None
+        if stratified:
+            u = jitter if jitter is not None else torch.rand(rays_o.shape[0], dtype=torch.float32, device=rays_o.device)
+        near_planes, far_planes = ops.ray_planes(rays_o.shape[0], rays_o.device, near_plane, far_plane, t_min, t_max, u,
+                                                 render_step_size)
+        cap = self._cap_per_ray(near_plane, far_plane, render_step_size, cone_angle)
+        cnts, ts_slots, te_slots, _ = ops.traverse_grids_slots_deferred(
+            rays_o.contiguous(), rays_d.contiguous(), self._binaries_u8(), self.aabbs, near_planes, far_planes,
+            render_step_size, cone_angle, cap, overflow=self._overflow_flag(), fma_setup=self.traverse_fma)
+        return cnts, ts_slots, te_slots, cap
+
     def _sampling_deferred(self, rays_o, rays_d, sigma_fn, alpha_fn, near_plane, far_plane, t_min, t_max, render_step_size,
                            early_stop_eps, alpha_thre, stratified, cone_angle, jitter, premarched=None):
         if premarched is None:

@@ -62,6 +62,22 @@ class LSENeRFModelConfig:
     hidden_dim_color: int = 64
     # --- refresh the occupancy grid through occ_refresh.DeviceGridRefresher: no host synchronisation, replayable as a HIP graph
     device_grid_refresh: bool = False
+    # --- early ray termination of the whole-image eval render (evaluation._render_early_stop).  0 = off: every route
+    # and output is what it is without these two fields.  With 0 < eps < 1 a chunk of the count-free eval route is composited in
+    # segments of the ray and a ray whose transmittance has dropped to eps or below at the end of a segment (optical depth >=
+    # float32(-ln eps)) is not evaluated any further: its outputs are those of the full render for a ray cut at that segment
+    # boundary, bit for bit, "num_samples_per_ray" is the number of samples composited, and the weight left behind is below eps.
+    # Ignored -- the full ``forward`` loop runs, as with 0 -- wherever the count-free route is not available: training mode, a field
+    # other than LSEField, the small-grid base MLP, or a chunk capacity above ``deferred_max_slots``.  Checked at render time
+    # (ValueError unless 0 <= eps < 1).  Measured on one MI355X (tools/bench_eval_early_stop.py, 640 x 480, eps 1e-4):
+    # with opaque surfaces and chunks of 32768 rays 22.6 ms per image against 38.9 ms; at the default chunk of 3512 rays it LOSES,
+    # 72 ms against 43.5 ms, whether 26 % or all of the samples are evaluated (five segments per chunk are five times the launches:
+    # what is paid there is issuing them), and on a field without opaque surfaces it costs 3 % at chunk 32768.  Switch it on
+    # together with a large ``eval_num_rays_per_chunk``.
+    eval_early_stop_eps: float = 0.0
+    # base segment length S, a positive multiple of 64 (checked at render time): the segments are S, S, 2S, 4S, ... samples long
+    # (evaluation.segment_schedule), each a fixed set of launches whether or not a ray is still alive.
+    eval_segment_samples: int = 128
 
     def __post_init__(self):   # R:lse_nerf/lsenerf.py:86-99
         if self.evs_mapping_method is None or str(self.evs_mapping_method).lower() == "none":
@@ -277,6 +293,21 @@ class VolumetricSampler(nn.Module):
             far_plane=1e10 if far_plane is None else far_plane, t_min=t_min, t_max=t_max, render_step_size=render_step_size,
             stratified=self.training, cone_angle=cone_angle, jitter=jitter, out=out)
 
+    def march_slots(self, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0, far_plane=None,
+                    cone_angle: float = 0.0, jitter: Optional[Tensor] = None):
+        """The marcher of ``sample_packed`` with the samples left in their per-ray slots (LSEOccGridEstimator.march_slots): (cnts,
+        t_start_slots, t_end_slots, cap).  No visibility pre-pass and no fake sample: the early-stop eval route, which packs the
+        slots a segment at a time, runs in eval mode (no pre-pass there) and inserts the fake sample into its first segment."""
+        t_min = ray_bundle.nears.contiguous().reshape(-1) if ray_bundle.nears is not None else None
+        t_max = ray_bundle.fars.contiguous().reshape(-1) if ray_bundle.fars is not None else None
+        res = self.occupancy_grid.march_slots(
+            ray_bundle.origins.detach().contiguous(), ray_bundle.directions.detach().contiguous(), near_plane=near_plane,
+            far_plane=1e10 if far_plane is None else far_plane, t_min=t_min, t_max=t_max, render_step_size=render_step_size,
+            stratified=self.training, cone_angle=cone_angle, jitter=jitter)
+        if self.occupancy_grid.after_march_hook is not None:
+            self.occupancy_grid.after_march_hook()
+        return res
+
     def sample_packed(self, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0, far_plane=None,
                       alpha_thre: float = 0.01, cone_angle: float = 0.0, jitter: Optional[Tensor] = None, premarched=None):
         """The sampler call of ``forward`` for the packed fast path, WITHOUT reading a sample count back to the host and without
@@ -488,7 +519,9 @@ class LSENeRFModel(nn.Module):
         "num_samples_per_ray" and the keys ``route_outputs`` adds in eval mode.  In eval mode with ``LSEField`` the chunks take the
         count-free route (no host synchronisation until one overflow check after the last chunk; ``lse_eval_composite`` writes the
         image rows); otherwise -- training mode, another field, a capacity above ``deferred_max_slots`` -- ``forward`` runs per
-        chunk as in nerfstudio.  Both routes give the same values (lsenerf_amd.evaluation)."""
+        chunk as in nerfstudio.  Both routes give the same values (lsenerf_amd.evaluation).  ``config.eval_early_stop_eps > 0``
+        adds early ray termination to the count-free route (see the config field): "num_samples_per_ray" then counts the samples
+        composited."""
         return evaluation.render_ray_bundle(self, camera_ray_bundle)
 
     @torch.no_grad()

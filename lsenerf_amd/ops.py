@@ -259,6 +259,49 @@ def traverse_grids_deferred(rays_o, rays_d, binaries, aabbs, near_planes, far_pl
 
 
 @torch.no_grad()
+def traverse_grids_slots_deferred(rays_o, rays_d, binaries, aabbs, near_planes, far_planes, step_size: float, cone_angle: float,
+                                  cap: int, overflow=None, fma_setup: bool = False):
+    """The marcher half of ``traverse_grids_deferred``: the same ``lse_traverse_grids_slots`` call, nothing packed.  Returns
+    (cnts int64 [R], t_start_slots [R * cap], t_end_slots [R * cap], overflow int32 [1]): ray r's samples are the first cnts[r]
+    entries of its slot row [r * cap, (r + 1) * cap); ``overflow`` is the sticky accumulator described there.
+    ``compact_ray_slots`` packs any window of the rows."""
+    R = rays_o.shape[0]
+    L, rx, ry, rz = binaries.shape
+    dev = rays_o.device
+    C = R * cap
+    if not (0 < cap and C <= MAX_SLOT_ELEMS):
+        raise _lib.LseHipError(f"deferred sampling: {R} rays x {cap} slots exceed the slot budget ({MAX_SLOT_ELEMS})")
+    if overflow is None:
+        overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    flag = _chk(overflow, torch.int32, "overflow")
+    cnts = torch.empty(R, dtype=torch.int64, device=dev)
+    ts_slots = torch.empty(C, dtype=torch.float32, device=dev)
+    te_slots = torch.empty(C, dtype=torch.float32, device=dev)
+    _lib.call("lse_traverse_grids_slots", _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), R, _chk(binaries, torch.uint8, "binaries"),
+              _f32(aabbs, "aabbs"), L, rx, ry, rz, _f32(near_planes, "near_planes"), _f32(far_planes, "far_planes"),
+              float(step_size), float(cone_angle), cap, ctypes.c_void_p(cnts.data_ptr()), ctypes.c_void_p(ts_slots.data_ptr()),
+              ctypes.c_void_p(te_slots.data_ptr()), flag, _lib.LSE_TRAVERSE_FMA_SETUP if fma_setup else 0, _stream())
+    return cnts, ts_slots, te_slots, overflow
+
+
+@torch.no_grad()
+def compact_ray_slots(t_start_slots, t_end_slots, cap: int, packed_info, ray_indices, t_starts, t_ends, slot_offset: int = 0):
+    """``lse_compact_ray_slots``: ray r's ``packed_info[r, 1]`` samples, taken from its slot row starting at entry ``slot_offset``,
+    go to ``packed_info[r, 0]`` of ``ray_indices`` / ``t_starts`` / ``t_ends`` (written in place; their extent must cover the
+    packed total).  ``slot_offset + packed_info[r, 1] <= cap`` is the caller's to hold."""
+    R = packed_info.shape[0]
+    slot_offset = int(slot_offset)
+    if not (0 <= slot_offset < cap) or t_start_slots.numel() < R * cap or t_end_slots.numel() < R * cap:
+        raise ValueError(f"compact_ray_slots: slot_offset {slot_offset} outside [0, {cap}) or slot arrays shorter than {R} x {cap}")
+    if R == 0:
+        return
+    src_s, src_e = _f32(t_start_slots, "t_start_slots"), _f32(t_end_slots, "t_end_slots")
+    _lib.call("lse_compact_ray_slots", ctypes.c_void_p(src_s.value + 4 * slot_offset),
+              ctypes.c_void_p(src_e.value + 4 * slot_offset), cap, _chk(packed_info, torch.int64, "packed_info"), R,
+              _chk(ray_indices, torch.int32, "ray_indices"), _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _stream())
+
+
+@torch.no_grad()
 def fake_sample_if_empty(packed_info, n_dev, ray_indices, t_starts, t_ends, features=None):
     """nerfstudio's single fake sample (ray 0, t = 1) when the device-side count is 0 (lse_fake_sample_if_empty); in place.
     ``features = (x01 [C,3], selector [C], y [L,C,F])``: the parked pre-pass features of these very buffers -- slot 0 is zeroed
@@ -326,10 +369,17 @@ def ray_planes(n_rays: int, device, near_plane: float, far_plane: float, t_min=N
 
 
 @torch.no_grad()
-def pack_info_from_counts(cnts: torch.Tensor):
+def pack_info_from_counts(cnts: torch.Tensor, out=None):
+    """``out``: (packed_info int64 [R, 2], total int64 [1]) to write into instead of allocating."""
     R = cnts.shape[0]
-    packed = torch.empty((R, 2), dtype=torch.int64, device=cnts.device)
-    total = torch.empty(1, dtype=torch.int64, device=cnts.device)       # written (not accumulated) by the kernel, also for R == 0
+    if out is not None:
+        packed, total = out
+        if packed.shape != (R, 2) or total.shape != (1,):
+            raise ValueError("pack_info_from_counts: out = (packed_info [R, 2], total [1]) expected")
+        _chk(packed, torch.int64, "out.packed_info"), _chk(total, torch.int64, "out.total")
+    else:
+        packed = torch.empty((R, 2), dtype=torch.int64, device=cnts.device)
+        total = torch.empty(1, dtype=torch.int64, device=cnts.device)   # written (not accumulated) by the kernel, also for R == 0
     _lib.call("lse_pack_info_from_counts", _chk(cnts, torch.int64, "cnts"), R, ctypes.c_void_p(packed.data_ptr()),
               ctypes.c_void_p(total.data_ptr()), _stream())
     return packed, total
@@ -1132,6 +1182,80 @@ def eval_composite(t_starts, t_ends, sigmas, rgb, packed_info, out_rgb, out_acc,
         | (_lib.LSE_EVAL_CLAMP if clamp else 0)
     _lib.call("lse_eval_composite", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(sigmas, "sigmas"), _rgb_ptr(rgb),
               rgb.stride(0), _chk(packed_info, torch.int64, "packed_info"), n, flags,
+              float(background) if background is not None else 0.0, _f32(workspace, "workspace"), _f32(out_rgb, "out_rgb"),
+              _f32(out_acc, "out_acc"), _f32(out_depth, "out_depth"), _chk(out_nsamples, torch.int64, "out_nsamples"), _stream())
+
+
+def _eval_flags(nan_to_num: bool, background: Optional[float], clamp: bool) -> int:
+    return (_lib.LSE_EVAL_NAN_TO_NUM if nan_to_num else 0) | (_lib.LSE_EVAL_BACKGROUND if background is not None else 0) \
+        | (_lib.LSE_EVAL_CLAMP if clamp else 0)
+
+
+def eval_tau_stop(eps: float) -> float:
+    """The optical depth at which the early-stop eval route finishes a ray: float32(-ln(eps)), the logarithm taken in double."""
+    import math
+    import numpy as np
+    if not (0.0 < eps < 1.0):
+        raise ValueError(f"eval_tau_stop: eps must lie in (0, 1), got {eps}")
+    return float(np.float32(-math.log(float(eps))))
+
+
+def eval_segment_state_bytes(n_rays: int) -> int:
+    """Bytes of the per-ray compositing state the three calls below share (lse_eval_segment_state_bytes)."""
+    v = ctypes.c_int64(0)
+    _lib.call("lse_eval_segment_state_bytes", int(n_rays), ctypes.byref(v))
+    return int(v.value)
+
+
+def _segment_state_ptr(state: torch.Tensor, n_rays: int):
+    if not state.is_cuda or not state.is_contiguous() or state.numel() * state.element_size() < eval_segment_state_bytes(n_rays):
+        raise ValueError(f"segment state: a contiguous GPU buffer of at least {eval_segment_state_bytes(n_rays)} bytes expected")
+    return ctypes.c_void_p(state.data_ptr())
+
+
+@torch.no_grad()
+def eval_segment_begin(ray_cnts, first_len: int, state, seg_cnts):
+    """Start of a segmented eval compositing (lse_eval_segment_begin): resets ``state`` (a buffer of ``eval_segment_state_bytes``)
+    for the ``ray_cnts.shape[0]`` rays and writes segment 0's counts ``seg_cnts[r] = min(ray_cnts[r], first_len)``."""
+    n = ray_cnts.shape[0]
+    if seg_cnts.shape != (n,):
+        raise ValueError("eval_segment_begin: seg_cnts [n] expected")
+    st = _segment_state_ptr(state, n)
+    _lib.call("lse_eval_segment_begin", _chk(ray_cnts, torch.int64, "ray_cnts"), n, int(first_len), st,
+              _chk(seg_cnts, torch.int64, "seg_cnts"), _stream())
+
+
+@torch.no_grad()
+def eval_composite_segment(t_starts, t_ends, sigmas, rgb, seg_packed, ray_cnts, seg_end: int, next_len: int, tau_stop: float, state,
+                           next_seg_cnts, nan_to_num: bool):
+    """One segment of the segmented eval compositing (lse_eval_composite_segment): every ray continues from ``state`` over the
+    ``seg_packed`` samples of this segment's packed arrays; a ray with no sample beyond ``seg_end`` or a carried optical depth
+    >= ``tau_stop`` is finished.  ``next_seg_cnts`` receives the next segment's counts (``next_len == 0``: last segment, may be
+    None)."""
+    n = seg_packed.shape[0]
+    if ray_cnts.shape != (n,) or (next_seg_cnts is not None and next_seg_cnts.shape != (n,)):
+        raise ValueError("eval_composite_segment: ray_cnts / next_seg_cnts [n] expected")
+    _lib.call("lse_eval_composite_segment", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(sigmas, "sigmas"), _rgb_ptr(rgb),
+              rgb.stride(0), _chk(seg_packed, torch.int64, "seg_packed"), _chk(ray_cnts, torch.int64, "ray_cnts"), n,
+              _eval_flags(nan_to_num, None, False), int(seg_end), int(next_len), float(tau_stop), _segment_state_ptr(state, n),
+              _chk(next_seg_cnts, torch.int64, "next_seg_cnts", allow_none=True), _stream())
+
+
+@torch.no_grad()
+def eval_composite_finish(state, out_rgb, out_acc, out_depth, out_nsamples, background: Optional[float], clamp: bool,
+                          workspace: Optional[torch.Tensor] = None):
+    """End of the segmented eval compositing (lse_eval_composite_finish): ``eval_composite``'s reductions and epilogue over the state;
+    ``out_nsamples`` = samples composited per ray.  Outputs and ``workspace`` as in ``eval_composite``."""
+    n = out_acc.shape[0]
+    if n == 0:
+        return
+    if out_rgb.shape != (n, 3) or out_depth.shape != (n,) or out_nsamples.shape != (n,):
+        raise ValueError("eval_composite_finish: out_rgb [n,3], out_acc / out_depth / out_nsamples [n] expected")
+    if workspace is None:
+        workspace = torch.empty(3 * n, dtype=torch.float32, device=out_acc.device)
+    elif workspace.numel() < 3 * n:
+        raise ValueError(f"eval_composite_finish: workspace of {workspace.numel()} floats, {3 * n} needed")
+    _lib.call("lse_eval_composite_finish", _segment_state_ptr(state, n), n, _eval_flags(False, background, clamp),
               float(background) if background is not None else 0.0, _f32(workspace, "workspace"), _f32(out_rgb, "out_rgb"),
               _f32(out_acc, "out_acc"), _f32(out_depth, "out_depth"), _chk(out_nsamples, torch.int64, "out_nsamples"), _stream())
 
