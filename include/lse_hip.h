@@ -429,6 +429,30 @@ int lse_image_metrics_workspace(int32_t B, int32_t C, int32_t H, int32_t W, int6
 int lse_image_metrics(const float *preds, const float *target, int32_t B, int32_t C, int32_t H, int32_t W, const float *h_window,
                       void *workspace, int64_t workspace_bytes, float *out_ssim, float *out_mse, lse_stream_t stream);
 
+/* ---- eval images: a resident ground truth and a rendered image -> the planes lse_image_metrics takes ----------------------
+ *   lse_eval_image_prep: one launch per image.  gt [H, W, 3] of gt_type (LSE_PIX_U8: value = (float)u8 / 255.0f, a division;
+ *      LSE_PIX_F32: the value itself), msk [H, W] of msk_type (LSE_PIX_U8 | LSE_PIX_F32; LSE_PIX_NONE: msk is ignored), rgb
+ *      [H * W, 3] f32 the rendered image.  Writes the contiguous [3, H, W] f32 planes gt_planes = value * msk and pred_planes =
+ *      rgb * msk (no multiplication without a mask): R:lse_nerf/lsenerf.py:477-530's `image * msk` / `rgb * msk` after moveaxis.
+ *      flags & LSE_PREP_EVENT_STATS: also the moments of the event-only metric (R:lse_nerf/lse_pipeline.py:149-164 over
+ *      R:lse_nerf/utils.py:99-135) into `stats`: per pixel y = logf(gray + 1e-6f), gray = (0.2989 r + 0.5870 g) + 0.1140 b of the
+ *      MASKED ground truth, and x = logf((r + g) + 1e-6f) of the UNMASKED prediction (the reference zeroes blue and sums the
+ *      channels of the image dictionary's halves, of which only the ground truth is masked); per workgroup the sums of x, x^2, y,
+ *      x y in double, in a fixed order, no atomics.  stats: lse_log_scale_correct_workspace bytes, 8-byte aligned.
+ *   lse_log_scale_correct: one launch.  Sums the partials in a fixed order and solves the normal equations of y ~ a x + b in double,
+ *      N = H * W: det = N Sxx - Sx^2, a = (N Sxy - Sx Sy) / det, b = (Sxx Sy - Sx Sxy) / det.  A NaN a or b becomes 5/255 (the
+ *      reference's rule); a det that is not finite, or zero to within the rounding of its two terms (|det| <= 2^-40 N Sxx), counts
+ *      as NaN for both -- there the reference's torch.linalg.inv raises, or inverts rounding noise.  Writes coef[2] = (a, b) as
+ *      f32, corrected[H * W] = expf((float)(a x + b)) and gray[H * W] (the grey masked ground truth): two [1, H, W] planes for
+ *      lse_image_metrics with C = 1 (the reference feeds three identical channels, whose mean over C is this one's value).
+ *      x and gray are recomputed from gt_planes / rgb with the arithmetic of the prep launch.  Two calls are bit-identical. */
+#define LSE_PREP_EVENT_STATS 1
+int lse_eval_image_prep(const void *gt, int32_t gt_type, const void *msk, int32_t msk_type, const float *rgb, int32_t H, int32_t W,
+                        int32_t flags, float *gt_planes, float *pred_planes, void *stats, int64_t stats_bytes, lse_stream_t stream);
+int lse_log_scale_correct_workspace(int32_t H, int32_t W, int64_t *h_bytes);
+int lse_log_scale_correct(const float *gt_planes, const float *rgb, int32_t H, int32_t W, const void *stats, int64_t stats_bytes,
+                          float *coef, float *corrected, float *gray, lse_stream_t stream);
+
 /* ---- occupancy grid (nerfacc OccGridEstimator._update) --------------------------- */
 /* occs[id] = max(occs[id]*ema_decay, occ_new); duplicate ids resolve to the maximum over the duplicates (upstream:
  * an arbitrary one of them wins).  workspace: n floats. */
@@ -650,6 +674,20 @@ int lse_compose_batch(const lse_compose_desc *desc, const lse_compose_scene *sce
 int lse_compose_rays_bwd(const lse_compose_desc *desc, const lse_compose_scene *scene, const lse_compose_out *out,
                          const float *d_origins, const float *d_directions, float *d_col_pose, float *d_prev_pose,
                          float *d_next_pose, lse_stream_t stream);
+
+/* ---- whole-image rays of one camera (the eval set): the composer's ray arithmetic over a row-major pixel range -------------
+ * Pixel p = first + i (y = p / W, x = p % W) of an H x W camera with the pose pose[3, 4] (device, f32; one row of a pose table)
+ * writes row i of origins / directions [n, 3] and pixel_area / directions_norm [n]: the device functions of lse_compose_batch, so
+ * the values are bit-equal to what the composer writes for the same (pose, y, x).  One thread per pixel, one launch.
+ * LSE_E_INVALID before any launch: first < 0, n < 0, first + n > H * W, a zero focal length, a null pose or output.  n == 0: no-op. */
+typedef struct lse_camera_desc {
+    float fx, fy, cx, cy;
+    float dist[6];          /* (k1, k2, k3, k4, p1, p2); read when `distort` != 0 */
+    int32_t distort;
+    int32_t H, W;
+} lse_camera_desc;
+int lse_camera_rays(const lse_camera_desc *cam, const float *pose, int64_t first, int64_t n, float *origins, float *directions,
+                    float *pixel_area, float *directions_norm, lse_stream_t stream);
 
 /* ---- spline camera poses: the composer's pose tables from a SplineCameraOptimizer's parameters, on the device -------------
  * Replaces, in front of every step, SplineCameraOptimizer.get_rgb_cameras / get_evs_cameras / get_deblur_cameras of

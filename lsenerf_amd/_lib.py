@@ -23,6 +23,7 @@ LSE_ABI_VERSION = 6
 LSE_MLP_ARITH_AUTO, LSE_MLP_ARITH_F32_MFMA = 0, 1
 LSE_TRAVERSE_FMA_SETUP = 1
 LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
+LSE_PREP_EVENT_STATS = 1
 LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
 
 
@@ -90,6 +91,12 @@ class ComposeOut(Structure):
         "evs_indices", "evs_batch_appearance_id")]
 
 
+class CameraDesc(Structure):
+    """lse_camera_desc: intrinsics, distortion and size of one camera set (lse_camera_rays)."""
+    _fields_ = [("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("dist", c_float * 6), ("distort", c_int32),
+                ("H", c_int32), ("W", c_int32)]
+
+
 class SplineDesc(Structure):
     """lse_spline_desc: a pose spline's parameters (device pointers), the per-query brackets and the per-control-point query lists."""
     _fields_ = [("n_ctrl", c_int32), ("n_query", c_int32 * 3), ("evs", c_int32 * 3), ("csr_len", c_int32), ("dM", c_float * 16),
@@ -145,6 +152,9 @@ SIGNATURES = {
     "lse_eval_composite_finish": [P, I32, I32, F32, P, P, P, P, P, P],
     "lse_image_metrics_workspace": [I32, I32, I32, I32, POINTER(c_int64)],
     "lse_image_metrics": [P, P, I32, I32, I32, I32, P, P, I64, P, P, P],
+    "lse_eval_image_prep": [P, I32, P, I32, P, I32, I32, I32, P, P, P, I64, P],
+    "lse_log_scale_correct_workspace": [I32, I32, POINTER(c_int64)],
+    "lse_log_scale_correct": [P, P, I32, I32, P, I64, P, P, P, P],
     "lse_render_weight_fwd": [P, P, P, P, I32, P, P, P, P],
     "lse_render_weight_bwd": [P, P, P, P, I32, P, P, P, P],
     "lse_loss_epilogue_fwd": [POINTER(EpilogueDesc), P, P, I32, P, P, P, P, I32, P, P, P, POINTER(MapperMlp), POINTER(MapperMlp), P, P],
@@ -163,6 +173,7 @@ SIGNATURES = {
     "lse_adam_schedule_dev": [P, P, P, P],
     "lse_compose_batch": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, I64, I32, P, P, P],
     "lse_compose_rays_bwd": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, P, P, P, P, P],
+    "lse_camera_rays": [POINTER(CameraDesc), P, I64, I64, P, P, P, P, P],
     "lse_spline_poses": [POINTER(SplineDesc), P, P, P, P],
     "lse_spline_poses_bwd": [POINTER(SplineDesc), P, P, P, P, P, P],
 }

@@ -81,4 +81,16 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+// one value of a resident image or mask of element type LSE_PIX_* as float
+__device__ __forceinline__ float load_pix(const void *p, int type, int64_t i)
+{
+    switch (type) {
+    case LSE_PIX_I8: return (float)static_cast<const int8_t *>(p)[i];
+    case LSE_PIX_U8: return (float)static_cast<const uint8_t *>(p)[i];
+    case LSE_PIX_I16: return (float)static_cast<const int16_t *>(p)[i];
+    case LSE_PIX_I32: return (float)static_cast<const int32_t *>(p)[i];
+    default: return static_cast<const float *>(p)[i];
+    }
+}
+
 }  // namespace lse

@@ -3,6 +3,8 @@
 //                    EdCameras.generate_rays (lsenerf_amd/cameras.py, R:lse_nerf/lse_cameras.py:340-586) from a pose table, and the
 //                    metadata of add_metadata / CameraIdxFixer (R:lse_nerf/utils.py:153-194, R:lse_nerf/data_components.py:70-90).
 //                    A colour pixel writes its G rays, an event pixel one ray into the previous and one into the next bundle.
+//   camera_rays_kernel  one thread per pixel of a row-major pixel range of ONE camera (the eval set's whole images): the same ray
+//                    device functions, so its rays are bit-equal to the composer's for the same (pose, y, x).
 //   advance_kernel   one thread: *step += 1, in stream order behind the composer (so the counter is part of a replayed graph).
 //   rays_bwd_kernel  d origins / d directions -> d pose table.  One wave per table row: every lane walks the rays of the row's
 //                    bundle(s) with stride 64, keeps the contributions of the rays that read this row in ray order, then a
@@ -33,16 +35,7 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1)
     return c;
 }
 
-__device__ __forceinline__ float load_pix(const void *p, int type, int64_t i)
-{
-    switch (type) {
-    case LSE_PIX_I8: return (float)static_cast<const int8_t *>(p)[i];
-    case LSE_PIX_U8: return (float)static_cast<const uint8_t *>(p)[i];
-    case LSE_PIX_I16: return (float)static_cast<const int16_t *>(p)[i];
-    case LSE_PIX_I32: return (float)static_cast<const int32_t *>(p)[i];
-    default: return static_cast<const float *>(p)[i];
-    }
-}
+using lse::load_pix;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -220,6 +213,19 @@ __global__ __launch_bounds__(kThreads) void compose_kernel(lse_compose_desc D, l
     }
 }
 
+// the rays of the row-major pixels [first, first + n) of one camera: compose_kernel's ray arithmetic (pixel_points, write_ray) with the
+// pixel taken from the thread index instead of a draw, so a ray is bit-equal to what the composer writes for the same (pose, y, x)
+__global__ __launch_bounds__(kThreads) void camera_rays_kernel(lse_compose_stream s, lse_compose_out O, const float *__restrict__ pose,
+                                                               int64_t first, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int64_t pix = first + i;
+    const int y = (int)(pix / s.W);
+    const int x = (int)(pix - (int64_t)y * s.W);
+    write_ray(O, i, pose, pixel_points(s, y, x));
+}
+
 __global__ void advance_kernel(int64_t *step)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *step = *step + 1;
@@ -360,6 +366,34 @@ extern "C" int lse_compose_batch(const lse_compose_desc *desc, const lse_compose
     hipLaunchKernelGGL(compose_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, st, *desc, S, *out,
                        (const int64_t *)step_dev, step, col_indices_in, evs_indices_in);
     if (advance) hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, step_dev);
+    return lse::check_launch(what);
+}
+
+extern "C" int lse_camera_rays(const lse_camera_desc *cam, const float *pose, int64_t first, int64_t n, float *origins,
+                               float *directions, float *pixel_area, float *directions_norm, lse_stream_t stream)
+{
+    const char *what = "lse_camera_rays";
+    LSE_REQUIRE(cam, "%s: null descriptor", what);
+    LSE_REQUIRE(cam->H >= 1 && cam->W >= 1, "%s: H and W must be >= 1 (got H=%d, W=%d)", what, cam->H, cam->W);
+    const int64_t pixels = (int64_t)cam->H * cam->W;
+    LSE_REQUIRE(pixels <= INT32_MAX, "%s: %lld pixels exceed the supported image size", what, (long long)pixels);
+    LSE_REQUIRE(cam->fx != 0.f && cam->fy != 0.f, "%s: zero focal length", what);
+    LSE_REQUIRE(first >= 0, "%s: first < 0", what);
+    LSE_REQUIRE(n >= 0, "%s: n < 0", what);
+    LSE_REQUIRE(first <= pixels && n <= pixels - first, "%s: pixels [%lld, %lld) leave the %d x %d image", what, (long long)first,
+                (long long)(first + n), cam->H, cam->W);
+    if (n == 0) return LSE_OK;
+    LSE_REQUIRE(pose, "%s: null pose", what);
+    LSE_REQUIRE(origins && directions && pixel_area && directions_norm, "%s: null output", what);
+    lse_compose_stream s = {};
+    s.fx = cam->fx; s.fy = cam->fy; s.cx = cam->cx; s.cy = cam->cy;
+    for (int k = 0; k < 6; ++k) s.dist[k] = cam->dist[k];
+    s.H = cam->H; s.W = cam->W;
+    s.distort = cam->distort;
+    lse_compose_out o = {};
+    o.origins = origins; o.directions = directions; o.pixel_area = pixel_area; o.directions_norm = directions_norm;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, lse::as_stream(stream),
+                       s, o, pose, first, n);
     return lse::check_launch(what);
 }
 

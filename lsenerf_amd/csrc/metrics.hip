@@ -11,6 +11,16 @@
 //   3. metrics_final_kernel: one workgroup sums the tile partials and the squared-difference partials in a fixed order.
 // Moments, SSIM and every sum are formed in double (FP64 is full-rate vector arithmetic here): sigma^2 = E[x^2] - mu^2 cancels badly
 // in f32 when the data range is small against the values, and the fixed-order sums make the result bit-reproducible.
+//
+// In front of them, for a whole eval set (lsenerf_amd/eval_set.py):
+//   eval_prep_kernel: one launch per image -- resident ground truth (uint8 / 255.0f, a division, or f32) and rendered rgb, times the
+//      optional mask, as the two [3, H, W] planes above; optionally the per-workgroup double sums of x, x^2, y, x y of the event-only
+//      metric (R:lse_nerf/lse_pipeline.py:149-164): y = logf(gray(masked gt) + 1e-6f), x = logf((pred_r + pred_g) + 1e-6f) of the
+//      UNMASKED prediction -- the reference passes the image dictionary's halves, of which only the ground truth is masked;
+//   log_scale_correct_kernel: the reference's correct_img_scale / solve_normal_equations (R:lse_nerf/utils.py:109-135) -- every
+//      workgroup sums the partials in the same order, solves y ~ a x + b in double (NaN -> 5/255; a singular system, where the
+//      reference's torch.linalg.inv raises, counts as NaN) and writes expf(a x + b) and the grey ground truth as [1, H, W] planes.
+// logf / expf are the accurate library functions; the grey sum is written with single roundings (no contraction).
 #include "common.h"
 
 namespace {
@@ -186,6 +196,128 @@ __global__ __launch_bounds__(kFinalThreads) void metrics_final_kernel(const doub
     }
 }
 
+// ---- eval images: ground truth + render -> metric planes, and the event-only metric's log-space scale correction ----------------
+constexpr int kPrepThreads = 256;
+
+// to_gray of the reference (img @ [0.2989, 0.5870, 0.1140]): three products summed left to right, every operation rounded once
+__device__ __forceinline__ float gray3(float r, float g, float b)
+{
+#pragma clang fp contract(off)
+    return (r * 0.2989f + g * 0.5870f) + b * 0.1140f;
+}
+
+// log of the prediction's R + G (its blue channel zeroed, then summed over the channels), unmasked
+__device__ __forceinline__ float log_pred(const float *__restrict__ rgb, int64_t p)
+{
+    return logf((rgb[3 * p] + rgb[3 * p + 1]) + 1e-6f);
+}
+
+// partials (doubles): [sum x G][sum x^2 G][sum y G][sum x y G]; part == nullptr: planes only
+__global__ __launch_bounds__(kPrepThreads) void eval_prep_kernel(const void *__restrict__ gt, int gt_type, const void *__restrict__ msk,
+                                                                 int msk_type, const float *__restrict__ rgb, int64_t HW,
+                                                                 float *__restrict__ gt_pl, float *__restrict__ pr_pl,
+                                                                 double *__restrict__ part)
+{
+    __shared__ double s_d[4][kPrepThreads / 64];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * kPrepThreads;
+    for (int64_t p = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x; p < HW; p += stride) {
+        float v[3], q[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            v[c] = gt_type == LSE_PIX_U8 ? (float)static_cast<const uint8_t *>(gt)[3 * p + c] / 255.0f
+                                         : static_cast<const float *>(gt)[3 * p + c];
+            q[c] = rgb[3 * p + c];
+        }
+        if (msk_type != LSE_PIX_NONE) {
+            const float m = lse::load_pix(msk, msk_type, p);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                v[c] = v[c] * m;
+                q[c] = q[c] * m;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            gt_pl[c * HW + p] = v[c];
+            pr_pl[c * HW + p] = q[c];
+        }
+        if (part != nullptr) {
+            const double x = log_pred(rgb, p);
+            const double y = logf(gray3(v[0], v[1], v[2]) + 1e-6f);
+            acc[0] += x; acc[1] += x * x; acc[2] += y; acc[3] += x * y;
+        }
+    }
+    if (part == nullptr) return;
+    const int wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        acc[q] = wave_sum_d(acc[q]);
+        if ((threadIdx.x & 63) == 0) s_d[q][wv] = acc[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int q = threadIdx.x;
+        double s = s_d[q][0];
+        for (int k = 1; k < kPrepThreads / 64; ++k) s += s_d[q][k];
+        part[(int64_t)q * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// every workgroup sums the G partials in the same order and solves the same 2 x 2 system: one (a, b) for all
+__global__ __launch_bounds__(kPrepThreads) void log_scale_correct_kernel(const float *__restrict__ gt_pl, const float *__restrict__ rgb,
+                                                                         int64_t HW, const double *__restrict__ part, int G,
+                                                                         float *__restrict__ coef, float *__restrict__ corrected,
+                                                                         float *__restrict__ gray)
+{
+    __shared__ double s_d[4][kPrepThreads / 64];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = threadIdx.x; k < G; k += kPrepThreads) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] += part[(int64_t)q * G + k];
+    }
+    const int wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        acc[q] = wave_sum_d(acc[q]);
+        if ((threadIdx.x & 63) == 0) s_d[q][wv] = acc[q];
+    }
+    __syncthreads();
+    double S[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        S[q] = s_d[q][0];
+        for (int k = 1; k < kPrepThreads / 64; ++k) S[q] += s_d[q][k];
+    }
+    const double N = (double)HW, Sx = S[0], Sxx = S[1], Sy = S[2], Sxy = S[3];
+    const double det = N * Sxx - Sx * Sx;
+    double a = NAN, b = NAN;
+    if (isfinite(det) && fabs(det) > 0x1p-40 * fabs(N * Sxx)) {
+        a = (N * Sxy - Sx * Sy) / det;
+        b = (Sxx * Sy - Sx * Sxy) / det;
+    }
+    if (isnan(a)) a = 5.0 / 255.0;
+    if (isnan(b)) b = 5.0 / 255.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        coef[0] = (float)a;
+        coef[1] = (float)b;
+    }
+    const int64_t stride = (int64_t)gridDim.x * kPrepThreads;
+    for (int64_t p = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x; p < HW; p += stride) {
+        const double x = log_pred(rgb, p);
+        corrected[p] = expf((float)(a * x + b));
+        gray[p] = gray3(gt_pl[p], gt_pl[HW + p], gt_pl[2 * HW + p]);
+    }
+}
+
+int prep_shape(int32_t H, int32_t W, int *G, const char *what)
+{
+    LSE_REQUIRE(H >= 1 && W >= 1, "%s: H and W must be >= 1 (got H=%d, W=%d)", what, H, W);
+    LSE_REQUIRE((int64_t)H * W <= INT32_MAX, "%s: %lld pixels exceed the supported image size", what, (long long)H * W);
+    *G = stats_blocks((int64_t)H * W);
+    return LSE_OK;
+}
+
 struct Layout {
     int G, tiles_x, tiles_y;
     int64_t n_tiles;
@@ -242,4 +374,57 @@ extern "C" int lse_image_metrics(const float *preds, const float *target, int32_
     hipLaunchKernelGGL(metrics_final_kernel, dim3(1), dim3(kFinalThreads), 0, st, (const double *)tiles, L.n_tiles,
                        (const double *)(stats + 4 * (int64_t)L.G), L.G, n_valid, (double)total, out_ssim, out_mse);
     return lse::check_launch("lse_image_metrics");
+}
+
+extern "C" int lse_log_scale_correct_workspace(int32_t H, int32_t W, int64_t *h_bytes)
+{
+    const char *what = "lse_log_scale_correct_workspace";
+    LSE_REQUIRE(h_bytes, "%s: null pointer", what);
+    int G;
+    const int rc = prep_shape(H, W, &G, what);
+    if (rc != LSE_OK) return rc;
+    *h_bytes = (int64_t)sizeof(double) * 4 * G;
+    return LSE_OK;
+}
+
+extern "C" int lse_eval_image_prep(const void *gt, int32_t gt_type, const void *msk, int32_t msk_type, const float *rgb, int32_t H,
+                                   int32_t W, int32_t flags, float *gt_planes, float *pred_planes, void *stats, int64_t stats_bytes,
+                                   lse_stream_t stream)
+{
+    const char *what = "lse_eval_image_prep";
+    int G;
+    const int rc = prep_shape(H, W, &G, what);
+    if (rc != LSE_OK) return rc;
+    LSE_REQUIRE(gt_type == LSE_PIX_U8 || gt_type == LSE_PIX_F32, "%s: gt_type %d (uint8 or f32 images)", what, gt_type);
+    LSE_REQUIRE(msk_type == LSE_PIX_NONE || msk_type == LSE_PIX_U8 || msk_type == LSE_PIX_F32, "%s: msk_type %d", what, msk_type);
+    LSE_REQUIRE((flags & ~LSE_PREP_EVENT_STATS) == 0, "%s: unknown flags %d", what, flags);
+    LSE_REQUIRE(gt && rgb && gt_planes && pred_planes, "%s: null pointer", what);
+    LSE_REQUIRE(msk_type == LSE_PIX_NONE || msk, "%s: null mask with msk_type %d", what, msk_type);
+    double *part = nullptr;
+    if (flags & LSE_PREP_EVENT_STATS) {
+        LSE_REQUIRE(stats, "%s: null stats workspace", what);
+        LSE_REQUIRE(stats_bytes >= (int64_t)sizeof(double) * 4 * G, "%s: stats workspace of %lld bytes, %lld needed", what,
+                    (long long)stats_bytes, (long long)(sizeof(double) * 4 * G));
+        LSE_REQUIRE(reinterpret_cast<uintptr_t>(stats) % sizeof(double) == 0, "%s: stats workspace not 8-byte aligned", what);
+        part = static_cast<double *>(stats);
+    }
+    hipLaunchKernelGGL(eval_prep_kernel, dim3(G), dim3(kPrepThreads), 0, lse::as_stream(stream), gt, (int)gt_type, msk, (int)msk_type,
+                       rgb, (int64_t)H * W, gt_planes, pred_planes, part);
+    return lse::check_launch(what);
+}
+
+extern "C" int lse_log_scale_correct(const float *gt_planes, const float *rgb, int32_t H, int32_t W, const void *stats,
+                                     int64_t stats_bytes, float *coef, float *corrected, float *gray, lse_stream_t stream)
+{
+    const char *what = "lse_log_scale_correct";
+    int G;
+    const int rc = prep_shape(H, W, &G, what);
+    if (rc != LSE_OK) return rc;
+    LSE_REQUIRE(gt_planes && rgb && stats && coef && corrected && gray, "%s: null pointer", what);
+    LSE_REQUIRE(stats_bytes >= (int64_t)sizeof(double) * 4 * G, "%s: stats workspace of %lld bytes, %lld needed", what,
+                (long long)stats_bytes, (long long)(sizeof(double) * 4 * G));
+    LSE_REQUIRE(reinterpret_cast<uintptr_t>(stats) % sizeof(double) == 0, "%s: stats workspace not 8-byte aligned", what);
+    hipLaunchKernelGGL(log_scale_correct_kernel, dim3(G), dim3(kPrepThreads), 0, lse::as_stream(stream), gt_planes, rgb, (int64_t)H * W,
+                       static_cast<const double *>(stats), G, coef, corrected, gray);
+    return lse::check_launch(what);
 }

@@ -21,7 +21,8 @@ differentiable torch expressions over O(cameras) rows, and ``lse_compose_rays_bw
 
 The outputs of ``compose`` ARE the composer's static buffers (row blocks of one buffer per field, the layout
 ``graph._static_bundles`` uses): the next ``compose`` overwrites them.  All images are resident (the reference's
-``num_images_to_sample_from = -1``); an image-subset cache, patch sampling and eval loaders are out of scope.
+``num_images_to_sample_from = -1``); an image-subset cache and patch sampling are out of scope.  Whole eval images are
+``lsenerf_amd.eval_set``'s: an ``EvalSet`` is a ``CameraSetData`` with a pose table of its own.
 """
 from __future__ import annotations
 

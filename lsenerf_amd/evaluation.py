@@ -72,7 +72,7 @@ def _render_loop(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
     return {k: torch.cat(v) for k, v in lists.items()}
 
 
-def _render_count_free(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
+def _render_count_free(model, rb: RayBundle, chunk: int, check_overflow: bool = True) -> Dict[str, Tensor]:
     cfg, fld = model.config, model.field
     R = len(rb)
     dev = rb.origins.device
@@ -96,7 +96,8 @@ def _render_count_free(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
         sigma, _, _, head = fld.density_rgb_packed(rays_o, rays_d, ri, ts, te, packed, eidx, table, n_dev)
         ops.eval_composite(ts, te, sigma, head, packed, rgb[lo:hi], acc[lo:hi], depth[lo:hi], nsamples[lo:hi],
                            nan_to_num=not linear, background=background, clamp=not linear, workspace=ws)
-    model.occupancy_grid.check_deferred_overflow()      # the one read-back: a truncated ray raises here
+    if check_overflow:
+        model.occupancy_grid.check_deferred_overflow()      # the one read-back: a truncated ray raises here
     raw = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": nsamples}
     return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
 
@@ -132,7 +133,7 @@ def early_stop_settings(config) -> Tuple[float, int]:
     return eps, int(base)
 
 
-def _render_early_stop(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
+def _render_early_stop(model, rb: RayBundle, chunk: int, check_overflow: bool = True) -> Dict[str, Tensor]:
     """The count-free route with early ray termination: a chunk is marched as in ``_render_count_free`` but its samples stay in the
     marcher's per-ray slots; per segment of ``segment_schedule`` the live rays' samples are packed, the field evaluates them and
     ``lse_eval_composite_segment`` continues every ray from its saved state, finishing those whose optical depth has reached
@@ -189,15 +190,18 @@ def _render_early_stop(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
                                        seg_cnts[:m] if next_len else None, nan_to_num=not linear)
         ops.eval_composite_finish(state, rgb[lo:hi], acc[lo:hi], depth[lo:hi], nsamples[lo:hi], background=background,
                                   clamp=not linear, workspace=ws)
-    model.occupancy_grid.check_deferred_overflow()      # the one read-back, as on the full route
+    if check_overflow:
+        model.occupancy_grid.check_deferred_overflow()      # the one read-back, as on the full route
     raw = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": nsamples}
     return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
 
 
 @torch.no_grad()
-def render_flat(model, rb: RayBundle) -> Dict[str, Tensor]:
+def render_flat(model, rb: RayBundle, check_overflow: bool = True) -> Dict[str, Tensor]:
     """Outputs ``[R, ...]`` for the ``[R, ...]`` bundle ``rb``, chunked by ``config.eval_num_rays_per_chunk`` on every route (the
-    chunking is observable: nerfstudio's fake sample is inserted per chunk)."""
+    chunking is observable: nerfstudio's fake sample is inserted per chunk).  ``check_overflow=False`` leaves out the count-free
+    routes' ``check_deferred_overflow()`` behind the last chunk: the accumulator is sticky, so a caller that renders many images
+    (``eval_set.evaluate_set``) reads it once behind the last of them -- and MUST do so."""
     chunk = int(model.config.eval_num_rays_per_chunk)
     if chunk <= 0:
         raise ValueError("eval_num_rays_per_chunk must be positive")
@@ -206,8 +210,8 @@ def render_flat(model, rb: RayBundle) -> Dict[str, Tensor]:
         raise ValueError("empty ray bundle")
     if uses_count_free_route(model, len(rb)):
         if eps > 0.0:
-            return _render_early_stop(model, rb, chunk)
-        return _render_count_free(model, rb, chunk)
+            return _render_early_stop(model, rb, chunk, check_overflow)
+        return _render_count_free(model, rb, chunk, check_overflow)
     return _render_loop(model, rb, chunk)
 
 

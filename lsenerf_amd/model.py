@@ -539,6 +539,13 @@ class LSENeRFModel(nn.Module):
         [H, W, C] outputs.  ``camera_opt_to_camera``: a pose correction as ``EdCameras.generate_rays`` takes it."""
         return evaluation.render_camera(self, cameras, camera_index, camera_opt_to_camera)
 
+    def evaluate_set(self, eval_set, events_only: bool = False, on_image=None):
+        """``(average, per_image)`` metrics over a device-resident ``eval_set.EvalSet`` -- the reference pipeline's
+        ``get_average_eval_image_metrics`` without host work or a wait per image; ``events_only``: its ``update_evs_only_metric``
+        (grey, scale-corrected psnr / ssim).  See ``lsenerf_amd.eval_set.evaluate_set``."""
+        from . import eval_set as _eval_set
+        return _eval_set.evaluate_set(self, eval_set, events_only=events_only, on_image=on_image)
+
     def _ngp_metrics_dict(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]) -> Dict[str, Tensor]:
         image = batch["image"].to(outputs["rgb"].device)
         return {"psnr": self.psnr(outputs["rgb"], image), "num_samples_per_batch": outputs["num_samples_per_ray"].sum()}

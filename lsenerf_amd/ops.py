@@ -1278,12 +1278,15 @@ def image_metrics_workspace_bytes(B: int, C: int, H: int, W: int) -> int:
 
 
 @torch.no_grad()
-def image_metrics(preds: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def image_metrics(preds: torch.Tensor, target: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(ssim, mse): two 0-dim float32 device tensors for ``preds`` / ``target`` [B,C,H,W] f32 (lse_image_metrics; H, W >= 11).
     SSIM is torchmetrics' ``structural_similarity_index_measure(preds, target)`` with its defaults (Gaussian 11-tap window, sigma 1.5,
     data range from the inputs, K = (0.01, 0.03), mean over the valid windows), restated from the published algorithm: torchmetrics
     is not a dependency, so that parity is UNPINNED -- the tests hold the kernel against a float64 numpy restatement.  MSE is the mean
-    squared difference over every pixel.  Nothing is read back to the host."""
+    squared difference over every pixel.  Nothing is read back to the host.  ``out``: a contiguous float32 device tensor whose
+    first two elements receive (ssim, mse) -- a row of a metrics table; ``workspace``: float64, at least
+    ``image_metrics_workspace_bytes`` bytes (both allocated when absent)."""
     global _SSIM_WINDOW
     if preds.dim() != 4 or preds.shape != target.shape:
         raise ValueError(f"image_metrics: preds and target must both be [B,C,H,W] (got {tuple(preds.shape)} and {tuple(target.shape)})")
@@ -1291,11 +1294,129 @@ def image_metrics(preds: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tens
     nbytes = image_metrics_workspace_bytes(B, C, H, W)       # refuses H or W < 11 with the library's message
     if _SSIM_WINDOW is None:
         _SSIM_WINDOW = (ctypes.c_float * 11)(*ssim_window().tolist())
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=preds.device)
-    out = torch.empty(2, dtype=torch.float32, device=preds.device)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=preds.device)
+    elif workspace.numel() * 8 < nbytes:
+        raise ValueError(f"image_metrics: workspace of {workspace.numel() * 8} bytes, {nbytes} needed")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=preds.device)
+    elif out.dim() != 1 or out.numel() < 2:
+        raise ValueError("image_metrics: out must be a 1-D tensor of at least two elements")
     _lib.call("lse_image_metrics", _f32(preds, "preds"), _f32(target, "target"), B, C, H, W, _SSIM_WINDOW,
-              ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(out.data_ptr() + 4), _stream())
+              _chk(workspace, torch.float64, "workspace"), nbytes, _f32(out, "out"), ctypes.c_void_p(out.data_ptr() + 4), _stream())
     return out[0], out[1]
+
+
+# ----------------------------------------------------------------------------------------------------
+# whole eval sets: rays of one camera, metric planes, the event-only metric's scale correction
+# ----------------------------------------------------------------------------------------------------
+def camera_desc(fx: float, fy: float, cx: float, cy: float, H: int, W: int, dist=None) -> "_lib.CameraDesc":
+    """``lse_camera_desc`` of one camera set; ``dist``: (k1, k2, k3, k4, p1, p2), None or all zero = pinhole."""
+    d = [0.0] * 6 if dist is None else [float(v) for v in dist]
+    if len(d) != 6:
+        raise ValueError("camera_desc: six distortion parameters (k1, k2, k3, k4, p1, p2) expected")
+    return _lib.CameraDesc(fx=float(fx), fy=float(fy), cx=float(cx), cy=float(cy), dist=(ctypes.c_float * 6)(*d),
+                           distort=int(any(v != 0.0 for v in d)), H=int(H), W=int(W))
+
+
+@torch.no_grad()
+def camera_rays(cam_desc, pose: torch.Tensor, first: int, n: int, out=None):
+    """(origins [n, 3], directions [n, 3], pixel_area [n, 1], directions_norm [n, 1]) of the row-major pixels ``[first, first + n)``
+    of the camera ``cam_desc`` (``camera_desc``) with the pose ``pose`` [3, 4] -- a float32 device tensor, usually a row of a pose
+    table (lse_camera_rays: ``EdCameras.generate_rays`` with the composer's arithmetic, bit-equal to ``BatchComposer.compose`` on the
+    same pixels).  ``out``: four contiguous float32 tensors of at least ``n`` rows to write rows ``[0, n)`` of (returned as given)."""
+    first, n = int(first), int(n)
+    if tuple(pose.shape) != (3, 4):
+        raise ValueError(f"camera_rays: pose must be [3, 4], got {tuple(pose.shape)}")
+    if out is None:
+        dev = pose.device
+        rows = max(n, 0)
+        out = (torch.empty((rows, 3), dtype=torch.float32, device=dev), torch.empty((rows, 3), dtype=torch.float32, device=dev),
+               torch.empty((rows, 1), dtype=torch.float32, device=dev), torch.empty((rows, 1), dtype=torch.float32, device=dev))
+    o, d, area, norm = out
+    for t, width, name in ((o, 3, "origins"), (d, 3, "directions"), (area, 1, "pixel_area"), (norm, 1, "directions_norm")):
+        if t.numel() < max(n, 0) * width or (t.dim() > 1 and t.shape[-1] != width):
+            raise ValueError(f"camera_rays: {name} must hold at least {n} rows of {width}")
+    _lib.call("lse_camera_rays", ctypes.byref(cam_desc), _f32(pose, "pose"), first, n, _f32(o, "origins"), _f32(d, "directions"),
+              _f32(area, "pixel_area"), _f32(norm, "directions_norm"), _stream())
+    return out
+
+
+def log_scale_correct_workspace_bytes(H: int, W: int) -> int:
+    v = ctypes.c_int64(0)
+    _lib.call("lse_log_scale_correct_workspace", int(H), int(W), ctypes.byref(v))
+    return int(v.value)
+
+
+_PIX_OF_DTYPE = {torch.uint8: _lib.LSE_PIX_U8, torch.float32: _lib.LSE_PIX_F32}
+
+
+@torch.no_grad()
+def eval_image_prep(gt: torch.Tensor, rgb: torch.Tensor, msk: Optional[torch.Tensor] = None, event_stats: bool = False, out=None,
+                    stats: Optional[torch.Tensor] = None):
+    """(gt_planes, pred_planes, stats): the two [1, 3, H, W] float32 images ``image_metrics`` takes, from the resident ground truth
+    ``gt`` [H, W, 3] (uint8: ``float(u8) / 255``; or float32), the rendered ``rgb`` [H * W, 3] (or [H, W, 3]) and the optional mask
+    ``msk`` [H, W] (uint8 or float32): ``moveaxis(image * msk)`` / ``moveaxis(rgb * msk)`` of ``image_metrics_and_images`` bit for
+    bit, in one launch (lse_eval_image_prep).  ``event_stats``: also the per-workgroup moments of the event-only metric into
+    ``stats`` (float64, ``log_scale_correct_workspace_bytes``; allocated when absent) for ``log_scale_correct``; else ``stats``
+    is returned as None.  ``out``: (gt_planes, pred_planes) to write into."""
+    if gt.dim() != 3 or gt.shape[-1] != 3 or gt.dtype not in _PIX_OF_DTYPE:
+        raise ValueError(f"eval_image_prep: gt must be uint8 or float32 [H, W, 3], got {gt.dtype} {tuple(gt.shape)}")
+    H, W = int(gt.shape[0]), int(gt.shape[1])
+    if rgb.numel() != H * W * 3 or rgb.shape[-1] != 3:
+        raise ValueError(f"eval_image_prep: rgb must be [{H * W}, 3], got {tuple(rgb.shape)}")
+    msk_type = _lib.LSE_PIX_NONE
+    if msk is not None:
+        if tuple(msk.shape) != (H, W) or msk.dtype not in _PIX_OF_DTYPE:
+            raise ValueError(f"eval_image_prep: msk must be uint8 or float32 [{H}, {W}], got {msk.dtype} {tuple(msk.shape)}")
+        msk_type = _PIX_OF_DTYPE[msk.dtype]
+    if out is None:
+        out = (torch.empty((1, 3, H, W), dtype=torch.float32, device=rgb.device),
+               torch.empty((1, 3, H, W), dtype=torch.float32, device=rgb.device))
+    gt_pl, pr_pl = out
+    if gt_pl.numel() != 3 * H * W or pr_pl.numel() != 3 * H * W:
+        raise ValueError(f"eval_image_prep: the planes must be [1, 3, {H}, {W}]")
+    nbytes = 0
+    if event_stats:
+        nbytes = log_scale_correct_workspace_bytes(H, W)
+        if stats is None:
+            stats = torch.empty(nbytes // 8, dtype=torch.float64, device=rgb.device)
+        elif stats.numel() * 8 < nbytes:
+            raise ValueError(f"eval_image_prep: stats of {stats.numel() * 8} bytes, {nbytes} needed")
+    else:
+        stats = None
+    _lib.call("lse_eval_image_prep", _chk(gt, gt.dtype, "gt"), _PIX_OF_DTYPE[gt.dtype],
+              _chk(msk, msk.dtype, "msk") if msk is not None else None, msk_type, _f32(rgb, "rgb"), H, W,
+              _lib.LSE_PREP_EVENT_STATS if event_stats else 0, _f32(gt_pl, "gt_planes"), _f32(pr_pl, "pred_planes"),
+              _chk(stats, torch.float64, "stats", allow_none=True), nbytes, _stream())
+    return gt_pl, pr_pl, stats
+
+
+@torch.no_grad()
+def log_scale_correct(gt_planes: torch.Tensor, rgb: torch.Tensor, stats: torch.Tensor, out=None):
+    """(coef [2], corrected [1, 1, H, W], gray [1, 1, H, W]) of the event-only metric (lse_log_scale_correct;
+    R:lse_nerf/utils.py:99-135): the least-squares affine fit ``log(gray gt + 1e-6) ~ a log(pred_r + pred_g + 1e-6) + b`` from the
+    moments ``eval_image_prep(..., event_stats=True)`` left in ``stats``, solved in double (``coef`` = (a, b) in float32; 5/255
+    where the reference's NaN rule applies or the system is singular), the corrected prediction ``exp(a x + b)`` and the grey
+    ground truth.  ``gt_planes`` [1, 3, H, W] and ``rgb`` are those of the prep call.  Deterministic; nothing is read back."""
+    if gt_planes.dim() != 4 or gt_planes.shape[:2] != (1, 3):
+        raise ValueError(f"log_scale_correct: gt_planes must be [1, 3, H, W], got {tuple(gt_planes.shape)}")
+    H, W = int(gt_planes.shape[2]), int(gt_planes.shape[3])
+    if rgb.numel() != H * W * 3 or rgb.shape[-1] != 3:
+        raise ValueError(f"log_scale_correct: rgb must be [{H * W}, 3], got {tuple(rgb.shape)}")
+    nbytes = log_scale_correct_workspace_bytes(H, W)
+    if stats is None or stats.numel() * 8 < nbytes:
+        raise ValueError(f"log_scale_correct: stats of at least {nbytes} bytes expected (eval_image_prep(..., event_stats=True))")
+    if out is None:
+        dev = rgb.device
+        out = (torch.empty(2, dtype=torch.float32, device=dev), torch.empty((1, 1, H, W), dtype=torch.float32, device=dev),
+               torch.empty((1, 1, H, W), dtype=torch.float32, device=dev))
+    coef, corrected, gray = out
+    if coef.numel() < 2 or corrected.numel() != H * W or gray.numel() != H * W:
+        raise ValueError(f"log_scale_correct: coef [2] and two [1, 1, {H}, {W}] planes expected")
+    _lib.call("lse_log_scale_correct", _f32(gt_planes, "gt_planes"), _f32(rgb, "rgb"), H, W, _chk(stats, torch.float64, "stats"),
+              nbytes, _f32(coef, "coef"), _f32(corrected, "corrected"), _f32(gray, "gray"), _stream())
+    return coef, corrected, gray
 
 
 # ----------------------------------------------------------------------------------------------------
