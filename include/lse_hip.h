@@ -727,6 +727,41 @@ int lse_spline_poses(const lse_spline_desc *desc, float *col_pose, float *prev_p
 int lse_spline_poses_bwd(const lse_spline_desc *desc, const float *d_col_pose, const float *d_prev_pose, const float *d_next_pose,
                          float *d_ctrl_tangents, float *d_scale, lse_stream_t stream);
 
+/* ---- per-camera pose deltas: the composer's pose tables from the pose_adjustment of CameraOptimizer / PrevNextCamOptimizer ------
+ * Replaces, in front of every step, lsenerf_amd.data.camera_tables + BatchComposer.set_poses for the per-camera optimisers of
+ * lsenerf_amd/cameras.py (CameraOptimizer.forward over hom_exp_map_SO3xR3 / exp_map_SE3; R:lse_nerf/ns_camera_optimizer.py:214-414,
+ * which R:lse_nerf/lse_datamanager.py:285-304 builds whenever optim_type is not "spline").
+ * Up to three tables, colour | prev | next, are fed (n_cam[s] cameras; 0 = the table is not fed).  Row c of table s is
+ *   [R_corr(c) R0(c) | t0(c) + t_corr(c)],  (R_corr | t_corr) = exp_map(adj[s][c]),  (R0 | t0) = base[s][c];
+ * a camera with frozen[s][c] != 0 gets (R_corr | t_corr) = (I | 0).  mode[s] picks the exponential:
+ *   LSE_POSE_SO3XR3  theta = sqrt(max(|w|^2, 1e-4)), R = I + (sin theta / theta) K + ((1 - cos theta) / theta^2) K^2, t_corr = v;
+ *   LSE_POSE_SE3     |w|^2 < 1e-4: a = 1 - t2/6, b = 1/2 - t2/24, c = 1/6 - t2/120, else the closed forms;
+ *                    R = I + a W + b W^2, t_corr = (I + b W + c W^2) v,
+ * with adj row = (v, w).  adj is read from the parameters' own storage at every launch: an in-place optimiser update is seen by the
+ * next launch (or graph replay) without a copy.  Everything is f32; (1 - cos t) / t^2 and (t - sin t) / t^3 and their derivatives
+ * are evaluated without cancellation (series below t = 2, half-angle form above).
+ * shared_prev_next != 0: ONE parameter block feeds prev and next (adj[2] == adj[1], frozen[2] == frozen[1], equal counts and
+ * modes), each over its own base poses; its gradient is the sum of the two rows. */
+#define LSE_POSE_SO3XR3 0
+#define LSE_POSE_SE3 1
+typedef struct lse_pose_delta_desc {
+    int32_t n_cam[3];            /* cameras (= rows) of the colour | prev | next table fed */
+    int32_t mode[3];             /* LSE_POSE_SO3XR3 | LSE_POSE_SE3 */
+    int32_t shared_prev_next;    /* 0 | 1 */
+    const float *base[3];        /* [n_cam[s], 3, 4] the scene's camera_to_worlds (static) */
+    const float *adj[3];         /* [n_cam[s], 6] pose_adjustment (translation part, rotation vector) */
+    const uint8_t *frozen[3];    /* [n_cam[s]] non-trainable cameras, or NULL */
+} lse_pose_delta_desc;
+/* One launch (one thread per row) writes every row of the fed tables [n_cam[s], 3, 4]; the table of a segment with n_cam == 0 is
+ * not touched (NULL allowed). */
+int lse_pose_delta_tables(const lse_pose_delta_desc *desc, float *col_pose, float *prev_pose, float *next_pose, lse_stream_t stream);
+/* d tables -> d_adj_* [n_cam[s], 6], every element OVERWRITTEN; one launch, one thread per (parameter block, camera), no atomics: two
+ * runs are bit-equal.  The derivative torch autograd takes of cameras.py: `where` selects a branch and the clamp passes no gradient
+ * below its bound (SO3xR3 coefficients are constants below |w| = 0.01); a frozen camera gets exact zeros.  With shared_prev_next the
+ * camera's gradient, row(prev) + row(next) in that order, goes to d_adj_prev and d_adj_next is not written (NULL allowed). */
+int lse_pose_delta_tables_bwd(const lse_pose_delta_desc *desc, const float *d_col_pose, const float *d_prev_pose,
+                              const float *d_next_pose, float *d_adj_col, float *d_adj_prev, float *d_adj_next, lse_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,16 @@ class SplineDesc(Structure):
                 ("csr_query", c_void_p)]
 
 
+LSE_POSE_SO3XR3, LSE_POSE_SE3 = 0, 1
+
+
+class PoseDeltaDesc(Structure):
+    """lse_pose_delta_desc: per fed pose table the camera count, the exponential, the base poses, the pose_adjustment parameters
+    (device pointers, read in place) and the optional mask of non-trainable cameras."""
+    _fields_ = [("n_cam", c_int32 * 3), ("mode", c_int32 * 3), ("shared_prev_next", c_int32), ("base", c_void_p * 3),
+                ("adj", c_void_p * 3), ("frozen", c_void_p * 3)]
+
+
 P = c_void_p
 I32, I64, F32 = c_int32, c_int64, c_float
 
@@ -176,6 +186,8 @@ SIGNATURES = {
     "lse_camera_rays": [POINTER(CameraDesc), P, I64, I64, P, P, P, P, P],
     "lse_spline_poses": [POINTER(SplineDesc), P, P, P, P],
     "lse_spline_poses_bwd": [POINTER(SplineDesc), P, P, P, P, P, P],
+    "lse_pose_delta_tables": [POINTER(PoseDeltaDesc), P, P, P, P],
+    "lse_pose_delta_tables_bwd": [POINTER(PoseDeltaDesc), P, P, P, P, P, P, P],
 }
 # exported by the development build only (csrc/dev_knobs.h)
 DEV_SIGNATURES = {

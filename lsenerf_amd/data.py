@@ -307,6 +307,7 @@ class BatchComposer:
         self.pose_tables: Tuple[Optional[Tensor], Optional[Tensor], Optional[Tensor]] = (t_col, t_prev, t_nxt)
         self._pose_grads = tuple(None if t is None else torch.zeros_like(t) for t in self.pose_tables)
         self.spline = None                     # attach_spline(): a SplinePoses that fills (some of) the tables in front of every compose
+        self.deltas = None                     # attach_camera_optimizers(): a DeltaPoses, the same for the per-camera optimisers
         self.bundles = self._make_bundles(self._buf["origins"], self._buf["directions"])
         # C-ABI descriptors (host structs; the pointers are those of the static tensors above)
         key = "consec" if self.consec else "prev"
@@ -370,6 +371,8 @@ class BatchComposer:
                 raise ValueError(f"this composer has no '{name}' pose table")
             if self.spline is not None and self.spline.fed[i]:
                 raise ValueError(f"the '{name}' pose table is fed by the attached spline: every compose() overwrites it")
+            if self.deltas is not None and self.deltas.fed[i]:
+                raise ValueError(f"the '{name}' pose table is fed by the attached camera optimiser: every compose() overwrites it")
             if name == "col" and src.dim() == 3:
                 src = src[:, None].expand(-1, self.G, -1, -1)
             if tuple(src.shape) != tuple(dst.shape):
@@ -399,21 +402,23 @@ class BatchComposer:
                  "nxt": None if not self.n_evs or self.consec else ("evs", scene.evs_times["next"])}
         if self.G == 4 and "col" in names and int(spline.n_deblur_rays) != self.G:
             raise ValueError(f"the spline has {spline.n_deblur_rays} deblur cameras per exposure, the composer {self.G} rays per pixel")
+        if self.deltas is not None and any(self.deltas.fed[SEGMENTS.index(n)] for n in names):
+            raise ValueError("a pose table named here is already fed by an attached camera optimiser")
         segments = [times[n] if n in names else None for n in SEGMENTS]
         shapes = [None if t is None else tuple(t.shape) for t in self.pose_tables]
         self.spline = SplinePoses(spline, segments, shapes, scene.device)
         return self.spline
 
-    def spline_grads(self, pose_grads) -> Dict[str, Tensor]:
+    def spline_grads(self, pose_grads, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
         """``{"ctrl_tangents": [K, 6], "scale": [1]}``: the gradients of the attached spline's parameters from the gradients of the
         pose tables -- ``pose_grads`` as ``pose_grads()`` returns them or as ``GraphedTrainStep.pose_grads`` holds them (entries of
         tables the spline does not feed are ignored).  One launch of fixed-order sums (two calls are bit-equal, control points that
-        no query brackets get exactly zero); the result lives in static tensors that the next call overwrites."""
+        no query brackets get exactly zero); the result lives in static tensors that the next call overwrites, or in ``out``."""
         if self.spline is None:
             raise ValueError("no spline attached (attach_spline)")
         if isinstance(pose_grads, dict):
             pose_grads = [pose_grads.get(k) for k in ("col", "prev", "next")]
-        return self.spline.backward(list(pose_grads))
+        return self.spline.backward(list(pose_grads), out=out)
 
     def spline_pose_tables(self):
         """``(col, prev, nxt)`` of the attached spline as NEW tensors with autograd history back to ``ctrl_tangents`` / ``scale`` (None
@@ -421,6 +426,80 @@ class BatchComposer:
         if self.spline is None:
             raise ValueError("no spline attached (attach_spline)")
         return tuple(self.spline.tables())
+
+    def attach_camera_optimizers(self, col=None, evs=None):
+        """From now on the pose tables come from per-camera optimisers on the composer's device by one launch in front of every
+        ``compose()`` -- ``lse_pose_delta_tables``, the device-side counterpart of ``camera_tables`` -- over static copies of the
+        scene's own poses taken here, so they are always those of the CURRENT ``pose_adjustment``, which the kernel reads in place.
+        ``col``: a ``CameraOptimizer`` over the colour cameras (not with deblur rays: the reference's exist only with the spline,
+        R:lse_nerf/lse_ray_generator.py:103-147).  ``evs``: "consec" pairing -- a ``CameraOptimizer`` for the one event table, which
+        both bundles read (R:lse_nerf/lse_datamanager.py:363-364 applies one optimiser to both); "prevnext" pairing -- a
+        ``PrevNextCamOptimizer`` (``prev_optim`` feeds prev, ``next_optim`` nxt) or a plain ``CameraOptimizer`` (one parameter block
+        feeds both tables, each over its own base poses; its gradient is row(prev) + row(nxt)).
+        ``non_trainable_camera_indices`` becomes a device mask.  An optimiser whose mode is "off" (frozen, or "delayed" before
+        ``turn_on()``) is refused like a spline that is off; so is a table an attached spline feeds already (a spline on "col" beside
+        per-camera optimisers on the event tables is fine).  ``set_poses`` on a fed table and ``compose(tables=...)`` then raise
+        ValueError; ``delta_grads`` / ``delta_pose_tables`` are the way back to the parameters.  Returns the ``DeltaPoses``."""
+        from .cameras import CameraOptimizer, PrevNextCamOptimizer
+        from .pose_delta_dev import DeltaPoses, check_trainable
+        if col is None and evs is None:
+            raise ValueError("attach_camera_optimizers: give col=, evs= or both")
+        scene = self.scene
+        feeds = [None, None, None]
+        if col is not None:
+            if not self.n_col:
+                raise ValueError("this composer has no 'col' pose table")
+            if not isinstance(col, CameraOptimizer):
+                raise ValueError("col= takes a CameraOptimizer (a spline is attached with attach_spline)")
+            if self.G == 4:
+                raise ValueError("deblur rays (G == 4) come from the spline only: a per-camera optimiser has one pose per camera")
+            check_trainable(col, "'col'")
+            if int(col.num_cameras) != scene.col.n_cameras:
+                raise ValueError(f"the 'col' optimiser has {col.num_cameras} cameras, the colour table {scene.col.n_cameras}")
+            feeds[0] = (col, scene.col.cameras.camera_to_worlds)
+        if evs is not None:
+            if not self.n_evs:
+                raise ValueError("this composer has no 'prev' pose table")
+            if isinstance(evs, PrevNextCamOptimizer):
+                if self.consec:
+                    raise ValueError("a PrevNextCamOptimizer needs event_pairing='prevnext': 'consec' has ONE event table")
+                pair = (evs.prev_optim, evs.next_optim)
+            elif isinstance(evs, CameraOptimizer):
+                pair = (evs, None if self.consec else evs)
+            else:
+                raise ValueError("evs= takes a CameraOptimizer or a PrevNextCamOptimizer (a spline is attached with attach_spline)")
+            sets = (scene.evs.cameras, None) if self.consec else (scene.prev_cameras, scene.next_cameras)
+            for i, (o, cams) in enumerate(zip(pair, sets)):
+                if o is None:
+                    continue
+                name = ("prev", "nxt")[i]
+                check_trainable(o, f"'{name}'")
+                if int(o.num_cameras) != len(cams):
+                    raise ValueError(f"the '{name}' optimiser has {o.num_cameras} cameras, the table {len(cams)}")
+                feeds[1 + i] = (o, cams.camera_to_worlds)
+        if self.spline is not None and any(f is not None and sp for f, sp in zip(feeds, self.spline.fed)):
+            raise ValueError("a pose table named here is already fed by the attached spline")
+        shapes = [None if t is None or f is None else tuple(t.shape) for t, f in zip(self.pose_tables, feeds)]
+        self.deltas = DeltaPoses(feeds, shapes, scene.device)
+        return self.deltas
+
+    def delta_grads(self, pose_grads, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+        """``{block: [C, 6]}``: the gradients of the attached ``pose_adjustment`` parameters ("col", "prev", "nxt": a block carries the
+        name of the first table it feeds) from the gradients of the pose tables, as ``spline_grads`` does for the spline.  One launch,
+        no sums across threads (two calls are bit-equal, non-trainable cameras get exactly zero); the result lives in static tensors
+        that the next call overwrites, or in ``out``."""
+        if self.deltas is None:
+            raise ValueError("no camera optimiser attached (attach_camera_optimizers)")
+        if isinstance(pose_grads, dict):
+            pose_grads = [pose_grads.get(k) for k in ("col", "prev", "next")]
+        return self.deltas.backward(list(pose_grads), out=out)
+
+    def delta_pose_tables(self):
+        """``(col, prev, nxt)`` of the attached camera optimisers as NEW tensors with autograd history back to the parameters (None
+        where they feed none): the eager, differentiable twin of what ``compose()`` writes into ``pose_tables``."""
+        if self.deltas is None:
+            raise ValueError("no camera optimiser attached (attach_camera_optimizers)")
+        return tuple(self.deltas.tables())
 
     # -- launches
     def _given(self, indices):
@@ -446,11 +525,16 @@ class BatchComposer:
         if tables is None:
             if self.spline is not None:        # the tables of the spline's current parameters, in stream order in front of the rays
                 self.spline.forward(self.pose_tables)
+            if self.deltas is not None:        # ... and those of the per-camera optimisers' current parameters
+                self.deltas.forward(self.pose_tables)
             self._launch(step, indices)
             return self.bundles, self.batch
         if self.spline is not None:
             raise ValueError("compose(tables=...) with a spline attached: the attached spline feeds the pose tables "
                              "(spline_pose_tables() is their differentiable twin)")
+        if self.deltas is not None:
+            raise ValueError("compose(tables=...) with a camera optimiser attached: the attached optimisers feed the pose tables "
+                             "(delta_pose_tables() is their differentiable twin)")
         given = [t for t, own in zip(tables, self.pose_tables) if own is not None]
         if len(given) != sum(t is not None for t in self.pose_tables) or any(t is None for t in given):
             raise ValueError("tables= takes one tensor per pose table of this composer")

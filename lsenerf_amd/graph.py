@@ -158,11 +158,22 @@ def _run_copies(pairs: list) -> None:
                 d.copy_(s, non_blocking=True)
 
 
+def _adam_state(o: FlatAdam):
+    return o.flat.data.clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), o.step_count
+
+
+def _restore_adam_state(o: FlatAdam, saved) -> None:
+    with torch.no_grad():
+        o.flat.data.copy_(saved[0]); o.exp_avg.copy_(saved[1]); o.exp_avg_sq.copy_(saved[2])
+    o.step_count = saved[3]
+
+
 def capture_body(body, opt: Optional[FlatAdam], estimator, warmup: int = 3, pool=None, stream: Optional[torch.cuda.Stream] = None,
-                 before_capture=None):
+                 before_capture=None, camera_opt: Optional[FlatAdam] = None):
     """Capture ``body()`` -- a zero-argument callable that runs one step on tensors at fixed addresses and synchronises with
     nothing -- into a HIP graph.  Warm-up runs on a side stream as torch.cuda.graph requires (allocator pools, lazy
-    initialisation); the optimizer state those eager runs change is saved and restored, so capturing trains nothing.
+    initialisation); the optimizer state those eager runs change is saved and restored, so capturing trains nothing (``camera_opt``:
+    a second optimizer whose ``step_staged`` the body contains -- the camera parameters' -- treated the same way).
 
     Warm-up and capture run on ONE stream (``stream``, or a new one), and ``before_capture()`` lets the caller drop whatever the
     warm-up runs left behind (losses, outputs: their autograd graphs) before the capture starts: an autograd node that outlives the
@@ -170,29 +181,28 @@ def capture_body(body, opt: Optional[FlatAdam], estimator, warmup: int = 3, pool
     through a node of ANOTHER stream synchronises with that stream inside the capture (_fresh_ray_leaves).  Returns the graph."""
     dev = opt.flat.data.device if opt is not None else estimator.occs.device
     estimator._occ_mean_device()                          # allocate / refresh the device-side alpha cap before the capture
-    saved = (opt.flat.data.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.step_count) if opt is not None else None
+    opts = [o for o in (opt, camera_opt) if o is not None]
+    saved = [_adam_state(o) for o in opts]
     side = stream if stream is not None else torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
         for _ in range(warmup):
-            if opt is not None:
-                opt.prepare_step()
+            for o in opts:
+                o.prepare_step()
             body()
     torch.cuda.current_stream(dev).wait_stream(side)
     estimator.check_deferred_overflow()                   # (the eager warm-up runs' flags; one synchronisation, at construction)
     if before_capture is not None:
         before_capture()
     graph = torch.cuda.CUDAGraph()
-    if opt is not None:
-        opt.prepare_step()
+    for o in opts:
+        o.prepare_step()
     with torch.cuda.graph(graph, pool=pool, stream=side):
         body()
     # (the captured marcher calls OR into the estimator's sticky overflow accumulator at every replay, like the eager ones:
     #  LSEOccGridEstimator._overflow_flag -- read at the occupancy refresh and by check_overflow())
-    if opt is not None:
-        with torch.no_grad():
-            opt.flat.data.copy_(saved[0]); opt.exp_avg.copy_(saved[1]); opt.exp_avg_sq.copy_(saved[2])
-        opt.step_count = saved[3]
+    for o, sv in zip(opts, saved):
+        _restore_adam_state(o, sv)
     return graph
 
 
@@ -232,15 +242,25 @@ class GraphedTrainStep:
     read in place, and ``step.spline_grads`` ({"ctrl_tangents", "scale"}) holds the parameters' gradients after every replay; the
     caller finishes with ``spl.ctrl_tangents.grad = step.spline_grads["ctrl_tangents"]`` (likewise ``scale``) and its own torch
     optimiser step (``ray_grads=False``: only the pose evaluation is captured).  Attach before building the step.
+    Per-camera optimisers (``composer.attach_camera_optimizers``) run the same way through ``lse_pose_delta_tables`` /
+    ``lse_pose_delta_tables_bwd``; ``step.camera_grads`` holds every attached parameter's gradient by name ("ctrl_tangents", "scale",
+    and the ``pose_adjustment`` blocks "col", "prev", "nxt").
+    ``camera_opt=`` (a ``FlatAdam`` over a ``FlatParams`` of exactly the attached parameters, built BEFORE attaching -- ``FlatParams``
+    re-points ``.data``; with ``composer=`` and ``ray_grads=True``): the two backward kernels write straight into the ``.grad`` views
+    of ``camera_opt.flat`` and the body ends with ``camera_opt.step_staged()`` behind ``opt.step_staged()``, so a replay leaves
+    nothing to the host.  A camera no ray of the step touched gets gradient exactly zero; its moments decay like torch's dense Adam.
     Not combined with ``prefetch_march`` (ValueError)."""
 
     def __init__(self, model, opt: FlatAdam, col: Optional[RayBundle] = None, prev: Optional[RayBundle] = None,
                  nxt: Optional[RayBundle] = None, batch: Optional[Dict[str, object]] = None, ray_grads: bool = False,
                  jitter: str = "graph", warmup: int = 3, grad_scale: float = 1.0, prefetch_march: bool = False,
-                 prefetch_fork: str = "hash_bwd", optimizer_in_graph: bool = True, composer=None):
+                 prefetch_fork: str = "hash_bwd", optimizer_in_graph: bool = True, composer=None,
+                 camera_opt: Optional[FlatAdam] = None):
         assert jitter in ("graph", "input")
         assert model.training, "the captured step is the training step"
         self.composer = composer
+        if camera_opt is not None and composer is None:
+            raise ValueError("camera_opt= belongs to a step built with composer=: the camera parameters feed the composer's pose tables")
         if composer is not None:
             if prefetch_march:
                 raise ValueError("composer= with prefetch_march=True is not supported: the marcher of the next step would need the "
@@ -249,6 +269,8 @@ class GraphedTrainStep:
                 raise ValueError("with composer= the bundles and the batch are the composer's own buffers: pass none")
         elif batch is None:
             raise ValueError("example bundles and a batch fix the composition of the step (or pass composer=)")
+        self.camera_opt = camera_opt
+        self._camera_out = self._camera_grad_views(composer, bool(ray_grads)) if camera_opt is not None else None
         self.model, self.opt, self.grad_scale = model, opt, grad_scale
         # False: the graph ends with the backward pass and the caller finishes the step -- data parallel: all-reduce of
         # opt.flat.grad (lsenerf_amd.dist), then opt.step(grad_scale=1 / world) -- two more launches instead of ~25
@@ -267,6 +289,8 @@ class GraphedTrainStep:
         self.pose_grads: Optional[Dict[str, Optional[Tensor]]] = None
         # ... and with a spline attached to the composer: the gradients of its parameters {"ctrl_tangents", "scale"}
         self.spline_grads: Optional[Dict[str, Tensor]] = None
+        # ... and of everything attached (spline and / or per-camera optimisers), by name; with camera_opt= these ARE its .grad views
+        self.camera_grads: Optional[Dict[str, Tensor]] = None
         n_total = sum(len(b) for b in (self.col, self.prev, self.nxt) if b is not None)
         dev = opt.flat.data.device
         self.jitter = torch.rand(n_total, device=dev) if jitter == "input" else None
@@ -282,7 +306,7 @@ class GraphedTrainStep:
             # (the warm-up runs advance the composer's device step counter like any eager compose(): put it back, in stream order)
             k0 = composer.step_dev.clone() if composer is not None else None
             self.graph = capture_body(self._body, opt, model.occupancy_grid, warmup, stream=self._capture_stream,
-                                      before_capture=self._drop_run)
+                                      before_capture=self._drop_run, camera_opt=camera_opt)
             if composer is not None:
                 with torch.no_grad():
                     composer.step_dev.copy_(k0)
@@ -319,6 +343,32 @@ class GraphedTrainStep:
                 out[k] = v.detach().clone() if torch.is_tensor(v) else v
         return out
 
+    def _camera_grad_views(self, composer, ray_grads: bool):
+        """The checks of ``camera_opt=`` and where the two backward kernels write: ``(spline out, delta out)``, the ``.grad`` views of
+        ``camera_opt.flat`` by the names the backward calls use."""
+        co = self.camera_opt
+        if not ray_grads:
+            raise ValueError("camera_opt= needs ray_grads=True: without ray gradients the camera parameters receive none")
+        spline, deltas = composer.spline, composer.deltas
+        for attached in (spline, deltas):               # (a FlatParams built AFTER attaching has moved the parameters: refuse here,
+            if attached is not None:                    #  before the model is switched to deferred counts)
+                attached._current_desc()
+        named = []
+        if spline is not None:
+            named += [("spline", "ctrl_tangents", spline.spline.ctrl_tangents), ("spline", "scale", spline.spline.scale)]
+        if deltas is not None:
+            named += [("deltas", name, p) for name, p in zip(deltas.blocks, deltas.parameters())]
+        if not named:
+            raise ValueError("camera_opt= with nothing attached to the composer (attach_spline / attach_camera_optimizers)")
+        if sorted(p.data_ptr() for _, _, p in named) != sorted(p.data_ptr() for p in co.flat.params):
+            raise ValueError("camera_opt must cover exactly the parameters attached to the composer (ctrl_tangents + scale and / or the "
+                             "pose_adjustments): build FlatParams over them, then attach, then build the step")
+        co.zero_grad()                                  # (makes every .grad the view of the flat gradient again)
+        out = {"spline": {}, "deltas": {}}
+        for kind, name, p in named:
+            out[kind][name] = p.grad
+        return out["spline"] or None, out["deltas"] or None
+
     def _drop_run(self):
         """Forget the last run of ``_body`` (capture_body calls this between the warm-up runs and the capture): its losses and
         outputs hold that run's autograd graph, and with it autograd nodes bound to the warm-up."""
@@ -342,11 +392,20 @@ class GraphedTrainStep:
             with torch.no_grad():
                 g = self.composer.pose_grads((o.grad, d.grad))
             self.pose_grads = dict(zip(("col", "prev", "next"), g))
+            s_out, d_out = self._camera_out if self._camera_out is not None else (None, None)
+            cam = {}
             if self.composer.spline is not None:                   # d pose tables -> d ctrl_tangents, d scale (static tensors too)
                 with torch.no_grad():
-                    self.spline_grads = self.composer.spline_grads(g)
+                    self.spline_grads = self.composer.spline_grads(g, out=s_out)
+                cam.update(self.spline_grads)
+            if self.composer.deltas is not None:  # d pose tables -> d pose_adjustment of every block
+                with torch.no_grad():
+                    cam.update(self.composer.delta_grads(g, out=d_out))
+            self.camera_grads = cam or None
         if self.optimizer_in_graph:
             self.opt.step_staged(self.grad_scale)
+        if self.camera_opt is not None:                            # (every element of its gradient was written above; the padding is 0)
+            self.camera_opt.step_staged()
         self.losses, self.outputs = losses, out
 
     def _body_prefetch(self, x: int):
@@ -467,6 +526,8 @@ class GraphedTrainStep:
             raise ValueError('this step draws its jitter inside the graph; build it with jitter="input" to pass one')
         if self.optimizer_in_graph:
             self.opt.prepare_step()
+        if self.camera_opt is not None:
+            self.camera_opt.prepare_step()
         self.graph.replay()
         self.replays += 1
         return self.losses

@@ -146,6 +146,7 @@ class SplinePoses:
         if any(k == "evs" for k in plan.kinds) and spline.dM is None:
             raise ValueError("an 'evs' table needs the spline's dM")
         self._params = self._check_params()
+        self._ptrs = tuple(p.data_ptr() for p in self._params)     # (the addresses themselves: re-pointing .data keeps the Parameter)
         self._desc = _lib.SplineDesc(
             n_ctrl=plan.n_ctrl, n_query=(ctypes.c_int32 * 3)(*plan.n_query), evs=(ctypes.c_int32 * 3)(*[int(k == "evs") for k in plan.kinds]),
             csr_len=int(plan.csr_query.numel()), dM=(ctypes.c_float * 16)(*[float(v) for v in dM.detach().cpu().float().reshape(-1)]),
@@ -164,7 +165,7 @@ class SplinePoses:
         """The kernels read the parameters where they were at attach time (a captured step keeps reading there): a spline whose
         parameters were moved or replaced since (``.to()``, a loaded checkpoint that swaps ``.data``) must be attached again."""
         ct, sc = self.spline.ctrl_tangents, self.spline.scale
-        if ct.data_ptr() != self._params[0].data_ptr() or sc.data_ptr() != self._params[1].data_ptr():
+        if (ct.data_ptr(), sc.data_ptr()) != self._ptrs:
             raise ValueError("the spline's parameters have moved since attach_spline(): attach again (and rebuild a captured step)")
         return self._desc
 
@@ -189,11 +190,18 @@ class SplinePoses:
         t = self._checked(tables, "lse_spline_poses")
         _lib.call("lse_spline_poses", ctypes.byref(self._current_desc()), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _stream())
 
-    def backward(self, d_tables: Sequence[Optional[Tensor]], static: bool = True) -> Dict[str, Tensor]:
+    def backward(self, d_tables: Sequence[Optional[Tensor]], static: bool = True, out: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
         """``{"ctrl_tangents": [K, 6], "scale": [1]}`` from the gradients of the fed tables; ``static``: in the tensors of
-        ``self.grads``, which the next call overwrites."""
+        ``self.grads``, which the next call overwrites; ``out``: in the caller's tensors instead (the ``.grad`` views of a flat
+        optimiser buffer: no copy)."""
         g = self._checked(d_tables, "lse_spline_poses_bwd")
-        out = self.grads if static else {k: torch.empty_like(v) for k, v in self.grads.items()}
+        if out is not None:
+            for k, v in self.grads.items():
+                t = out.get(k)
+                if t is None or tuple(t.shape) != tuple(v.shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                    raise ValueError(f"lse_spline_poses_bwd: out['{k}'] must be a contiguous float32 {tuple(v.shape)} tensor on {self.device}")
+        else:
+            out = self.grads if static else {k: torch.empty_like(v) for k, v in self.grads.items()}
         _lib.call("lse_spline_poses_bwd", ctypes.byref(self._current_desc()), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
                   _ptr(out["ctrl_tangents"]), _ptr(out["scale"]), _stream())
         return out

@@ -9,6 +9,13 @@
   (c) "spline"       (b) with the spline ATTACHED (``composer.attach_spline``): the graph starts with ``lse_spline_poses``, which reads
                      the spline's parameters in place -- nothing runs in front of a replay.  Feeds the table (b) feeds (colour).
                      Default composition only.
+  (c+) "spline + torch Adam"  (c) with ``ray_grads=True``, followed per step by what a caller does without ``camera_opt=``: assign
+                     ``step.spline_grads`` to ``.grad``, ``torch.optim.Adam`` (lr 1e-3, eps 1e-15) and its exponential decay;
+  (d) "camera_opt"   (c) with ``ray_grads=True`` and ``camera_opt=``: the spline backward writes into the flat gradient of a
+                     ``FlatAdam`` over ``ctrl_tangents`` + ``scale`` whose update is the last launch of the graph.
+  At config 2 the same pair for per-camera optimisers (a ``CameraOptimizer`` on the colour and on the event cameras):
+  "set_poses" = ``camera_tables`` + ``set_poses`` in front of the replay, torch autograd over ``step.pose_grads`` and torch Adam behind
+  it; "attached" = ``attach_camera_optimizers`` + ``camera_opt=``.
 All at the reference's default composition (579 x 4 + 597 + 597 rays, deblur colour bundle, poses from the spline) and at config 2
 (2318 + 597 + 597), on a synthetic resident scene (32 colour images 480 x 640, 64 int8 event frames 260 x 346, cameras on a
 sphere around the [-1, 1]^3 box).  Per route: ms per step (median of the per-step device-event intervals, 100 steps after 20
@@ -19,13 +26,21 @@ warm-up ones) and host ms per step (time.perf_counter around the loop, no synchr
     python tools/bench_compose.py analyze DIR_PRECOMPOSED_1 DIR_PRECOMPOSED_2 DIR_COMPOSER
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_compose.py trace composer_poses|spline
     python tools/bench_compose.py analyze_spline DIR_COMPOSER_POSES_1 DIR_COMPOSER_POSES_2 DIR_SPLINE
+    python tools/bench_compose.py camera                     # (c+), (d) and the config-2 pair: one JSON line each
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_compose.py trace spline|spline_adam
+    python tools/bench_compose.py analyze_camera DIR_SPLINE_1 DIR_SPLINE_2 DIR_SPLINE_ADAM
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_compose.py trace cfg2_set_poses|cfg2_attached cfg2
+    python tools/bench_compose.py analyze_cfg2 DIR_SET_POSES_1 DIR_SET_POSES_2 DIR_ATTACHED
 
 ``trace``: replays only -- the composer step, or the parent's graphed step fed the SAME batches composed beforehand -- behind a
 0.5 s pause that marks the start of the timed region in the kernel trace.  ``analyze``: summed kernel time per step of the three traces, the time of the two
 composer kernels, and the bar of the change -- (b) may exceed the mean of the two precomposed runs by no more than the composer
 kernels' own time plus twice the spread between those two runs.  ``trace composer_poses`` / ``trace spline``: routes (b) / (c) at the
 default composition with ``ray_grads=True`` ((c) then ends with ``lse_spline_poses_bwd``); ``analyze_spline``: the same bar with the two
-spline kernels as the change's own."""
+spline kernels as the change's own.  ``trace spline_adam``: route (d); ``analyze_camera``: the same bar against (c) with the camera
+parameters' Adam launches as the change's own (the field's Adam runs the same two kernels: of every pair in a step the second launch
+is the camera's).  ``analyze_cfg2``: the attached route against the set_poses route, own kernels = the two pose-delta kernels and the
+camera Adam."""
 import csv
 import glob
 import json
@@ -38,10 +53,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 STEPS, WARMUP = 100, 20
 COMPOSE_KERNELS = ("compose_kernel", "advance_kernel", "rays_bwd_kernel")
 SPLINE_KERNELS = ("spline_fwd_kernel", "spline_bwd_kernel")
+DELTA_KERNELS = ("pose_delta_fwd_kernel", "pose_delta_bwd_kernel")
+ADAM_KERNELS = ("adam_schedule_kernel", "adam_kernel")
+CAMERA_ADAM = tuple("camera " + k for k in ADAM_KERNELS)
 
 
-def analyze(dirs, own_kernels=COMPOSE_KERNELS):
-    def load(d):
+def analyze(dirs, own_kernels=COMPOSE_KERNELS, camera_adam=False):
+    def load(d, split_adam=False):
         rows = []
         for f in glob.glob(f"{d}/**/*kernel_trace.csv", recursive=True):
             for r in csv.DictReader(open(f)):
@@ -51,12 +69,19 @@ def analyze(dirs, own_kernels=COMPOSE_KERNELS):
         last_gap = max(i for i in range(1, len(rows)) if rows[i][0] - rows[i - 1][1] > 200e6)     # the 0.5 s pause
         timed = rows[last_gap:]
         per = {}
+        seen = {k: 0 for k in ADAM_KERNELS}
         for s, e, name in timed:
             key = next((k for k in own_kernels if k in name), "other")
+            adam = next((k for k in ADAM_KERNELS if k in name), None) if split_adam else None
+            if adam is not None:        # field's, camera's, field's, ...: the camera's update is the second of every pair
+                seen[adam] += 1
+                key = "camera " + adam if seen[adam] % 2 == 0 else "other"
             tot, n = per.get(key, (0, 0))
             per[key] = (tot + (e - s), n + 1)
+        if split_adam:
+            assert all(n == 2 * STEPS for n in seen.values()), f"{d}: expected two Adam pairs per step, saw {seen}"
         return per
-    pre1, pre2, comp = (load(d) for d in dirs)
+    pre1, pre2, comp = load(dirs[0]), load(dirs[1]), load(dirs[2], split_adam=camera_adam)
     steps = STEPS
     total = lambda per: sum(t for t, _ in per.values()) / steps / 1e6
     a, b, c = total(pre1), total(pre2), total(comp)
@@ -74,11 +99,15 @@ def analyze(dirs, own_kernels=COMPOSE_KERNELS):
 if len(sys.argv) > 1 and sys.argv[1] in ("analyze", "analyze_spline"):
     analyze(sys.argv[2:5], COMPOSE_KERNELS if sys.argv[1] == "analyze" else SPLINE_KERNELS)
     sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] in ("analyze_camera", "analyze_cfg2"):
+    # (the set_poses route of config 2 has ONE Adam pair per step, the field's: only the last directory is split by parity)
+    analyze(sys.argv[2:5], CAMERA_ADAM if sys.argv[1] == "analyze_camera" else DELTA_KERNELS + CAMERA_ADAM, camera_adam=True)
+    sys.exit(0)
 
 import numpy as np
 import torch
 from lsenerf_amd import LSENeRFModel, LSENeRFModelConfig, RayBundle, cameras as cam
-from lsenerf_amd.data import BatchComposer, DeviceScene, batch_split, spline_tables
+from lsenerf_amd.data import BatchComposer, DeviceScene, batch_split, camera_tables, spline_tables
 from lsenerf_amd.graph import GraphedTrainStep
 from lsenerf_amd.optim import FlatAdam, FlatParams
 
@@ -223,7 +252,90 @@ def run(kind):
                       "warmup": WARMUP, "torch_route": res_a, "composer": res_b, **res_c}), flush=True)
 
 
+CAM_LR, CAM_LR_FINAL, CAM_STEPS = 1e-3, 1e-4, 5000       # the reference's camera_opt group (R:lse_nerf/lse_config.py:29-38)
+
+
+def torch_camera_adam(params):
+    adam = torch.optim.Adam(params, lr=CAM_LR, eps=1e-15)
+    return adam, torch.optim.lr_scheduler.ExponentialLR(adam, gamma=(CAM_LR_FINAL / CAM_LR) ** (1.0 / CAM_STEPS))
+
+
+def flat_camera_adam(params):
+    return FlatAdam(FlatParams(params), lr=CAM_LR, eps=1e-15, lr_final=CAM_LR_FINAL, max_steps=CAM_STEPS)
+
+
+def camera_optimizers(scene):
+    mk = lambda n: cam.CameraOptimizerConfig(mode="SO3xR3").setup(num_cameras=n, device=dev)
+    return mk(scene.col.n_cameras), mk(scene.evs.n_cameras)
+
+
+def camera_route(name, kind="default"):
+    """``(fn, step)`` of one camera-optimiser route on a freshly built model: "spline_torch_adam" (c+), "spline_adam" (d) at the default
+    composition; "cfg2_set_poses", "cfg2_attached" at config 2."""
+    model, opt, scene, n_col, n_evs, spl = build(kind)
+    comp = BatchComposer(scene, n_col, n_evs, deblur=spl is not None, seed=0, num_embd=N_EMB)
+    if name == "spline_torch_adam":
+        comp.attach_spline(spl, tables=("col",))
+        step = GraphedTrainStep(model, opt, composer=comp, ray_grads=True)
+        adam, sched = torch_camera_adam([spl.ctrl_tangents, spl.scale])
+
+        def fn():
+            step()
+            spl.ctrl_tangents.grad = step.spline_grads["ctrl_tangents"]
+            spl.scale.grad = step.spline_grads["scale"]
+            adam.step()
+            sched.step()
+    elif name == "spline_adam":
+        cam_opt = flat_camera_adam([spl.ctrl_tangents, spl.scale])            # (FlatParams re-points .data: before attaching)
+        comp.attach_spline(spl, tables=("col",))
+        step = fn = GraphedTrainStep(model, opt, composer=comp, ray_grads=True, camera_opt=cam_opt)
+    elif name == "cfg2_set_poses":
+        col_o, evs_o = camera_optimizers(scene)
+        step = GraphedTrainStep(model, opt, composer=comp, ray_grads=True)
+        adam, sched = torch_camera_adam([col_o.pose_adjustment, evs_o.pose_adjustment])
+
+        def fn():
+            tabs = [camera_tables(scene.col.cameras, col_o), camera_tables(scene.evs.cameras, evs_o)]
+            comp.set_poses(col=tabs[0].detach(), prev=tabs[1].detach())
+            step()
+            adam.zero_grad(set_to_none=True)
+            torch.autograd.backward(tabs, [step.pose_grads["col"].reshape(-1, 3, 4), step.pose_grads["prev"]])
+            adam.step()
+            sched.step()
+    else:
+        assert name == "cfg2_attached", name
+        col_o, evs_o = camera_optimizers(scene)
+        cam_opt = flat_camera_adam([col_o.pose_adjustment, evs_o.pose_adjustment])
+        comp.attach_camera_optimizers(col=col_o, evs=evs_o)
+        step = fn = GraphedTrainStep(model, opt, composer=comp, ray_grads=True, camera_opt=cam_opt)
+    return fn, step
+
+
+def run_camera():
+    for kind, names in (("default", ("spline_torch_adam", "spline_adam")), ("cfg2", ("cfg2_set_poses", "cfg2_attached"))):
+        res = {}
+        for name in names:
+            fn, step = camera_route(name, kind)
+            res[name] = timed(fn)
+            step.check_overflow()
+            step.close()
+            del fn, step
+        print(json.dumps({"composition": kind, "camera_optimiser_routes": res, "steps": STEPS, "warmup": WARMUP}), flush=True)
+
+
 def trace(mode, kind):
+    if mode in ("spline_adam", "cfg2_set_poses", "cfg2_attached"):
+        fn, step = camera_route(mode, kind)
+        for _ in range(WARMUP):
+            fn()
+        torch.cuda.synchronize()
+        time.sleep(0.5)
+        for _ in range(STEPS):
+            fn()
+        torch.cuda.synchronize()
+        step.check_overflow()
+        print(json.dumps({"trace": mode, "composition": kind, "steps": STEPS}), flush=True)
+        return
     model, opt, scene, n_col, n_evs, spl = build(kind)
     comp = BatchComposer(scene, n_col, n_evs, deblur=spl is not None, seed=0, num_embd=N_EMB)
     if mode in ("composer_poses", "spline"):
@@ -273,6 +385,8 @@ def trace(mode, kind):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "trace":
         trace(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "default")
+    elif len(sys.argv) > 1 and sys.argv[1] == "camera":
+        run_camera()
     else:
         for kind in ("default", "cfg2"):
             run(kind)
