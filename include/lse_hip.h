@@ -169,7 +169,7 @@ int lse_compact_samples(const uint8_t *mask, const int64_t *packed_info, const i
 /* ---- field ------------------------------------------------------------------------------------------- */
 
 /* Device-side sample count `n_dev` (nullable) of the PER-SAMPLE entry points
- *     lse_positions_fwd / _bwd, lse_hash_fwd, lse_hash_bwd / _levels / _ex, lse_mlp_fwd / _fwd_pair / _bwd.
+ *     lse_positions_fwd / _bwd, lse_hash_fwd, lse_hash_bwd / _levels / _ex / _input, lse_mlp_fwd / _fwd_pair / _bwd.
  * The sampler knows the number of packed samples only on the device (lse_pack_info_from_counts); reading it back costs a host
  * synchronisation per sampler call, twice per step with the visibility pre-pass.  With n_dev != NULL the `n` argument is a
  * CAPACITY -- buffer extents, level strides and the launch grid are sized by it -- and every kernel clamps it to the int64 that
@@ -262,6 +262,14 @@ int64_t lse_hash_bwd_workspace_bytes(const lse_grid_desc *desc, const lse_hash_b
 int lse_hash_bwd_ex(const lse_grid_desc *desc, const float *x01, const float *dy, const float *table, float *dtable,
                     float *dx, int32_t dx_accumulate, int32_t level_begin, int32_t level_end, int64_t n,
                     const int64_t *n_dev, const lse_hash_bwd_opts *opts /* NULL = defaults */, lse_stream_t stream);
+
+/* tcnn kernel_grid_backward_input alone, for a FROZEN table (test-time refinement): dx[N,3] = d(loss)/d(x01) from dy[L][N][2]
+ * (level stride n, as lse_hash_bwd_ex reads it), overwritten.  The cell is the one lse_hash_fwd picks, out-of-range positions
+ * included.  A pure gather: no table gradient, no workspace, no atomics; the levels are summed in a fixed order, so two calls
+ * give the same bits.  Serves every geometry lse_hash_fwd serves (no level alignment needed).  Rows at or beyond the count are
+ * not written. */
+int lse_hash_bwd_input(const lse_grid_desc *desc, const float *x01, const float *dy, const float *table, float *dx,
+                       int64_t n, const int64_t *n_dev, lse_stream_t stream);
 
 /* fused MLP forward on the matrix cores (f32 MFMA, or bf16 MFMA on three-piece operands with the same error bound:
  * lse_mlp_desc.arith).  row_bias[R,width] (nullable) is added to layer-0 pre-activations of sample i

@@ -138,6 +138,7 @@ SIGNATURES = {
     "lse_hash_bwd": [POINTER(GridDesc), P, P, P, P, P, I64, P, P],
     "lse_hash_bwd_levels": [POINTER(GridDesc), P, P, P, P, P, I32, I32, I32, I64, P, P],
     "lse_hash_bwd_ex": [POINTER(GridDesc), P, P, P, P, P, I32, I32, I32, I64, P, POINTER(HashBwdOpts), P],
+    "lse_hash_bwd_input": [POINTER(GridDesc), P, P, P, P, I64, P, P],
     "lse_mlp_fwd": [POINTER(MlpDesc), P, P, P, P, P, I32, P, I32, P, P, F32, I64, P, P],
     "lse_mlp_fwd_pair": [POINTER(MlpDesc), P, P, P, F32, POINTER(MlpDesc), P, P, P, P, P, P, I32, I64, P, P],
     "lse_mlp_bwd": [POINTER(MlpDesc), P, P, P, I32, P, I32, P, P, P, F32, P, P, P, P, P, P, P, P, I64, P, P],

@@ -15,6 +15,8 @@
 //     0.85 ms against 0.60 ms; tools/hash_fwd_level_cost.py.)  Placement affects speed only, never results.
 //   * backward: 16 lanes per sample (one per corner x feature) with run-length pre-accumulation, see hash_bwd_kernel;
 //     table gradients are f32 global atomics (memory-side on gfx950, so no level/XCD affinity is attempted there).
+//   * backward of a FROZEN table (lse_hash_bwd_input): d(x) alone, the forward's lane mapping with a level loop per workgroup --
+//     a gather without atomics, see hash_bwd_input_kernel.
 #include "common.h"
 #include <stdlib.h>
 
@@ -1448,6 +1450,81 @@ __global__ __launch_bounds__(256) void hash_bwd_reduce_replicas_kernel(float *__
     }
 }
 
+// Input-only backward (frozen table): dx[i] = sum_l sum_f dy[l][i][f] * d y[l][i][f] / d x[i], nothing else.  A pure gather -- no
+// table gradient, no atomics, no LDS -- with the forward's lane mapping (lane = sample, kFwdItems samples per lane, so 32 gathers
+// are in flight per lane) and the forward's cell (pos_fract, corner_indices: out-of-range positions wrap the same way).
+// Schedule: ONE pass; a workgroup owns kFwdThreads * kFwdItems samples, walks the levels 0 .. L-1 and keeps the three sums in
+// registers, so dx is written once and the level order of the sum is fixed (two runs give the same bits).  The workgroups drift
+// apart, so an XCD's L2 serves several level tables at once and the fine levels come from the Infinity Cache: 0.60 / 0.70 ms for
+// 4096 x 1024 samples (inside-box / sphere rays) against the forward's 0.44 / 0.48.  That gather traffic is the bound -- 1 to 4
+// samples per lane (2 to 8 waves per SIMD) and a factored form with half the multiply-adds all land within 3 % on the sphere rays.
+// The forward's level-major dispatch keeps each L2 on one table but has to write per-level partial dx and sum them in a second
+// pass: 0.93 / 0.96 ms, dropped (DESIGN_HISTORY.md).
+__global__ __launch_bounds__(kFwdThreads) void hash_bwd_input_kernel(GridParams g, const float *__restrict__ x,
+                                                                     const float2 *__restrict__ dy,
+                                                                     const float2 *__restrict__ table, float *__restrict__ dx,
+                                                                     int64_t n_cap, const int64_t *__restrict__ n_dev)
+{
+    const int64_t n = lse::clamp_count(n_cap, n_dev);      // n_cap stays the level stride of dy
+    const int64_t base = (int64_t)blockIdx.x * (kFwdThreads * kFwdItems) + threadIdx.x;
+    if ((int64_t)blockIdx.x * (kFwdThreads * kFwdItems) >= n) return;
+
+    float px[kFwdItems][3], acc[kFwdItems][3];
+    int64_t si[kFwdItems];
+    bool valid[kFwdItems];
+#pragma unroll
+    for (int it = 0; it < kFwdItems; ++it) {
+        const int64_t i = base + (int64_t)it * kFwdThreads;
+        valid[it] = i < n;
+        si[it] = valid[it] ? i : (n - 1);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            px[it][d] = x[si[it] * 3 + d];
+            acc[it][d] = 0.f;
+        }
+    }
+    for (int l = 0; l < g.n_levels; ++l) {
+        const LevelInfo li = level_info(g, l);
+        const float2 *__restrict__ tab = table + li.offset;
+        const float2 *__restrict__ dyl = dy + (int64_t)l * n_cap;
+        float w[kFwdItems][3];
+        float2 gy[kFwdItems], v[kFwdItems][8];
+#pragma unroll
+        for (int it = 0; it < kFwdItems; ++it) {
+            uint32_t p[3], idx[8];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) pos_fract(px[it][d], li.scale, w[it][d], p[d]);
+            corner_indices(li, p[0], p[1], p[2], idx);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[it][c] = tab[idx[c]];
+            gy[it] = dyl[si[it]];
+        }
+#pragma unroll
+        for (int it = 0; it < kFwdItems; ++it) {
+            const float w0 = w[it][0], w1 = w[it][1], w2 = w[it][2];
+            float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float sx = (c & 1) ? w0 : 1.f - w0, sy = (c & 2) ? w1 : 1.f - w1, sz = (c & 4) ? w2 : 1.f - w2;
+                const float t = gy[it].x * v[it][c].x + gy[it].y * v[it][c].y;
+                d0 += ((c & 1) ? t : -t) * (sy * sz);
+                d1 += ((c & 2) ? t : -t) * (sx * sz);
+                d2 += ((c & 4) ? t : -t) * (sx * sy);
+            }
+            acc[it][0] += li.scale * d0;
+            acc[it][1] += li.scale * d1;
+            acc[it][2] += li.scale * d2;
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < kFwdItems; ++it)
+        if (valid[it]) {
+            dx[si[it] * 3 + 0] = acc[it][0];
+            dx[si[it] * 3 + 1] = acc[it][1];
+            dx[si[it] * 3 + 2] = acc[it][2];
+        }
+}
+
 int fill_params(const lse_grid_desc *desc, GridParams &g, const char *who)
 {
     LSE_REQUIRE(desc, "%s: null desc", who);
@@ -1514,6 +1591,23 @@ extern "C" int lse_hash_fwd(const lse_grid_desc *desc, const float *x01, const f
                        reinterpret_cast<const float2 *>(table), reinterpret_cast<float2 *>(y), n, chunks, mapping,
                        n_dev, lds_levels);
     return lse::check_launch("lse_hash_fwd");
+}
+
+extern "C" int lse_hash_bwd_input(const lse_grid_desc *desc, const float *x01, const float *dy, const float *table,
+                                  float *dx, int64_t n, const int64_t *n_dev, lse_stream_t stream)
+{
+    GridParams g;
+    int rc = fill_params(desc, g, "lse_hash_bwd_input");
+    if (rc) return rc;
+    LSE_REQUIRE(n >= 0, "lse_hash_bwd_input: n < 0");
+    if (n == 0) return LSE_OK;
+    LSE_REQUIRE(x01 && dy && table && dx, "lse_hash_bwd_input: null pointer");
+    const int64_t chunks = (n + kFwdThreads * kFwdItems - 1) / (kFwdThreads * kFwdItems);
+    LSE_REQUIRE(chunks < (1ll << 31), "lse_hash_bwd_input: grid too large");
+    hipStream_t st = lse::as_stream(stream);
+    hipLaunchKernelGGL(hash_bwd_input_kernel, dim3((unsigned)chunks), dim3(kFwdThreads), 0, st, g, x01,
+                       reinterpret_cast<const float2 *>(dy), reinterpret_cast<const float2 *>(table), dx, n, n_dev);
+    return lse::check_launch("lse_hash_bwd_input");
 }
 
 extern "C" void lse_hash_bwd_default_opts(lse_hash_bwd_opts *o)

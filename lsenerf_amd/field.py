@@ -585,6 +585,18 @@ class LSEField(nn.Module):
         assert emb.test_emb is not None, "for deblur pretrain test only! need to init test_emb!"
         return emb.test_emb.weight, torch.zeros(n_rays, dtype=torch.int32, device=device)
 
+    def _ray_emb(self, metadata, camera_indices, n_rays: int, device):
+        """(table, idx) of the appearance embedding for ``n_rays`` rays.  Training mode reads the training table by the rays' ids --
+        unless ``gbconfig.IS_EVAL`` is set: the reference's ``forward`` then returns ``get_test_emb``
+        (R:lse_nerf/lse_embeddings.py:36-38), which is how a refinement run reaches the ``test_emb`` row it fits."""
+        if self.embedding_appearance is None:
+            return None, None
+        from .model import gbconfig
+        if self.training and not gbconfig.IS_EVAL:
+            return self._train_emb_table(), self.embedding_appearance.ray_indices(metadata, camera_indices, n_rays,
+                                                                                  device).contiguous()
+        return self._eval_emb(n_rays, device)
+
     # -- reference interface ---------------------------------------------------------------------------
     @staticmethod
     def _packed_view(ray_samples):
@@ -645,13 +657,7 @@ class LSEField(nn.Module):
         else:   # stock RaySamples: arbitrary per-sample directions / ids -- every sample is its own "ray"
             dirs, ridx, pinfo, n_rays = fr.directions.reshape(-1, 3).contiguous(), None, None, n
             meta, cams = (getattr(ray_samples, "metadata", None) or {}), ray_samples.camera_indices
-        if self.embedding_appearance is None:
-            table, eidx = None, None
-        elif self.training:
-            table = self._train_emb_table()
-            eidx = self.embedding_appearance.ray_indices(meta, cams, n_rays, dev).contiguous()
-        else:
-            table, eidx = self._eval_emb(n_rays, dev)
+        table, eidx = self._ray_emb(meta, cams, n_rays, dev)
         outputs = self._side_heads(ray_samples, density_embedding, n, ridx)
         out16 = self.rgb_packed(h, dirs, eidx, ridx, pinfo, table)
         rgb = out16[:, :3].view(*fr.directions.shape[:-1], 3)

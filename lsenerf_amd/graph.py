@@ -249,15 +249,26 @@ class GraphedTrainStep:
     re-points ``.data``; with ``composer=`` and ``ray_grads=True``): the two backward kernels write straight into the ``.grad`` views
     of ``camera_opt.flat`` and the body ends with ``camera_opt.step_staged()`` behind ``opt.step_staged()``, so a replay leaves
     nothing to the host.  A camera no ray of the step touched gets gradient exactly zero; its moments decay like torch's dense Adam.
-    Not combined with ``prefetch_march`` (ValueError)."""
+    Not combined with ``prefetch_march`` (ValueError).
+    Frozen field (``LSENeRFModel.freeze_field``; test-time refinement): ``opt`` is a ``FlatAdam`` over the parameters ``freeze_field``
+    left trainable (the appearance embedding), or ``None`` when only the cameras are optimised (together with ``camera_opt=``,
+    or with ``ray_grads=True`` for a pose optimiser outside the graph) -- the step then holds no field optimiser at all.  The hash
+    backward of a frozen table is the input gradient alone (or nothing, without ray gradients) and no frozen parameter receives a
+    gradient.  ``prefetch_march`` with a frozen table: ValueError."""
 
-    def __init__(self, model, opt: FlatAdam, col: Optional[RayBundle] = None, prev: Optional[RayBundle] = None,
+    def __init__(self, model, opt: Optional[FlatAdam], col: Optional[RayBundle] = None, prev: Optional[RayBundle] = None,
                  nxt: Optional[RayBundle] = None, batch: Optional[Dict[str, object]] = None, ray_grads: bool = False,
                  jitter: str = "graph", warmup: int = 3, grad_scale: float = 1.0, prefetch_march: bool = False,
                  prefetch_fork: str = "hash_bwd", optimizer_in_graph: bool = True, composer=None,
                  camera_opt: Optional[FlatAdam] = None):
         assert jitter in ("graph", "input")
         assert model.training, "the captured step is the training step"
+        if opt is None and camera_opt is None and not ray_grads:
+            raise ValueError("opt=None is the camera-only step of a frozen field: it needs camera_opt= (with composer=), or "
+                             "ray_grads=True for a pose optimiser outside the graph -- otherwise the step trains nothing")
+        if prefetch_march and not model.field.mlp_base_grid.params.requires_grad:
+            raise ValueError("prefetch_march=True with a frozen hash table is not supported: the side stream forks off in front of "
+                             "the table-gradient scatter, which a frozen table does not run")
         self.composer = composer
         if camera_opt is not None and composer is None:
             raise ValueError("camera_opt= belongs to a step built with composer=: the camera parameters feed the composer's pose tables")
@@ -274,7 +285,8 @@ class GraphedTrainStep:
         self.model, self.opt, self.grad_scale = model, opt, grad_scale
         # False: the graph ends with the backward pass and the caller finishes the step -- data parallel: all-reduce of
         # opt.flat.grad (lsenerf_amd.dist), then opt.step(grad_scale=1 / world) -- two more launches instead of ~25
-        self.optimizer_in_graph = bool(optimizer_in_graph)
+        # (opt=None -- a frozen field whose cameras alone are optimised: no field optimiser anywhere in the step)
+        self.optimizer_in_graph = bool(optimizer_in_graph) and opt is not None
         self._deferred_before = (model.deferred_counts, model.deferred_max_slots)
         model.deferred_counts, model.deferred_max_slots = True, 1 << 62     # nothing inside the graph may wait for the host
         if composer is not None:       # the static inputs ARE the composer's output buffers: nothing is copied in front of a replay
@@ -292,7 +304,7 @@ class GraphedTrainStep:
         # ... and of everything attached (spline and / or per-camera optimisers), by name; with camera_opt= these ARE its .grad views
         self.camera_grads: Optional[Dict[str, Tensor]] = None
         n_total = sum(len(b) for b in (self.col, self.prev, self.nxt) if b is not None)
-        dev = opt.flat.data.device
+        dev = opt.flat.data.device if opt is not None else model.occupancy_grid.occs.device
         self.jitter = torch.rand(n_total, device=dev) if jitter == "input" else None
         self.losses: Dict[str, Tensor] = {}
         self.outputs = None
@@ -375,7 +387,8 @@ class GraphedTrainStep:
         self.losses, self.outputs, self._ray_leaves = {}, None, None
 
     def _body(self, premarched=None):
-        self.opt.zero_grad()
+        if self.opt is not None:
+            self.opt.zero_grad()
         if self.composer is not None:          # draw, gather, rays and metadata of this step; the device step counter ticks behind it
             self.composer.compose()
         col, prev, nxt = self.col, self.prev, self.nxt

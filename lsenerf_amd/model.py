@@ -474,18 +474,60 @@ class LSENeRFModel(nn.Module):
     def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
         """R:lse_nerf/lsenerf.py:231-249 (NGPModel: {"fields": field parameters}).  In an evaluation run (``gbconfig.IS_EVAL``,
         :246-247) only the appearance embedding is optimised: the radiance field is frozen and the test-time embedding fitted."""
-        groups = {"fields": list(self.field.parameters())}
-        if self.config.mapping_method == "gt":
-            return groups
-        if self.config.use_mapping:
-            groups["fields"] += list(self.rgb_mapper.parameters())
-        if self.config.ev_one_dim:
-            groups["fields"] += list(self.rgb_to_one.parameters())
-        if self.config.evs_mapping_method is not None and self.evs_mapper is not None:
-            groups["fields"] += list(self.evs_mapper.parameters())
-        if gbconfig.IS_EVAL:
+        groups = {"fields": self._training_field_params()}
+        if gbconfig.IS_EVAL and self.config.mapping_method != "gt":      # (the reference returns before this line for "gt")
             groups["fields"] = list(self.field.embedding_appearance.parameters())
         return groups
+
+    def _training_field_params(self) -> List[nn.Parameter]:
+        """What ``get_param_groups()["fields"]`` lists in a TRAINING run, whatever ``gbconfig.IS_EVAL`` says."""
+        fields = list(self.field.parameters())
+        if self.config.mapping_method == "gt":
+            return fields
+        if self.config.use_mapping:
+            fields += list(self.rgb_mapper.parameters())
+        if self.config.ev_one_dim:
+            fields += list(self.rgb_to_one.parameters())
+        if self.config.evs_mapping_method is not None and self.evs_mapper is not None:
+            fields += list(self.evs_mapper.parameters())
+        return fields
+
+    def freeze_field(self, train_embedding: bool = True) -> List[nn.Parameter]:
+        """Freeze the radiance field for a test-time refinement run (R:lse_nerf/lsenerf.py:246-247, R:scripts/emb_eval.sh):
+        ``requires_grad_(False)`` on every parameter a training run optimises -- hash table, both MLPs, side heads, mappers,
+        ``rgb_to_one`` -- except, with ``train_embedding``, the appearance embedding's (its ``test_emb`` row included once
+        ``init_test_params`` has made one).  Returns the parameters left trainable (``[]`` without ``train_embedding``, or without an
+        embedding): what the refinement's ``FlatAdam`` is built over.  The step of a frozen field computes no table gradient and
+        hands no frozen parameter a gradient (ops._HashFn, ops._MlpPairFn); ``unfreeze_field`` restores the flags."""
+        if self.__dict__.get("_frozen_flags") is not None:
+            raise RuntimeError("freeze_field: the field is frozen already (unfreeze_field first)")
+        emb = self.field.embedding_appearance
+        keep = {id(p) for p in emb.parameters()} if (train_embedding and emb is not None) else set()
+        flags, seen = [], set()
+        for p in self._training_field_params():
+            if id(p) in seen:
+                continue
+            seen.add(id(p))
+            flags.append((p, p.requires_grad))
+            if id(p) not in keep:
+                p.requires_grad_(False)
+        self.__dict__["_frozen_flags"] = flags
+        if self.field.mlp_head.params.is_cuda:
+            # where the recomputing MLP backward parks the weight-gradient products of a frozen network: allocated here, outside
+            # any graph capture (ops.frozen_wgrad_scratch)
+            for mlp in (self.field.mlp_base_mlp, self.field.mlp_head):
+                if not mlp.params.requires_grad:
+                    ops.frozen_wgrad_scratch(mlp.params)
+        return [p for p, _ in flags if p.requires_grad]
+
+    def unfreeze_field(self) -> None:
+        """Put back the ``requires_grad`` flags ``freeze_field`` found."""
+        flags = self.__dict__.get("_frozen_flags")
+        if flags is None:
+            return
+        for p, was in flags:
+            p.requires_grad_(was)
+        self.__dict__["_frozen_flags"] = None
 
     def init_test_params(self):   # R:lse_nerf/lsenerf.py:251-252
         self.field.embedding_appearance.init_test_params()
@@ -605,14 +647,7 @@ class LSENeRFModel(nn.Module):
         grid = getattr(fld, "mlp_base_grid", None)
         if grid is not None and hasattr(grid, "dense_steps"):      # regime hint for the hash backward's path thresholds
             grid.dense_steps = not (self.config.cone_angle and self.config.cone_angle > 0)
-        if fld.embedding_appearance is None:
-            table, eidx = None, None
-        elif fld.training:
-            table = fld._train_emb_table()
-            eidx = fld.embedding_appearance.ray_indices(ray_bundle.metadata, ray_bundle.camera_indices, num_rays,
-                                                        rays_o.device).contiguous()
-        else:
-            table, eidx = fld._eval_emb(num_rays, rays_o.device)
+        table, eidx = fld._ray_emb(ray_bundle.metadata, ray_bundle.camera_indices, num_rays, rays_o.device)
         # density_packed -> rgb_packed on the same samples (the two MLP forwards are one launch where the shapes allow)
         sigma, _, _, rgb16 = fld.density_rgb_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, eidx, table, n_dev)
         linear = isinstance(self.renderer_rgb, LinearRenderer)

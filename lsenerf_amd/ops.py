@@ -584,6 +584,18 @@ class _HashFn(torch.autograd.Function):
         meta = ctx.meta
         n = x01.shape[0]
         dy = _c(dy)
+        if not ctx.needs_input_grad[1]:
+            # frozen table (test-time refinement): the input gradient alone -- a gather, no table-sized tensor, no scatter
+            hooks = _hash_bwd_hooks_of(table)
+            if hooks and hooks.get("before") is not None:
+                hooks["before"]()
+            dx = None
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x01)
+                desc = meta.desc()
+                _call_n("lse_hash_bwd_input", ctx.n_dev, ctypes.byref(desc), _f32(x01, "x01"), _f32(dy, "dy"),
+                        _f32(table, "table"), ctypes.c_void_p(dx.data_ptr()), n, _stream())
+            return dx, None, None, None, None
         direct = _direct_grad(table)
         dtable = direct if direct is not None else torch.zeros_like(table)
         dx = torch.empty_like(x01) if ctx.needs_input_grad[0] else None
@@ -637,6 +649,22 @@ def compact_features(mask, packed_info, new_packed_info, n_new: int, x01, sel, y
 # ----------------------------------------------------------------------------------------------------
 # fused MLP
 # ----------------------------------------------------------------------------------------------------
+def frozen_wgrad_scratch(params: torch.Tensor) -> torch.Tensor:
+    """Where the recomputing MLP backward (act_tiled = 3) puts the weight-gradient products of a FROZEN parameter vector
+    (``requires_grad == False``): the kernel forms them together with the data gradients, so they need an address, and nothing ever
+    reads it.  One buffer of the parameter's size, kept on the parameter object for its whole life -- a captured graph bakes the
+    address in (the reason ``GlobalEmbedding._zero_idx`` is a buffer) -- and therefore never allocated during a stream capture,
+    whose allocations belong to that graph's pool: run one eager step first (``GraphedTrainStep`` warms up, ``freeze_field``
+    allocates at once)."""
+    s = getattr(params, "_lse_wgrad_scratch", None)
+    if s is None or s.numel() != params.numel() or s.device != params.device:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.LseHipError("the weight-gradient scratch of a frozen MLP parameter cannot be allocated inside a stream "
+                                   "capture: run one eager step (or ops.frozen_wgrad_scratch(param)) before capturing")
+        s = params._lse_wgrad_scratch = torch.zeros(params.numel(), dtype=torch.float32, device=params.device)
+    return s
+
+
 class _MlpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, params, x, row_bias, row_bias_idx, bias_packed_info, selector, meta: MlpMeta, n: int, out_cols: int,
@@ -653,7 +681,9 @@ class _MlpFn(torch.autograd.Function):
                      or (FUSED_BIAS_GRAD and row_bias_idx is not None and bias_packed_info is not None)):
             tiled = 2     # (only the second-generation backward recomputes: it needs the bias gradient reduced in-kernel)
         # third generation (mlp_x6.h): nothing is saved, the backward recomputes every hidden layer on the bf16 matrix cores
-        if tiled and RECOMPUTE_ALL and meta.width == 64 and need_grad and params.requires_grad \
+        # (frozen parameters under a device-side count take it too -- the saved-activation kernels have no count; their weight
+        # gradients go to frozen_wgrad_scratch)
+        if tiled and RECOMPUTE_ALL and meta.width == 64 and need_grad and (params.requires_grad or n_dev is not None) \
                 and ((meta.n_in == 16 and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR)
                      or (meta.n_in == 32 and meta.n_hidden_layers == 1)) \
                 and (row_bias is None or not row_bias.requires_grad
@@ -663,6 +693,7 @@ class _MlpFn(torch.autograd.Function):
         n_saved = meta.n_hidden_layers - (1 if tiled == 2 else 0)
         act = torch.empty((n_saved, n_act, meta.width), dtype=torch.float32, device=dev) if (need_grad and tiled != 3) else None
         ctx.act_tiled = tiled
+        ctx.wscratch = frozen_wgrad_scratch(params) if (tiled == 3 and not params.requires_grad) else None
         desc = meta.desc()
         if n_dev is not None and need_grad and tiled != 3:
             raise _lib.LseHipError("a device-side sample count needs the recomputing MLP kernels (width 64, head / base shape)")
@@ -690,6 +721,7 @@ class _MlpFn(torch.autograd.Function):
         d_in = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         direct = _direct_grad(params) if (ctx.needs_input_grad[0] and (ctx.act_tiled or FUSED_WGRAD)) else None
         d_params = direct if direct is not None else (torch.zeros_like(params) if ctx.needs_input_grad[0] else None)
+        wgrad_out = d_params if (d_params is not None or ctx.act_tiled != 3) else ctx.wscratch     # act_tiled = 3 always forms them
         desc = meta.desc()
         scale = float(ctx.density_scale or 0.0)
         sel = _chk(selector, torch.uint8, "selector", True)
@@ -698,7 +730,7 @@ class _MlpFn(torch.autograd.Function):
                       _f32(act, "act", ctx.act_tiled == 3),
                       ctx.act_tiled, _f32(out, "out"), out_cols, _f32(d_out, "d_out"), _f32(d_sigma, "d_sigma", True), sel, scale,
                       None, None, _f32(d_act0, "d_act0", True), _f32(d_in, "d_in", True),
-                      _f32(d_params, "d_params", True), _f32(row_bias, "row_bias", True),
+                      _f32(wgrad_out, "d_params", True), _f32(row_bias, "row_bias", True),
                       _chk(row_bias_idx, torch.int32, "row_bias_idx", True) if (fused_bias or ctx.act_tiled >= 2) else None,
                       _f32(d_bias if fused_bias else None, "d_bias", True), n, _stream())
         else:   # reference structure: materialise d_act, then one G^T A reduction per layer (padded outputs only)
@@ -757,6 +789,11 @@ class _MlpPairFn(torch.autograd.Function):
         ctx.save_for_backward(base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, h, out)
         ctx.base_meta, ctx.head_meta, ctx.n, ctx.out_cols, ctx.density_scale, ctx.n_dev = \
             base_meta, head_meta, n, out_cols, density_scale, n_dev
+        # frozen parameters: the recomputing backward still forms the weight-gradient products; they go where nothing reads them
+        need_grad = any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
+        ctx.head_scratch = frozen_wgrad_scratch(head_params) if (need_grad and not head_params.requires_grad) else None
+        ctx.base_scratch = frozen_wgrad_scratch(base_params) if (need_grad and not base_params.requires_grad
+                                                                 and y.requires_grad) else None
         ctx.set_materialize_grads(False)
         return h, sigma, out
 
@@ -771,9 +808,12 @@ class _MlpPairFn(torch.autograd.Function):
             need_bias = row_bias is not None and ctx.needs_input_grad[4]
             d_bias = torch.zeros_like(row_bias) if need_bias else None
             d_in_head = torch.empty_like(h)
-            direct = _direct_grad(head_params)
-            d_hp = direct if direct is not None else torch.zeros_like(head_params)
-            d_hp_ret = None if direct is not None else d_hp
+            if ctx.needs_input_grad[3]:
+                direct = _direct_grad(head_params)
+                d_hp = direct if direct is not None else torch.zeros_like(head_params)
+                d_hp_ret = None if direct is not None else d_hp
+            else:
+                d_hp = ctx.head_scratch
             hdesc = ctx.head_meta.desc()
             _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(hdesc), _f32(head_params, "params"), _f32(h, "mlp input"), None, 3,
                     _f32(out, "out"), out_cols, _f32(d_out, "d_out"), None, None, 0.0, None, None, None,
@@ -785,13 +825,17 @@ class _MlpPairFn(torch.autograd.Function):
         else:
             d_base = d_in_head if d_in_head is not None else d_h
         d_y, d_bp_ret = None, None
-        if d_base is not None or d_sigma is not None:
+        # (neither y nor the base parameters need a gradient -- a frozen field refining its embedding: no base launch at all)
+        if (d_base is not None or d_sigma is not None) and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             d_base = _c(d_base) if d_base is not None else torch.zeros((n, 16), dtype=torch.float32, device=dev)
             d_sigma = _c(d_sigma) if d_sigma is not None else None
             d_y = torch.empty_like(y) if ctx.needs_input_grad[1] else None
-            direct = _direct_grad(base_params)
-            d_bp = direct if direct is not None else torch.zeros_like(base_params)
-            d_bp_ret = None if direct is not None else d_bp
+            if ctx.needs_input_grad[0]:
+                direct = _direct_grad(base_params)
+                d_bp = direct if direct is not None else torch.zeros_like(base_params)
+                d_bp_ret = None if direct is not None else d_bp
+            else:
+                d_bp = ctx.base_scratch
             bdesc = ctx.base_meta.desc()
             _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(bdesc), _f32(base_params, "params"), _f32(y, "mlp input"), None, 3,
                     _f32(h, "out"), 16, _f32(d_base, "d_out"), _f32(d_sigma, "d_sigma", True),
@@ -803,14 +847,16 @@ class _MlpPairFn(torch.autograd.Function):
 def mlp_pair_usable(base_params, y, base_meta: MlpMeta, head_params, head_meta: MlpMeta, row_bias, row_bias_idx,
                     bias_packed_info) -> bool:
     """Whether ``fused_mlp_pair`` may replace ``fused_mlp`` (base, density head) followed by ``fused_mlp`` (head) on the same
-    samples: the switch is on, the shapes are the pair's, and either nothing needs a gradient or both calls would take the
-    recompute-all path (``_MlpFn.forward``: nothing saved, act_tiled = 3)."""
+    samples: the switch is on, the shapes are the pair's, and either nothing needs a gradient or both backward launches can take
+    the recompute-all path (nothing saved, act_tiled = 3) -- with trainable parameters what ``_MlpFn.forward`` would choose, with
+    frozen ones (``requires_grad == False``) the same kernels writing their weight-gradient products to ``frozen_wgrad_scratch``."""
     if not (MLP_FWD_PAIR and _mlp_pair_shapes(base_meta, head_meta)):
         return False
     need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
     if not need_grad:
         return True
-    return bool(FUSED_WGRAD and ACT_TILED and RECOMPUTE_ALL and base_params.requires_grad and head_params.requires_grad
+    # (frozen parameters recompute as well: their weight-gradient products land in frozen_wgrad_scratch)
+    return bool(FUSED_WGRAD and ACT_TILED and RECOMPUTE_ALL
                 and (row_bias is None or not row_bias.requires_grad
                      or (FUSED_BIAS_GRAD and row_bias_idx is not None and bias_packed_info is not None)))
 
