@@ -315,6 +315,21 @@ int lse_mlp_bwd(const lse_mlp_desc *desc, const float *params, const float *in, 
                 float *d_out_pre, float *d_act, float *d_act0, float *d_in, float *d_params,
                 const float *row_bias, const int32_t *row_bias_idx, float *d_row_bias, int64_t n, const int64_t *n_dev,
                 lse_stream_t stream);
+/* The data gradients of lse_mlp_bwd(act_tiled = 3) alone, for FROZEN parameters (test-time refinement): d_in (overwritten,
+ * layout of desc->in_layout; nullable) and d_row_bias[rows][width] (accumulated; nullable, needs row_bias and a sorted
+ * row_bias_idx), at least one of the two.  No weight-gradient product is formed and there is no d_params: every hidden layer is
+ * recomputed from `in` (and row_bias) on the bf16 matrix cores (three-piece operands) and only the transposed-weight products
+ * run.  out / out_cols / d_out / d_sigma / selector / density_scale as in lse_mlp_bwd.
+ * Contract: d_in is BIT-EQUAL to what lse_mlp_bwd(act_tiled = 3) writes for the same arguments (the same matrix-core products
+ * in the same order, no atomics), and two calls give the same bits.  d_row_bias sums the same f32 terms as lse_mlp_bwd in
+ * another order (fixed inside a wave, float atomics across waves): equal up to f32 summation order, not bitwise.  Rows of d_in
+ * at or beyond the count are not written.
+ * Shapes: width 64 with 16 row-major inputs and two hidden layers (first-layer view w0_ld / w0_col / w0_mask_col0 honoured) or
+ * 32 inputs (either layout) and one, LSE_MLP_ARITH_AUTO; anything else is LSE_E_UNSUPPORTED.  Keeps no state. */
+int lse_mlp_bwd_input(const lse_mlp_desc *desc, const float *params, const float *in, const float *out, int32_t out_cols,
+                      const float *d_out, const float *d_sigma, const uint8_t *selector, float density_scale, float *d_in,
+                      const float *row_bias, const int32_t *row_bias_idx, float *d_row_bias, int64_t n, const int64_t *n_dev,
+                      lse_stream_t stream);
 /* unfused weight gradients from materialised d_act / d_out_pre, accumulate into d_params (same layout as params). */
 int lse_mlp_wgrad(const lse_mlp_desc *desc, const float *in, const float *act, const float *d_act,
                   const float *d_out_pre, float *d_params, int64_t n, lse_stream_t stream);

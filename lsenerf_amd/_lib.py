@@ -142,6 +142,7 @@ SIGNATURES = {
     "lse_mlp_fwd": [POINTER(MlpDesc), P, P, P, P, P, I32, P, I32, P, P, F32, I64, P, P],
     "lse_mlp_fwd_pair": [POINTER(MlpDesc), P, P, P, F32, POINTER(MlpDesc), P, P, P, P, P, P, I32, I64, P, P],
     "lse_mlp_bwd": [POINTER(MlpDesc), P, P, P, I32, P, I32, P, P, P, F32, P, P, P, P, P, P, P, P, I64, P, P],
+    "lse_mlp_bwd_input": [POINTER(MlpDesc), P, P, P, I32, P, P, P, F32, P, P, P, P, I64, P, P],
     "lse_mlp_wgrad": [POINTER(MlpDesc), P, P, P, P, P, I64, P],
     "lse_segment_sum_rows": [P, I32, P, I32, P, P],
     "lse_ray_features_fwd": [P, P, P, I32, I32, P, P],

@@ -1519,6 +1519,21 @@ int launch_bwd3(const MlpArgs &a, hipStream_t st)
     return launch_bwd3_cfg<KIN, NHL, INL, BIAS, BIAS_ONES, 2, 8>(a, st);
 }
 
+// d(input) / d(row_bias) alone (mlp_bwd_input_kernel): WAVES_PER_SIMD workgroups of one wave per SIMD on each of the 256 CUs
+template <int KIN, int NHL, int INL>
+int launch_bwd_input(const MlpArgs &a, hipStream_t st)
+{
+    using C = X6BwdIn<KIN, NHL>;
+    static_assert(C::lds_bytes * C::WAVES_PER_SIMD <= 160 * 1024, "LDS budget of one CU");
+    const int64_t tiles = (a.n + 16 * C::CT - 1) / (16 * C::CT);
+    const int blocks = (int)std::min<int64_t>((tiles + C::NW - 1) / C::NW, 256 * C::WAVES_PER_SIMD);
+    if (a.row_bias)
+        hipLaunchKernelGGL((mlp_bwd_input_kernel<KIN, NHL, INL, true>), dim3(blocks), dim3(64 * C::NW), C::lds_bytes, st, a);
+    else
+        hipLaunchKernelGGL((mlp_bwd_input_kernel<KIN, NHL, INL, false>), dim3(blocks), dim3(64 * C::NW), C::lds_bytes, st, a);
+    return lse::check_launch("lse_mlp_bwd_input");
+}
+
 template <int KIN, int WIDTH, int NHL, int INL>
 int launch_bwd(const MlpArgs &a, hipStream_t st)
 {
@@ -1724,6 +1739,48 @@ extern "C" int lse_mlp_bwd(const lse_mlp_desc *desc, const float *params, const 
     fill_view(a, desc);
     hipStream_t st = lse::as_stream(stream);
     LSE_MLP_DISPATCH(launch_bwd, desc, a, st);
+}
+
+extern "C" int lse_mlp_bwd_input(const lse_mlp_desc *desc, const float *params, const float *in, const float *out,
+                                 int32_t out_cols, const float *d_out, const float *d_sigma, const uint8_t *selector,
+                                 float density_scale, float *d_in, const float *row_bias, const int32_t *row_bias_idx,
+                                 float *d_row_bias, int64_t n, const int64_t *n_dev, lse_stream_t stream)
+{
+    int rc = check_desc(desc, "lse_mlp_bwd_input");
+    if (rc) return rc;
+    LSE_REQUIRE(n >= 0, "lse_mlp_bwd_input: n < 0");
+    const bool head = desc->n_in == 16 && desc->width == 64 && desc->n_hidden_layers == 2 && desc->in_layout == LSE_IN_ROWMAJOR;
+    const bool base = desc->n_in == 32 && desc->width == 64 && desc->n_hidden_layers == 1;
+    if (!head && !base) {
+        lse::set_error("lse_mlp_bwd_input: built for the 16->64->64->16 row-major head and the 32->64->16 base only (got n_in=%d "
+                       "width=%d n_hidden_layers=%d in_layout=%d)",
+                       desc->n_in, desc->width, desc->n_hidden_layers, desc->in_layout);
+        return LSE_E_UNSUPPORTED;
+    }
+    if (desc->arith != LSE_MLP_ARITH_AUTO) {
+        lse::set_error("lse_mlp_bwd_input: bf16x6 arithmetic only (desc->arith must be LSE_MLP_ARITH_AUTO)");
+        return LSE_E_UNSUPPORTED;
+    }
+    LSE_REQUIRE(out_cols == 16 || out_cols == 4, "lse_mlp_bwd_input: out_cols must be 16 or 4");
+    LSE_REQUIRE(d_in || d_row_bias, "lse_mlp_bwd_input: neither d_in nor d_row_bias is wanted");
+    LSE_REQUIRE(!d_row_bias || row_bias_idx, "lse_mlp_bwd_input: d_row_bias needs row_bias_idx (sorted rows)");
+    LSE_REQUIRE(!d_row_bias || row_bias, "lse_mlp_bwd_input: d_row_bias needs row_bias");
+    if (n == 0) return LSE_OK;
+    LSE_REQUIRE(params && in && d_out, "lse_mlp_bwd_input: null pointer");
+    LSE_REQUIRE(desc->out_activation == LSE_ACT_NONE || out, "lse_mlp_bwd_input: sigmoid backward needs `out`");
+    LSE_REQUIRE(!d_sigma || out, "lse_mlp_bwd_input: the density gradient needs `out`");
+    MlpArgs a{};
+    a.params = params; a.in = in; a.out = const_cast<float *>(out); a.d_out = d_out; a.d_in = d_in; a.n = n;
+    a.n_stride = n; a.n_dev = n_dev;
+    a.out_activation = desc->out_activation; a.out_cols = out_cols; a.d_sigma = d_sigma; a.selector = selector;
+    a.density_scale = density_scale;
+    a.act_tiled = 3;
+    a.row_bias = row_bias; a.row_bias_idx = row_bias_idx; a.d_row_bias = d_row_bias;
+    fill_view(a, desc);
+    hipStream_t st = lse::as_stream(stream);
+    if (head) return launch_bwd_input<16, 2, LSE_IN_ROWMAJOR>(a, st);
+    if (desc->in_layout == LSE_IN_LEVELMAJOR) return launch_bwd_input<32, 1, LSE_IN_LEVELMAJOR>(a, st);
+    return launch_bwd_input<32, 1, LSE_IN_ROWMAJOR>(a, st);
 }
 
 extern "C" int lse_gemm_tn_acc(const float *g, int32_t m, const float *a, int32_t k, int32_t a_layout, int64_t n,

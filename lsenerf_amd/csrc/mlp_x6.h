@@ -1516,3 +1516,458 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
     if constexpr (NHL == 2) flush_wgrad<HB, HB>(a.d_params + a.rest_off, WIDTH, WIDTH, acc1, j, q);
     flush_wgrad<1, HB>(a.d_params + a.rest_off + (NHL - 1) * WIDTH * WIDTH, WIDTH, WIDTH, accO, j, q);
 }
+
+// ------------------------------------------------------------------------------------------------------
+// backward for FROZEN parameters: d(input) and d(row_bias) alone (lse_mlp_bwd_input).  The tile walk, the loads, the output
+// gradient preamble, the recomputed hidden layers and the three transposed-weight products are those of mlp_bwd3_kernel, product
+// by product in the same order, so d_in carries the same bits.  Nothing of the weight-gradient side is left: no dWo / dW1 / dW0
+// products, no second evaluation of H0^T, no per-wave LDS tile (the pieces of one product's accumulator are the B operand of the
+// next and stay in registers, as in the forward kernels), no accumulators that live across tiles except the 16 floats of the
+// running row-bias sum, no reduction tree and no parameter-sized output.  LDS = the plain weight piece images + the two
+// "minus identity" operands.
+//
+// d_row_bias[row] += sum over the row's samples of dH0 (what mlp_bwd3_kernel reads from a free column of its dW0 product): every
+// lane keeps the running sum of its own samples over the column tiles that belong wholly to the current row; when the row
+// changes, and at the end of the wave's range, the 16 sample lanes of a group are summed (fixed order) and added to memory with
+// float atomics.  A column tile that straddles rows goes through row_bias_grad_tile.
+// ------------------------------------------------------------------------------------------------------
+// one wave of a workgroup per SIMD, kBwdInWavesPerSimd workgroups per CU (what the register count allows: DESIGN.md section 4)
+constexpr int kBwdInNW = 4, kBwdInWavesPerSimd = 3;
+
+template <int KIN, int NHL>
+struct X6BwdIn {
+    static constexpr int S0 = KIN / 16;
+    static constexpr int W0_PIECE = 64 * 32 * S0, W1_PIECE = (NHL == 2) ? 64 * 128 : 0, WO_PIECE = 16 * 128;
+    static constexpr int W_BYTES = 3 * (W0_PIECE + W1_PIECE + WO_PIECE);
+    static constexpr int NI_BYTES = 2 * 1024;                 // the two "minus identity" A operands, one 16-byte entry per lane
+    static constexpr int lds_bytes = W_BYTES + NI_BYTES;      // head 38 912 B, base 20 480 B
+    static constexpr int NW = kBwdInNW, CT = 2, WAVES_PER_SIMD = kBwdInWavesPerSimd;
+};
+
+template <int KIN, int NHL, int INL, bool BIAS>
+__global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_input_kernel(MlpArgs a)
+{
+    using C = X6BwdIn<KIN, NHL>;
+    constexpr int CT = C::CT, NW = C::NW;
+    constexpr int TS = 16 * CT, HB = 4, WIDTH = 64, S0 = C::S0, KB0 = KIN / 16;
+    constexpr bool MS = (KIN == 32);      // remainder MFMAs on pairs of row blocks (base) / on single blocks (head), as in mlp_bwd3_kernel
+    static_assert((KIN == 16 && NHL == 2 && INL == LSE_IN_ROWMAJOR) || (KIN == 32 && NHL == 1), "head or base shape");
+    extern __shared__ float lds[];
+    uint8_t *imgW0 = reinterpret_cast<uint8_t *>(lds);
+    uint8_t *imgW1 = imgW0 + 3 * C::W0_PIECE;
+    uint8_t *imgWo = imgW1 + 3 * C::W1_PIECE;
+
+    const float *W0 = a.params + a.w0_col;
+    const float *W1 = a.params + a.rest_off;
+    const float *Wo = W1 + (NHL - 1) * WIDTH * WIDTH;
+    stage_plain<64, KIN>(imgW0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
+    if constexpr (NHL == 2) stage_plain<64, 64>(imgW1, W1, WIDTH, 0, 64 * NW);
+    stage_plain<16, 64>(imgWo, Wo, WIDTH, 0, 64 * NW);
+    if (threadIdx.x < 64) {
+        u32x4 t[2];
+        neg_identity(threadIdx.x, t);
+        u32x4 *dst = reinterpret_cast<u32x4 *>(imgWo + 3 * C::WO_PIECE);
+        dst[threadIdx.x] = t[0];
+        dst[64 + threadIdx.x] = t[1];
+    }
+    __syncthreads();       // the only barrier: the images are read-only from here on
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+    const int tq = j >> 2, tp = j & 3;               // transposed reads: this lane addresses row tq, chunk tp of its group's block
+    const u32x4 *nI_lds = reinterpret_cast<const u32x4 *>(imgWo + 3 * C::WO_PIECE) + lane;
+    struct NegI {
+        const u32x4 *p;
+        __device__ __forceinline__ u32x4 operator[](int b) const { return p[64 * b]; }
+    };
+    const NegI nI{nI_lds};
+    // per-lane byte offsets into the images (see mlp_bwd3_kernel)
+    int so_j[4], so_t[4];
+#pragma unroll
+    for (int seg = 0; seg < 4; ++seg) {
+        so_j[seg] = img_off<4>(j, seg, q);
+        so_t[seg] = img_off<4>(4 * q + tq, seg, tp);
+    }
+    const int sm_j = img_off<1>(j, 0, q), sm_t = img_off<1>(4 * q + tq, 0, tp);
+    const int w0b_j = img_off<2>(j, q >> 1, 2 * (q & 1));
+    int w0b_t[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) w0b_t[cb] = img_off<2>(4 * q + tq, cb, tp);
+
+    a.n = lse::clamp_count(a.n, a.n_dev);
+    const int64_t n = a.n, ns = a.n_stride;
+    const int64_t n_tiles = (n + TS - 1) / TS;
+    const int64_t total_waves = (int64_t)gridDim.x * NW;
+    const int64_t per = (n_tiles + total_waves - 1) / total_waves;
+    const int64_t w_id = (int64_t)blockIdx.x * NW + wave;
+    const int64_t t_begin = min(n_tiles, w_id * per), t_end = min(n_tiles, t_begin + per);
+    const bool need_out = a.out_activation == LSE_ACT_SIGMOID;
+    const int oc = a.out_cols;
+    const bool want_bias = BIAS && a.d_row_bias != nullptr;
+
+    // running row-bias sum: this lane's samples of the column tiles that belong wholly to row cur_row (wave-uniform)
+    int cur_row = -1;
+    f32x4 bsum[HB];
+#pragma unroll
+    for (int mb = 0; mb < HB; ++mb) bsum[mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    auto flush_bias = [&]() {
+        if (cur_row >= 0) {
+            float *dst = a.d_row_bias + (int64_t)cur_row * WIDTH + 4 * q;
+#pragma unroll
+            for (int mb = 0; mb < HB; ++mb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = bsum[mb][r];
+#pragma unroll
+                    for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 16);
+                    if (j == 0) atomicAdd(dst + 16 * mb + r, v);
+                }
+        }
+#pragma unroll
+        for (int mb = 0; mb < HB; ++mb) bsum[mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    };
+
+    auto row_chain_w1 = [&](int rb, int s, u32x4 (&o)[3]) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const u32x2 lo = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s]));
+            const u32x2 hi = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s + 1]));
+            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
+        }
+    };
+    auto tr_chain_w1 = [&](int cb, int s, u32x4 (&o)[3]) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const u32x2 lo = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + so_t[cb]));
+            const u32x2 hi = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + 2048 + so_t[cb]));
+            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
+        }
+    };
+    auto tr_chain_w0 = [&](int cb, int s, u32x4 (&o)[3]) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const int base = (KIN == 16) ? sm_t : w0b_t[cb & 1];
+            const int row32 = 32 * (32 * S0);        // bytes of 32 image rows
+            const u32x2 lo = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + base));
+            const u32x2 hi = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + row32 / 2 + base));
+            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
+        }
+    };
+    // pieces of two accumulator row blocks 2s2, 2s2+1 (= one k slab of the next product), both column tiles
+    auto split_blocks = [&](int s2, const f32x4 (&c0)[CT], const f32x4 (&c1)[CT], PiecesB<HB> (&x)[CT]) {
+        if constexpr (MS) {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) split_pair(c0[ct], c1[ct], nI, x[ct].p[s2]);
+        }
+    };
+    auto split_block_single = [&](int s2, int b, const f32x4 (&c)[CT], PiecesB<HB> (&x)[CT]) {
+        if constexpr (!MS) {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                uint32_t hi[2], mid[2], lo[2];
+                split_half(c[ct], nI, hi, mid, lo);
+#pragma unroll
+                for (int w2 = 0; w2 < 2; ++w2) {
+                    x[ct].p[s2][0][2 * b + w2] = hi[w2];
+                    x[ct].p[s2][1][2 * b + w2] = mid[w2];
+                    x[ct].p[s2][2][2 * b + w2] = lo[w2];
+                }
+            }
+        }
+    };
+
+    int brow_nx[CT] = {};
+    if (BIAS && a.row_bias_idx && t_begin < t_end) {
+        const int64_t b0 = t_begin * TS;
+        const int nr = (int)min((int64_t)TS, n - b0);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) brow_nx[ct] = a.row_bias_idx[b0 + min(ct * 16 + j, nr - 1)];
+    }
+    for (int64_t tile = t_begin; tile < t_end; ++tile) {
+        const int64_t tile_base = tile * TS;
+        const int n_rem = (int)min((int64_t)TS, n - tile_base);       // valid samples of this tile (wave-uniform, >= 1)
+        int sl[CT];
+        bool valid[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            valid[ct] = ct * 16 + j < n_rem;
+            sl[ct] = valid[ct] ? ct * 16 + j : n_rem - 1;
+        }
+        // ---- loads
+        f32x4 raw[CT][KIN / 16];
+        load_in_x6<KIN, INL, CT>(a, tile, j, q, raw);
+        const float *rbase = a.row_bias;
+        int brow[CT] = {};
+        if constexpr (BIAS) {
+            if (a.row_bias_idx) {       // this tile's rows were requested during the previous tile; request the next tile's now
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) brow[ct] = brow_nx[ct];
+                if (tile + 1 < t_end) {
+                    const int64_t nb_ = tile_base + TS;
+                    const int nr = (int)min((int64_t)TS, n - nb_);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) brow_nx[ct] = a.row_bias_idx[nb_ + min(ct * 16 + j, nr - 1)];
+                }
+            } else {
+                rbase = a.row_bias + tile_base * WIDTH;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) brow[ct] = sl[ct];
+            }
+        }
+        // ---- output gradient (the preamble of mlp_bwd3_kernel, expression by expression)
+        f32x4 g[CT];
+        {
+            const float *dout_t = a.d_out + tile_base * oc;
+            const float *out_t = a.out ? a.out + tile_base * oc : nullptr;
+            f32x4 ovv[CT];
+            float dsgv[CT], o0v[CT];
+            uint32_t selv[CT];
+            const bool lane_sig = a.d_sigma != nullptr && q == 0;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                const int slc = sl[ct];
+                ovv[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (oc == 16) g[ct] = *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 16 + 4 * q));
+                else g[ct] = (q == 0) ? *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (need_out) {
+                    if (oc == 16) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 16 + 4 * q));
+                    else if (q == 0) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 4));
+                }
+                dsgv[ct] = lane_sig ? a.d_sigma[tile_base + slc] : 0.f;
+                o0v[ct] = (lane_sig && !need_out) ? out_t[(unsigned)(slc * oc)] : 0.f;
+                selv[ct] = (lane_sig && a.selector) ? (uint32_t)a.selector[tile_base + slc] : 1u;
+            }
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                f32x4 ov = ovv[ct];
+                if (lane_sig && !need_out) ov[0] = o0v[ct];
+                const float dsg = selv[ct] != 0u ? dsgv[ct] : 0.f;
+                const float x0 = fminf(fmaxf(ov[0], -15.f), 15.f);
+                if (need_out) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) g[ct][r] = g[ct][r] * ov[r] * (1.f - ov[r]);
+                }
+                if (lane_sig) g[ct][0] += dsg * a.density_scale * expf(x0);
+                if (!valid[ct]) g[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        // ---- which column tiles feed the running row sum (wave-uniform): one row per tile, as in mlp_bwd3_kernel
+        bool whole[CT] = {};
+        if (want_bias) {
+            bool taken = false;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                const int first = __builtin_amdgcn_readfirstlane(brow[ct]);
+                if (__builtin_amdgcn_ballot_w64(brow[ct] != first) == 0) {     // one row owns this column tile
+                    if (first == cur_row) {
+                        whole[ct] = true;
+                        taken = true;
+                    } else if (!taken) {
+                        flush_bias();
+                        cur_row = first;
+                        whole[ct] = true;
+                        taken = true;
+                    }
+                }
+            }
+        }
+        // row block cb of the layer-0 pre-activation gradient (gated), both column tiles
+        auto bias_block = [&](int cb, const f32x4 (&d)[CT]) {
+            if (want_bias) {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    if (whole[ct]) {
+                        bsum[cb] += d[ct];
+                    } else {
+                        const f32x4 gcol[1] = {d[ct]};
+                        row_bias_grad_tile<1, WIDTH>(a.d_row_bias + 16 * cb, brow[ct], gcol, j, q);
+                    }
+                }
+            }
+        };
+        // ---- first hidden layer again: relu(W0 in + bias) -> mask bits, and (head) the pieces that feed the second layer
+        PiecesB<HB> x[CT];
+        uint32_t m0[CT] = {}, m1[CT] = {};      // ReLU masks, bit 4rb + r
+        {
+            PiecesB16 xin16[CT];
+            u32x4 xin[CT][3];
+            if constexpr (KIN == 16) {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) split_in16(raw[ct][0], nI, xin16[ct]);
+            } else {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) split_pair(raw[ct][0], raw[ct][1], nI, xin[ct]);
+            }
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb) {
+                f32x4 h[CT];
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    if constexpr (BIAS) h[ct] = *reinterpret_cast<const f32x4 *>(rbase + (unsigned)(brow[ct] * WIDTH + 16 * rb + 4 * q));
+                    else h[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+                if constexpr (KIN == 16) {
+                    u32x4 wc[3];
+                    combos16_lds([&](int p) { return lds_read8(imgW0 + (p * C::W0_PIECE + 512 * rb + sm_j)); }, wc);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[2], xin16[ct].c[2], h[ct]);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[1], xin16[ct].c[1], h[ct]);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[0], xin16[ct].c[0], h[ct]);
+                } else {
+                    u32x4 wa[3];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p)
+                        wa[p] = *reinterpret_cast<const u32x4 *>(imgW0 + (p * C::W0_PIECE + 1024 * rb + w0b_j));
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = mfma6(wa, xin[ct], h[ct]);
+                }
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        h[ct][r] = relu_bits(h[ct][r]);
+                        m0[ct] |= (h[ct][r] > 0.f ? 1u : 0u) << (4 * rb + r);
+                    }
+                // (the base needs the mask alone: its hidden layer feeds no further product here)
+                if constexpr (NHL == 2) split_block_single(rb >> 1, rb & 1, h, x);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if constexpr (NHL == 2) {
+            // ---- second hidden layer again: the mask alone
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb) {
+                f32x4 h[CT];
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) h[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    u32x4 wa[3];
+                    row_chain_w1(rb, s, wa);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = mfma6(wa, x[ct].p[s], h[ct]);
+                }
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) m1[ct] |= (relu_bits(h[ct][r]) > 0.f ? 1u : 0u) << (4 * rb + r);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // ---- dH_last = Wo^T G_out (16 rows of Wo: k = 16), gated by the last mask; pieces stay in registers
+        {
+            PiecesB16 gx[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) split_in16(g[ct], nI, gx[ct]);
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                f32x4 dh[2][CT];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const int rb = 2 * s2 + b;
+                    u32x4 wc[3];
+                    combos16_lds([&](int p) { return lds_tr_read(imgWo + (p * C::WO_PIECE + so_t[rb])); }, wc);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) {
+                        f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
+                        c = LSE_MFMA_BF(wc[2], gx[ct].c[2], c);
+                        c = LSE_MFMA_BF(wc[1], gx[ct].c[1], c);
+                        dh[b][ct] = LSE_MFMA_BF(wc[0], gx[ct].c[0], c);
+                        const uint32_t m = (NHL == 2) ? m1[ct] : m0[ct];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) dh[b][ct][r] = relu_gate(dh[b][ct][r], m, 4 * rb + r);
+                    }
+                    if constexpr (NHL == 1) bias_block(rb, dh[b]);
+                    split_block_single(s2, b, dh[b], x);
+                    if constexpr (!MS) __builtin_amdgcn_sched_barrier(0);
+                }
+                split_blocks(s2, dh[0], dh[1], x);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // ---- dIn = W0^T dH0, stored as mlp_bwd3_kernel stores it
+        auto d_in_of = [&](const PiecesB<HB> (&z)[CT]) {
+            if (a.d_in) {
+#pragma unroll
+                for (int cb = 0; cb < KB0; ++cb) {
+                    f32x4 di[CT];
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) di[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        u32x4 wa[3];
+                        tr_chain_w0(cb, s, wa);
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) di[ct] = mfma6(wa, z[ct].p[s], di[ct]);
+                    }
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) {
+                        if (!valid[ct]) continue;
+                        if (INL == LSE_IN_LEVELMAJOR) {
+                            float2 *d2 = reinterpret_cast<float2 *>(a.d_in) + tile_base;
+                            const int lv = 8 * cb + 2 * q;
+                            d2[(int64_t)lv * ns + sl[ct]] = make_float2(di[ct][0], di[ct][1]);
+                            d2[(int64_t)(lv + 1) * ns + sl[ct]] = make_float2(di[ct][2], di[ct][3]);
+                        } else {
+                            *reinterpret_cast<f32x4 *>(a.d_in + tile_base * KIN + (unsigned)(sl[ct] * KIN + 16 * cb + 4 * q)) = di[ct];
+                        }
+                    }
+                }
+            }
+        };
+        if constexpr (NHL == 2) {
+            // ---- dH0 = W1^T dH1, gated by m0.  Slab by slab over all four output blocks: every accumulator still receives slab 0's
+            // six products before slab 1's (the order of mlp_bwd3_kernel), and the pieces of a slab are dead once it has been
+            // used -- the four accumulators replace them in the register file instead of standing beside all of dH1 and dH0.
+            f32x4 d0[HB][CT];
+#pragma unroll
+            for (int cb = 0; cb < HB; ++cb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) d0[cb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int cb = 0; cb < HB; ++cb) {
+                    u32x4 wa[3];
+                    tr_chain_w1(cb, s, wa);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) d0[cb][ct] = mfma6(wa, x[ct].p[s], d0[cb][ct]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+            for (int cb = 0; cb < HB; ++cb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) d0[cb][ct][r] = relu_gate(d0[cb][ct][r], m0[ct], 4 * cb + r);
+            if (want_bias) {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    if (whole[ct]) {
+#pragma unroll
+                        for (int cb = 0; cb < HB; ++cb) bsum[cb] += d0[cb][ct];
+                    } else {
+                        f32x4 gcol[HB];
+#pragma unroll
+                        for (int cb = 0; cb < HB; ++cb) gcol[cb] = d0[cb][ct];
+                        row_bias_grad_tile<HB, WIDTH>(a.d_row_bias, brow[ct], gcol, j, q);
+                    }
+                }
+            }
+            if (a.d_in) {
+                PiecesB<HB> y[CT];
+#pragma unroll
+                for (int cb = 0; cb < HB; ++cb) {
+                    split_block_single(cb >> 1, cb & 1, d0[cb], y);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                d_in_of(y);
+            }
+        } else {
+            d_in_of(x);
+        }
+    }
+    if (want_bias) flush_bias();
+}

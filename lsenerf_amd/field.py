@@ -105,6 +105,9 @@ class MLP(nn.Module):
             s = math.sqrt(6.0 / (i + o))
             chunks.append((torch.rand(o * i) * 2 - 1) * s)
         self.params = nn.Parameter(torch.cat(chunks))
+        # backward of FROZEN params through lse_mlp_bwd_input (d(input) / d(row_bias) alone).  Set by
+        # LSENeRFModel.freeze_field(input_only_mlp=True) on that model's modules and handed to every ops.fused_mlp call as an argument.
+        self.input_only_bwd = False
 
     def get_out_dim(self) -> int:
         return self.out_dim
@@ -135,7 +138,7 @@ class MLP(nn.Module):
         if self.in_layout == _lib.LSE_IN_LEVELMAJOR:
             xl = x.reshape(n, self.in_dim // 2, 2).permute(1, 0, 2).contiguous()
             if self.in_pad == self.in_dim:
-                out = ops.fused_mlp(self.params, xl, self.meta(), n)
+                out = ops.fused_mlp(self.params, xl, self.meta(), n, input_only=self.input_only_bwd)
             else:
                 kparams, bias = self.split_padding()
                 idx = torch.zeros(n, dtype=torch.int32, device=x.device)
@@ -144,7 +147,7 @@ class MLP(nn.Module):
         else:
             if x.shape[-1] < self.in_pad:
                 x = torch.cat([x, torch.ones(n, self.in_pad - x.shape[-1], device=x.device, dtype=x.dtype)], dim=-1)
-            out = ops.fused_mlp(self.params, x.contiguous(), self.meta(), n)
+            out = ops.fused_mlp(self.params, x.contiguous(), self.meta(), n, input_only=self.input_only_bwd)
         return out[:, : self.out_dim].view(*in_tensor.shape[:-1], self.out_dim)
 
 
@@ -480,7 +483,7 @@ class LSEField(nn.Module):
         mlp = self.mlp_base_mlp
         dens = (sel, self.average_init_density)    # trunc_exp density head fused into the MLP epilogue / backward
         if mlp.in_pad == mlp.in_dim:
-            return ops.fused_mlp(mlp.params, y, mlp.meta(), n, density=dens, n_dev=n_dev)
+            return ops.fused_mlp(mlp.params, y, mlp.meta(), n, density=dens, n_dev=n_dev, input_only=mlp.input_only_bwd)
         if n_dev is not None:
             raise _lib.LseHipError("a device-side sample count needs the 32-input base MLP (L * F == 32)")
         # small grids (L*F < 16): tcnn's ones-padding columns act as a bias shared by every sample
@@ -533,10 +536,12 @@ class LSEField(nn.Module):
         if base.in_pad == base.in_dim and ops.mlp_pair_usable(base.params, y, base.meta(), head.params, head_meta, row_bias,
                                                               ray_idx, packed_info):
             h, sigma, out = ops.fused_mlp_pair(base.params, y, sel, self.average_init_density, base.meta(), head.params, head_meta,
-                                               n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev)
+                                               n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev,
+                                               input_only=base.input_only_bwd and head.input_only_bwd)
             return sigma, h, sel, out
         h, sigma = self._base_mlp(y, sel, n, n_dev)
-        out = ops.fused_mlp(head.params, h, head_meta, n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev)
+        out = ops.fused_mlp(head.params, h, head_meta, n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev,
+                            input_only=head.input_only_bwd)
         return sigma, h, sel, out
 
     def _head_row_bias(self, rays_d: Tensor, emb_idx: Optional[Tensor], emb_table: Optional[Tensor]):
@@ -563,7 +568,8 @@ class LSEField(nn.Module):
         W_in IN PLACE (first-layer view: leading dimension in_pad, column offset 15, column 0 masked) -- the parameter
         vector is never split or copied, and both kernels accumulate their weight gradients straight into its .grad."""
         row_bias, meta = self._head_row_bias(rays_d, emb_idx, emb_table)
-        return ops.fused_mlp(self.mlp_head.params, h, meta, h.shape[0], row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev)
+        return ops.fused_mlp(self.mlp_head.params, h, meta, h.shape[0], row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev,
+                             input_only=self.mlp_head.input_only_bwd)
 
     def _train_emb_table(self):
         if self.embedding_appearance is None:

@@ -492,13 +492,19 @@ class LSENeRFModel(nn.Module):
             fields += list(self.evs_mapper.parameters())
         return fields
 
-    def freeze_field(self, train_embedding: bool = True) -> List[nn.Parameter]:
+    def freeze_field(self, train_embedding: bool = True, input_only_mlp: bool = False) -> List[nn.Parameter]:
         """Freeze the radiance field for a test-time refinement run (R:lse_nerf/lsenerf.py:246-247, R:scripts/emb_eval.sh):
         ``requires_grad_(False)`` on every parameter a training run optimises -- hash table, both MLPs, side heads, mappers,
         ``rgb_to_one`` -- except, with ``train_embedding``, the appearance embedding's (its ``test_emb`` row included once
         ``init_test_params`` has made one).  Returns the parameters left trainable (``[]`` without ``train_embedding``, or without an
         embedding): what the refinement's ``FlatAdam`` is built over.  The step of a frozen field computes no table gradient and
-        hands no frozen parameter a gradient (ops._HashFn, ops._MlpPairFn); ``unfreeze_field`` restores the flags."""
+        hands no frozen parameter a gradient (ops._HashFn, ops._MlpPairFn); ``unfreeze_field`` restores the flags.
+
+        ``input_only_mlp`` (opt-in): the backward of the two frozen MLPs is ``lse_mlp_bwd_input`` -- d(input) and d(row_bias)
+        alone -- instead of the training kernel with its weight-gradient products parked in a scratch.  The flag sits on this
+        model's MLP modules and travels with every call (no other model sees it); no scratch is allocated, so such a model can be
+        captured without an eager step first.  Ray, pose and embedding gradients agree with the default route up to the summation
+        order of the per-ray bias gradient."""
         if self.__dict__.get("_frozen_flags") is not None:
             raise RuntimeError("freeze_field: the field is frozen already (unfreeze_field first)")
         emb = self.field.embedding_appearance
@@ -512,7 +518,9 @@ class LSENeRFModel(nn.Module):
             if id(p) not in keep:
                 p.requires_grad_(False)
         self.__dict__["_frozen_flags"] = flags
-        if self.field.mlp_head.params.is_cuda:
+        for mlp in (self.field.mlp_base_mlp, self.field.mlp_head):
+            mlp.input_only_bwd = bool(input_only_mlp)
+        if self.field.mlp_head.params.is_cuda and not input_only_mlp:
             # where the recomputing MLP backward parks the weight-gradient products of a frozen network: allocated here, outside
             # any graph capture (ops.frozen_wgrad_scratch)
             for mlp in (self.field.mlp_base_mlp, self.field.mlp_head):
@@ -527,6 +535,8 @@ class LSENeRFModel(nn.Module):
             return
         for p, was in flags:
             p.requires_grad_(was)
+        for mlp in (self.field.mlp_base_mlp, self.field.mlp_head):
+            mlp.input_only_bwd = False
         self.__dict__["_frozen_flags"] = None
 
     def init_test_params(self):   # R:lse_nerf/lsenerf.py:251-252

@@ -665,10 +665,31 @@ def frozen_wgrad_scratch(params: torch.Tensor) -> torch.Tensor:
     return s
 
 
+def mlp_input_only_shape(meta: MlpMeta) -> bool:
+    """The calls ``lse_mlp_bwd_input`` serves: the two shapes of the recompute-all backward (act_tiled = 3) in bf16x6 arithmetic."""
+    return (meta.width == 64 and meta.arith == _lib.LSE_MLP_ARITH_AUTO
+            and ((meta.n_in == 16 and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR)
+                 or (meta.n_in == 32 and meta.n_hidden_layers == 1)))
+
+
+@torch.no_grad()
+def mlp_bwd_input(params, x, meta: MlpMeta, n: int, out, out_cols: int, d_out, d_sigma=None, selector=None,
+                  density_scale: float = 0.0, d_in=None, row_bias=None, row_bias_idx=None, d_row_bias=None, n_dev=None) -> None:
+    """``lse_mlp_bwd_input``: the data gradients of a fused MLP with FROZEN parameters -- ``d_in`` (like ``x``; overwritten) and / or
+    ``d_row_bias`` (like ``row_bias``; accumulated) -- from the layer-0 input ``x``, the forward's ``out`` and ``d_out``.  No
+    weight-gradient product is formed and nothing parameter-sized is written.  ``d_in`` is bit-equal to what ``lse_mlp_bwd``
+    (act_tiled = 3) writes.  Head (16 -> 64 -> 64 -> 16, row-major) and base (32 -> 64 -> 16) shapes only: anything else raises."""
+    desc = meta.desc()
+    _call_n("lse_mlp_bwd_input", n_dev, ctypes.byref(desc), _f32(params, "params"), _f32(x, "mlp input"), _f32(out, "out", True),
+            out_cols, _f32(d_out, "d_out"), _f32(d_sigma, "d_sigma", True), _chk(selector, torch.uint8, "selector", True),
+            float(density_scale or 0.0), _f32(d_in, "d_in", True), _f32(row_bias, "row_bias", True),
+            _chk(row_bias_idx, torch.int32, "row_bias_idx", True), _f32(d_row_bias, "d_row_bias", True), n, _stream())
+
+
 class _MlpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, params, x, row_bias, row_bias_idx, bias_packed_info, selector, meta: MlpMeta, n: int, out_cols: int,
-                density_scale, n_dev=None):
+                density_scale, n_dev=None, input_only: bool = False):
         dev = params.device
         out = torch.empty((n, out_cols), dtype=torch.float32, device=dev)
         sigma = torch.empty(n, dtype=torch.float32, device=dev) if density_scale is not None else None
@@ -683,7 +704,9 @@ class _MlpFn(torch.autograd.Function):
         # third generation (mlp_x6.h): nothing is saved, the backward recomputes every hidden layer on the bf16 matrix cores
         # (frozen parameters under a device-side count take it too -- the saved-activation kernels have no count; their weight
         # gradients go to frozen_wgrad_scratch)
-        if tiled and RECOMPUTE_ALL and meta.width == 64 and need_grad and (params.requires_grad or n_dev is not None) \
+        # (input_only: the caller's frozen parameters take the recomputing route whatever the count, for lse_mlp_bwd_input)
+        input_only = bool(input_only) and not params.requires_grad and mlp_input_only_shape(meta)
+        if tiled and RECOMPUTE_ALL and meta.width == 64 and need_grad and (params.requires_grad or n_dev is not None or input_only) \
                 and ((meta.n_in == 16 and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR)
                      or (meta.n_in == 32 and meta.n_hidden_layers == 1)) \
                 and (row_bias is None or not row_bias.requires_grad
@@ -693,7 +716,8 @@ class _MlpFn(torch.autograd.Function):
         n_saved = meta.n_hidden_layers - (1 if tiled == 2 else 0)
         act = torch.empty((n_saved, n_act, meta.width), dtype=torch.float32, device=dev) if (need_grad and tiled != 3) else None
         ctx.act_tiled = tiled
-        ctx.wscratch = frozen_wgrad_scratch(params) if (tiled == 3 and not params.requires_grad) else None
+        ctx.input_only = input_only and tiled == 3        # d(input) / d(row_bias) alone: no weight-gradient products, no scratch
+        ctx.wscratch = frozen_wgrad_scratch(params) if (tiled == 3 and not params.requires_grad and not ctx.input_only) else None
         desc = meta.desc()
         if n_dev is not None and need_grad and tiled != 3:
             raise _lib.LseHipError("a device-side sample count needs the recomputing MLP kernels (width 64, head / base shape)")
@@ -719,6 +743,11 @@ class _MlpFn(torch.autograd.Function):
         d_bias = torch.zeros_like(row_bias) if fused_bias else None
         d_act0 = torch.empty((n, meta.width), dtype=torch.float32, device=dev) if (need_bias and not fused_bias) else None
         d_in = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        if ctx.input_only:       # frozen parameters, head / base shape (a bias gradient here is always the fused one: forward)
+            if d_in is not None or d_bias is not None:
+                mlp_bwd_input(params, x, meta, n, out, out_cols, d_out, d_sigma, selector, ctx.density_scale, d_in, row_bias,
+                              row_bias_idx, d_bias, ctx.n_dev)
+            return None, d_in, d_bias, None, None, None, None, None, None, None, None, None
         direct = _direct_grad(params) if (ctx.needs_input_grad[0] and (ctx.act_tiled or FUSED_WGRAD)) else None
         d_params = direct if direct is not None else (torch.zeros_like(params) if ctx.needs_input_grad[0] else None)
         wgrad_out = d_params if (d_params is not None or ctx.act_tiled != 3) else ctx.wscratch     # act_tiled = 3 always forms them
@@ -756,7 +785,7 @@ class _MlpFn(torch.autograd.Function):
                           ctypes.c_void_p(d_bias.data_ptr()), _stream())
             else:   # unsorted row indices: generic scatter-add (not on the hot path)
                 d_bias = torch.zeros_like(row_bias).index_add_(0, row_bias_idx.long(), d_act0)
-        return (None if direct is not None else d_params), d_in, d_bias, None, None, None, None, None, None, None, None
+        return (None if direct is not None else d_params), d_in, d_bias, None, None, None, None, None, None, None, None, None
 
 
 def _mlp_pair_shapes(base_meta: MlpMeta, head_meta: MlpMeta) -> bool:
@@ -775,7 +804,7 @@ class _MlpPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, base_meta: MlpMeta,
-                head_meta: MlpMeta, n: int, out_cols: int, density_scale, n_dev=None):
+                head_meta: MlpMeta, n: int, out_cols: int, density_scale, n_dev=None, input_only: bool = False):
         dev = base_params.device
         h = torch.empty((n, 16), dtype=torch.float32, device=dev)
         sigma = torch.empty(n, dtype=torch.float32, device=dev)
@@ -791,9 +820,13 @@ class _MlpPairFn(torch.autograd.Function):
             base_meta, head_meta, n, out_cols, density_scale, n_dev
         # frozen parameters: the recomputing backward still forms the weight-gradient products; they go where nothing reads them
         need_grad = any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
-        ctx.head_scratch = frozen_wgrad_scratch(head_params) if (need_grad and not head_params.requires_grad) else None
+        # (input_only: a frozen network's backward is lse_mlp_bwd_input, which forms none -- no scratch is created or touched)
+        ctx.head_input_only = bool(input_only) and not head_params.requires_grad and mlp_input_only_shape(head_meta)
+        ctx.base_input_only = bool(input_only) and not base_params.requires_grad and mlp_input_only_shape(base_meta)
+        ctx.head_scratch = frozen_wgrad_scratch(head_params) if (need_grad and not head_params.requires_grad
+                                                                 and not ctx.head_input_only) else None
         ctx.base_scratch = frozen_wgrad_scratch(base_params) if (need_grad and not base_params.requires_grad
-                                                                 and y.requires_grad) else None
+                                                                 and y.requires_grad and not ctx.base_input_only) else None
         ctx.set_materialize_grads(False)
         return h, sigma, out
 
@@ -803,7 +836,16 @@ class _MlpPairFn(torch.autograd.Function):
         n, out_cols, dev = ctx.n, ctx.out_cols, base_params.device
         # ---- head (the call of _MlpFn.backward at act_tiled = 3)
         d_in_head, d_bias, d_hp_ret = None, None, None
-        if d_out is not None:
+        if d_out is not None and ctx.head_input_only:
+            # frozen head: its d_in is wanted only where the base launch below will run (not in the embedding-only phase)
+            d_out = _c(d_out)
+            need_bias = row_bias is not None and ctx.needs_input_grad[4]
+            d_bias = torch.zeros_like(row_bias) if need_bias else None
+            d_in_head = torch.empty_like(h) if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else None
+            if d_in_head is not None or d_bias is not None:
+                mlp_bwd_input(head_params, h, ctx.head_meta, n, out, out_cols, d_out, None, None, 0.0, d_in_head, row_bias,
+                              row_bias_idx, d_bias, ctx.n_dev)
+        elif d_out is not None:
             d_out = _c(d_out)
             need_bias = row_bias is not None and ctx.needs_input_grad[4]
             d_bias = torch.zeros_like(row_bias) if need_bias else None
@@ -830,6 +872,10 @@ class _MlpPairFn(torch.autograd.Function):
             d_base = _c(d_base) if d_base is not None else torch.zeros((n, 16), dtype=torch.float32, device=dev)
             d_sigma = _c(d_sigma) if d_sigma is not None else None
             d_y = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+            if ctx.base_input_only:      # frozen base: this branch runs for d_y alone
+                mlp_bwd_input(base_params, y, ctx.base_meta, n, h, 16, d_base, d_sigma, selector, ctx.density_scale, d_y,
+                              n_dev=ctx.n_dev)
+                return None, d_y, None, d_hp_ret, d_bias, None, None, None, None, None, None, None, None, None
             if ctx.needs_input_grad[0]:
                 direct = _direct_grad(base_params)
                 d_bp = direct if direct is not None else torch.zeros_like(base_params)
@@ -841,7 +887,7 @@ class _MlpPairFn(torch.autograd.Function):
                     _f32(h, "out"), 16, _f32(d_base, "d_out"), _f32(d_sigma, "d_sigma", True),
                     _chk(selector, torch.uint8, "selector", True), float(ctx.density_scale), None, None, None,
                     _f32(d_y, "d_in", True), _f32(d_bp, "d_params"), None, None, None, n, _stream())
-        return d_bp_ret, d_y, None, d_hp_ret, d_bias, None, None, None, None, None, None, None, None
+        return d_bp_ret, d_y, None, d_hp_ret, d_bias, None, None, None, None, None, None, None, None, None
 
 
 def mlp_pair_usable(base_params, y, base_meta: MlpMeta, head_params, head_meta: MlpMeta, row_bias, row_bias_idx,
@@ -862,12 +908,13 @@ def mlp_pair_usable(base_params, y, base_meta: MlpMeta, head_params, head_meta: 
 
 
 def fused_mlp_pair(base_params, y, selector, density_scale, base_meta: MlpMeta, head_params, head_meta: MlpMeta, n: int,
-                   row_bias=None, row_bias_idx=None, bias_packed_info=None, out_cols: int = 4, n_dev=None):
+                   row_bias=None, row_bias_idx=None, bias_packed_info=None, out_cols: int = 4, n_dev=None,
+                   input_only: bool = False):
     """``fused_mlp(base_params, y, base_meta, n, density=(selector, density_scale))`` followed by ``fused_mlp(head_params, h,
     head_meta, n, row_bias, row_bias_idx, bias_packed_info, out_cols)`` with one forward launch; returns ``(h[n,16], sigma[n],
-    out[n,out_cols])`` with the same bits.  Callers check ``mlp_pair_usable`` first."""
+    out[n,out_cols])`` with the same bits.  Callers check ``mlp_pair_usable`` first.  ``input_only``: as in ``fused_mlp``."""
     return _MlpPairFn.apply(base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, base_meta, head_meta,
-                            n, out_cols, density_scale, n_dev)
+                            n, out_cols, density_scale, n_dev, input_only)
 
 
 # Hooks into the hash backward, keyed by the TABLE they belong to (its storage address): a second model in the same process -- an
@@ -923,13 +970,16 @@ FUSED_RAY_GRAD = True   # ray path of the positions backward: one launch (lse_ra
 
 
 def fused_mlp(params, x, meta: MlpMeta, n: int, row_bias=None, row_bias_idx=None, bias_packed_info=None,
-              out_cols: int = 16, density=None, n_dev=None):
+              out_cols: int = 16, density=None, n_dev=None, input_only: bool = False):
     """Bias-free fused MLP (tcnn layout).  Returns the padded output [n, 16] (or the compact [n, 4] = outputs 0..3).
     ``row_bias[rows, width]`` is added to the layer-0 pre-activation of sample i from row ``row_bias_idx[i]``;
     ``bias_packed_info[rows, 2]`` (start, count) must describe those rows' contiguous sample segments.
-    ``density=(selector_or_None, scale)`` fuses the trunc_exp density head on output 0 and returns ``(out, sigma[n])``."""
+    ``density=(selector_or_None, scale)`` fuses the trunc_exp density head on output 0 and returns ``(out, sigma[n])``.
+    ``input_only`` (this call's, not the process's): where ``params`` is frozen (``requires_grad == False``) and the shape is the
+    head's or the base's, the backward is ``lse_mlp_bwd_input`` -- d(input) and d(row_bias) alone, no weight-gradient products and
+    no ``frozen_wgrad_scratch``; everywhere else it changes nothing."""
     selector, scale = (None, None) if density is None else density
-    return _MlpFn.apply(params, x, row_bias, row_bias_idx, bias_packed_info, selector, meta, n, out_cols, scale, n_dev)
+    return _MlpFn.apply(params, x, row_bias, row_bias_idx, bias_packed_info, selector, meta, n, out_cols, scale, n_dev, input_only)
 
 
 # ----------------------------------------------------------------------------------------------------

@@ -11,9 +11,17 @@ device time (HIP events) of lse_hash_fwd, lse_hash_bwd_ex and lse_hash_bwd_input
 spent in its two lse_mlp_bwd launches, which still form the weight-gradient products of the frozen networks -- what a
 data-gradient-only MLP backward could save at most.
 
+The input-gradient-only MLP backward (freeze_field(input_only_mlp=True), lse_mlp_bwd_input) against that default route, A/B in the same
+process with the routes alternating:
+  kernels: inside the eager frozen camera-only step, on the very arguments of its two lse_mlp_bwd launches -- the head with d_in +
+           d_row_bias, the head with d_row_bias alone (what the embedding-only phase asks for), the base -- lse_mlp_bwd (weight
+           gradients into the scratch) and lse_mlp_bwd_input, two repeats of each (median of 8 timed calls);
+  steps:   (ii) and (iii) captured once more with the flag, replayed in the same interleaved rounds.
+Spread = the larger difference between the repeats (rounds) of either route; bar: new <= old - 2 x spread, for each comparison.
+
 Exit status 1 when lse_hash_bwd_input takes longer than 1.5 x lse_hash_fwd on the same inputs in the same run (the two kernels issue
 the same gathers and move the same bytes per sample; the factor covers three times the multiply-adds and the wider register
-footprint).  The step-level ratios are reported, not barred.
+footprint), or when an A/B bar above is missed.  The other step-level ratios are reported, not barred.
 
 Usage: python tools/bench_refine.py [--out profiles/refine_step.txt] [--replays 20] [--rounds 3]"""
 import argparse
@@ -153,6 +161,66 @@ def mlp_bwd_ms_of_an_eager_frozen_step(model, bundles, batch, steps=5):
     return statistics.median(per_step), launches
 
 
+def ab_verdict(old, new):
+    """(old median, new median, spread, new <= old - 2 x spread) of two routes' repeats."""
+    spread = max(max(old) - min(old), max(new) - min(new))
+    o, n = statistics.median(old), statistics.median(new)
+    return o, n, spread, n <= o - 2.0 * spread
+
+
+def mlp_bwd_kernel_ab(model, bundles, batch, repeats=2, iters=8):
+    """lse_mlp_bwd against lse_mlp_bwd_input on the arguments of the two lse_mlp_bwd launches of ONE eager frozen camera-only step
+    (the default route): the launches are intercepted where they happen, so every operand is the step's own.  Returns
+    {comparison: {"old": [ms per repeat], "new": [...]}}.  (The step's gradients are garbage afterwards: d_row_bias accumulates.)"""
+    from lsenerf_amd import RayBundle
+    out, real = {}, _lib.call
+
+    def timed(f):
+        ts = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); f(); e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    def hook(name, *a):
+        if name != "lse_mlp_bwd":
+            return real(name, *a)
+        (desc, params, x, _act, _tiled, o, oc, d_out, d_sig, sel, scale, _pre, _dact, _dact0, d_in, d_par, rb, idx, d_rb, n, n_dev, st) = a
+        head = desc._obj.n_in == 16
+
+        def routes(di):
+            old = lambda: real("lse_mlp_bwd", desc, params, x, None, 3, o, oc, d_out, d_sig, sel, scale, None, None, None, di, d_par, rb, idx,
+                               d_rb, n, n_dev, st)
+            new = lambda: real("lse_mlp_bwd_input", desc, params, x, o, oc, d_out, d_sig, sel, scale, di, rb, idx, d_rb, n, n_dev, st)
+            return {"old": old, "new": new}
+        todo = {"head, d_in + d_row_bias": routes(d_in), "head, d_row_bias alone": routes(None)} if head else {"base, d_in": routes(d_in)}
+        for what, fs in todo.items():
+            res = {k: [] for k in fs}
+            for f in fs.values():
+                f(); f()
+            for _ in range(repeats):
+                for k, f in fs.items():      # the routes alternate
+                    res[k].append(timed(f))
+            out[what] = res
+        return real(name, *a)
+
+    bs = [None if b is None else RayBundle(origins=b.origins.detach().clone().requires_grad_(True),
+                                           directions=b.directions.detach().clone().requires_grad_(True), camera_indices=b.camera_indices,
+                                           fars=b.fars, metadata=b.metadata) for b in bundles]
+    _lib.call = hook
+    try:
+        _, losses, _ = model.train_step_bundles(*bs, batch)
+        sum(losses.values()).backward()
+        torch.cuda.synchronize()
+    finally:
+        _lib.call = real
+    for p in model.parameters():
+        p.grad = None
+    return out
+
+
 def replay_ms(step, args, n):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -176,10 +244,17 @@ def run_workload(name, build, device, replays, rounds, log):
     assert model.freeze_field(train_embedding=False) == []
     steps["ii"] = GraphedTrainStep(model, None, *args, ray_grads=True)
     mlp_ms, mlp_launches = mlp_bwd_ms_of_an_eager_frozen_step(model, bundles, batch)
+    kernel_ab = mlp_bwd_kernel_ab(model, bundles, batch)
+    model.unfreeze_field()
+    assert model.freeze_field(train_embedding=False, input_only_mlp=True) == []
+    steps["ii+"] = GraphedTrainStep(model, None, *args, ray_grads=True)
     model.unfreeze_field()
     left = model.freeze_field()
     opt_emb = FlatAdam(FlatParams(left), lr=1e-3, eps=1e-15)
     steps["iii"] = GraphedTrainStep(model, opt_emb, *args, ray_grads=False)
+    model.unfreeze_field()
+    assert [id(p) for p in model.freeze_field(input_only_mlp=True)] == [id(p) for p in left]
+    steps["iii+"] = GraphedTrainStep(model, opt_emb, *args, ray_grads=False)      # (the same embedding optimiser: timing only)
     for s in steps.values():
         replay_ms(s, args, 5)
     ms = {k: [] for k in steps}
@@ -206,7 +281,21 @@ def run_workload(name, build, device, replays, rounds, log):
     log(f"  lse_hash_bwd_input / lse_hash_fwd = {ratio:.3f}   (bar {BAR})")
     log(f"  lse_mlp_bwd in the eager frozen camera-only step: {mlp_launches} launches, {mlp_ms:.3f} ms = {100 * mlp_ms / step_ms['ii']:.1f} % of (ii) "
         f"-- the ceiling of what a data-gradient-only MLP backward could save")
-    return ratio
+    ok = True
+    log("  input-gradient-only MLP backward, kernels on the step's own arguments (ms; repeats alternate old, new, old, new):")
+    for what, r in kernel_ab.items():
+        o, n, spread, good = ab_verdict(r["old"], r["new"])
+        ok &= good
+        log(f"    {what:26s} lse_mlp_bwd {['%.4f' % v for v in r['old']]}  lse_mlp_bwd_input {['%.4f' % v for v in r['new']]}  "
+            f"new/old = {n / o:.3f}  spread {spread:.4f}  bar new <= {o - 2 * spread:.4f}: {'met' if good else 'MISSED'}")
+    log("  the same through the captured steps (flag = freeze_field(input_only_mlp=True); rounds interleaved with the ones above):")
+    for what, a, b in (("(ii)  camera-only", "ii", "ii+"), ("(iii) embedding-only", "iii", "iii+")):
+        o, n, spread, good = ab_verdict(ms[a], ms[b])
+        ok &= good
+        log(f"    {what:22s} default {['%.3f' % v for v in ms[a]]}  flag {['%.3f' % v for v in ms[b]]}  saved {o - n:.3f} ms "
+            f"(new/old = {n / o:.3f})  spread {spread:.3f}  bar: {'met' if good else 'MISSED'}"
+            + (f"  = {100 * (o - n) / mlp_ms:.0f} % of this run's {mlp_ms:.3f} ms ceiling" if a == "ii" else ""))
+    return ratio, ok
 
 
 def main():
@@ -224,15 +313,18 @@ def main():
         print(s, flush=True)
         lines.append(s)
     log(f"tools/bench_refine.py --replays {a.replays} --rounds {a.rounds}   ({torch.cuda.get_device_name(0)})")
-    ratios = {}
+    ratios, ab_ok = {}, {}
     try:
         for name, build in (("headline workload", headline_workload), ("reference default batch", default_batch_workload)):
-            ratios[name] = run_workload(name, build, device, a.replays, a.rounds, log)
+            ratios[name], ab_ok[name] = run_workload(name, build, device, a.replays, a.rounds, log)
     finally:
         M.gbconfig.IS_EVAL = False
     ok = all(r <= BAR for r in ratios.values())
     log(("PASS" if ok else "FAIL") + f": lse_hash_bwd_input <= {BAR} x lse_hash_fwd on both workloads: " +
         ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+    log(("PASS" if all(ab_ok.values()) else "FAIL") + ": lse_mlp_bwd_input <= lse_mlp_bwd - 2 x spread, kernels and steps: " +
+        ", ".join(f"{k} {'met' if v else 'missed'}" for k, v in ab_ok.items()))
+    ok = ok and all(ab_ok.values())
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
