@@ -1539,7 +1539,7 @@ int launch_bwd(const MlpArgs &a, hipStream_t st)
 {
     const int cfg = (int)lse::option("mlp_bwd_cfg");   // CT*10 + NW
     if (a.act_tiled == 3) {     // nothing saved: third generation, hidden layers recomputed on the bf16 matrix cores (mlp_x6.h)
-        if constexpr (WIDTH == 64 && ((KIN == 16 && NHL == 2 && INL == LSE_IN_ROWMAJOR) || (KIN == 32 && NHL == 1))) {
+        if constexpr (x6_recompute_shape(KIN, WIDTH, NHL, INL)) {
             if (a.d_params && !a.d_out_pre && !a.d_act && !a.d_act0) {
                 if (a.row_bias && a.d_row_bias && a.w0_mask0) return launch_bwd3<KIN, NHL, INL, true, true>(a, st);
                 if (a.row_bias) return launch_bwd3<KIN, NHL, INL, true, false>(a, st);
@@ -1749,9 +1749,7 @@ extern "C" int lse_mlp_bwd_input(const lse_mlp_desc *desc, const float *params, 
     int rc = check_desc(desc, "lse_mlp_bwd_input");
     if (rc) return rc;
     LSE_REQUIRE(n >= 0, "lse_mlp_bwd_input: n < 0");
-    const bool head = desc->n_in == 16 && desc->width == 64 && desc->n_hidden_layers == 2 && desc->in_layout == LSE_IN_ROWMAJOR;
-    const bool base = desc->n_in == 32 && desc->width == 64 && desc->n_hidden_layers == 1;
-    if (!head && !base) {
+    if (!x6_recompute_shape(desc->n_in, desc->width, desc->n_hidden_layers, desc->in_layout)) {
         lse::set_error("lse_mlp_bwd_input: built for the 16->64->64->16 row-major head and the 32->64->16 base only (got n_in=%d "
                        "width=%d n_hidden_layers=%d in_layout=%d)",
                        desc->n_in, desc->width, desc->n_hidden_layers, desc->in_layout);
@@ -1778,7 +1776,7 @@ extern "C" int lse_mlp_bwd_input(const lse_mlp_desc *desc, const float *params, 
     a.row_bias = row_bias; a.row_bias_idx = row_bias_idx; a.d_row_bias = d_row_bias;
     fill_view(a, desc);
     hipStream_t st = lse::as_stream(stream);
-    if (head) return launch_bwd_input<16, 2, LSE_IN_ROWMAJOR>(a, st);
+    if (desc->n_in == 16) return launch_bwd_input<16, 2, LSE_IN_ROWMAJOR>(a, st);
     if (desc->in_layout == LSE_IN_LEVELMAJOR) return launch_bwd_input<32, 1, LSE_IN_LEVELMAJOR>(a, st);
     return launch_bwd_input<32, 1, LSE_IN_ROWMAJOR>(a, st);
 }

@@ -70,6 +70,22 @@ __device__ __forceinline__ void neg_identity(int lane, u32x4 (&nI)[2])
     }
 }
 
+// The two "minus identity" operands kept in LDS, 128 entries of 16 bytes (registers are the scarce resource of these kernels: 8
+// less, one more wave per SIMD for the base forward): staged once per workgroup, read where a split needs them.
+__device__ __forceinline__ void stage_neg_identity(u32x4 *dst)
+{
+    if (threadIdx.x < 64) {
+        u32x4 t[2];
+        neg_identity(threadIdx.x, t);
+        dst[threadIdx.x] = t[0];
+        dst[64 + threadIdx.x] = t[1];
+    }
+}
+struct NegI {
+    const u32x4 *p;          // the staged operands + this thread's lane
+    __device__ __forceinline__ u32x4 operator[](int b) const { return p[64 * b]; }
+};
+
 // c0, c1 -> pieces o[hi, mid, lo]; c0 / c1 are consumed (they end as the third remainders)
 template <typename NI>
 __device__ __forceinline__ void split_pair(f32x4 c0, f32x4 c1, const NI &nI, u32x4 (&o)[3])
@@ -231,6 +247,72 @@ __device__ __forceinline__ void stage_in16_image(u32x4 *img, const float *W, int
     }
 }
 
+// ---- the tile walk of every kernel of this file: tiles of 16 * CT samples, one contiguous range of tiles per wave ----
+template <int CT, int NW>
+__device__ __forceinline__ void wave_tile_range(int64_t n, int wave, int64_t &t_begin, int64_t &t_end)
+{
+    constexpr int TS = 16 * CT;
+    const int64_t n_tiles = (n + TS - 1) / TS;
+    const int64_t total_waves = (int64_t)gridDim.x * NW;
+    const int64_t per = (n_tiles + total_waves - 1) / total_waves;
+    const int64_t w_id = (int64_t)blockIdx.x * NW + wave;
+    t_begin = min(n_tiles, w_id * per);
+    t_end = min(n_tiles, t_begin + per);
+}
+
+// this lane's sample of each column tile (the last valid one where its own is past the end); returns the tile's number of valid
+// samples (wave-uniform, >= 1)
+template <int CT>
+__device__ __forceinline__ int tile_lanes(int64_t n, int64_t tile_base, int j, int (&sl)[CT], bool (&valid)[CT])
+{
+    const int n_rem = (int)min((int64_t)(16 * CT), n - tile_base);
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        valid[ct] = ct * 16 + j < n_rem;
+        sl[ct] = valid[ct] ? ct * 16 + j : n_rem - 1;
+    }
+    return n_rem;
+}
+
+// the row-bias rows of this lane's samples in the tile that starts at sample b0: requested one tile ahead, so that the bias
+// loads never wait for them
+template <int CT>
+__device__ __forceinline__ void request_bias_rows(const int32_t *row_bias_idx, int64_t n, int64_t b0, int j, int (&rows)[CT])
+{
+    const int nr = (int)min((int64_t)(16 * CT), n - b0);
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) rows[ct] = row_bias_idx[b0 + min(ct * 16 + j, nr - 1)];
+}
+
+// forward: the first layer's accumulators start as the per-row bias (rows_nx = the look-ahead of request_bias_rows) or as zero
+template <int HB, int WIDTH, int CT>
+__device__ __forceinline__ void init_h_from_row_bias(const MlpArgs &a, int64_t n, int64_t tile, int64_t t_end, int j, int q,
+                                                     const int (&sl)[CT], int (&rows_nx)[CT], f32x4 (&h)[HB][CT])
+{
+    if (a.row_bias) {
+        int64_t rowv[CT];
+        if (a.row_bias_idx) {      // this tile's rows were requested during the previous tile; the next tile's are requested now
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) rowv[ct] = rows_nx[ct];
+            if (tile + 1 < t_end) request_bias_rows<CT>(a.row_bias_idx, n, (tile + 1) * (16 * CT), j, rows_nx);
+        } else {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) rowv[ct] = tile * (16 * CT) + sl[ct];
+        }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            const int64_t row = rowv[ct];
+#pragma unroll
+            for (int rb = 0; rb < HB; ++rb) h[rb][ct] = *reinterpret_cast<const f32x4 *>(a.row_bias + row * WIDTH + 16 * rb + 4 * q);
+        }
+    } else {
+#pragma unroll
+        for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------
 // forward (third generation).  Same tile walk, prefetch, activation layout and stores as mlp_fwd2_kernel; WIDTH = 64.
 //   KIN = 16 row-major (head) or 32 level-major / row-major (base).
@@ -306,49 +388,27 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
     else stage_in32_image<HB>(img0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
     if constexpr (NHL == 2) stage_chain_image<HB, 2>(imgH, W1, WIDTH, WIDTH, 64 * NW);
     stage_chain_image<1, 2>(imgO, Wo, WIDTH, 16, 64 * NW);
-    if (threadIdx.x < 64) {
-        u32x4 t[2];
-        neg_identity(threadIdx.x, t);
-        imgO[C::IMGO + threadIdx.x] = t[0];
-        imgO[C::IMGO + 64 + threadIdx.x] = t[1];
-    }
+    stage_neg_identity(imgO + C::IMGO);
     __syncthreads();
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
     a.n = lse::clamp_count(a.n, a.n_dev);
     const int64_t n = a.n;
-    const int64_t n_tiles = (n + TS - 1) / TS;
-    const int64_t total_waves = (int64_t)gridDim.x * NW;
-    const int64_t per = (n_tiles + total_waves - 1) / total_waves;
-    const int64_t w_id = (int64_t)blockIdx.x * NW + wave;
-    const int64_t t_begin = min(n_tiles, w_id * per), t_end = min(n_tiles, t_begin + per);
+    int64_t t_begin, t_end;
+    wave_tile_range<CT, NW>(n, wave, t_begin, t_end);
     const int oc = a.out_cols;
-    struct NegI {          // "minus identity" operands from LDS (8 registers less: one more wave per SIMD for the base shape)
-        const u32x4 *p;
-        __device__ __forceinline__ u32x4 operator[](int b) const { return p[64 * b]; }
-    };
     const NegI nI{imgO + C::IMGO + lane};
 
     f32x4 raw_nx[CT][KIN / 16];
     if (t_begin < t_end) load_in_x6<KIN, INL, CT>(a, t_begin, j, q, raw_nx);
     int idx_nx[CT] = {};
-    if (a.row_bias && a.row_bias_idx && t_begin < t_end) {
-        const int64_t b0 = t_begin * TS;
-        const int nr = (int)min((int64_t)TS, n - b0);
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) idx_nx[ct] = a.row_bias_idx[b0 + min(ct * 16 + j, nr - 1)];
-    }
+    if (a.row_bias && a.row_bias_idx && t_begin < t_end) request_bias_rows<CT>(a.row_bias_idx, n, t_begin * TS, j, idx_nx);
     for (int64_t tile = t_begin; tile < t_end; ++tile) {
         const int64_t tile_base = tile * TS;
-        const int n_rem = (int)min((int64_t)TS, n - tile_base);
         int sl[CT];
         bool valid[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            valid[ct] = ct * 16 + j < n_rem;
-            sl[ct] = valid[ct] ? ct * 16 + j : n_rem - 1;
-        }
+        const int n_rem = tile_lanes<CT>(n, tile_base, j, sl, valid);
         f32x4 raw[CT][KIN / 16];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
@@ -359,34 +419,7 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) selv[ct] = (a.sigma_out && a.selector && q == 0) ? (uint32_t)a.selector[tile_base + sl[ct]] : 1u;
         f32x4 h[HB][CT];
-        if (a.row_bias) {
-            int64_t rowv[CT];
-            if (a.row_bias_idx) {      // this tile's rows were requested during the previous tile; the next tile's are requested now
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) rowv[ct] = idx_nx[ct];
-                if (tile + 1 < t_end) {
-                    const int64_t nb_ = tile_base + TS;
-                    const int nr = (int)min((int64_t)TS, n - nb_);
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) idx_nx[ct] = a.row_bias_idx[nb_ + min(ct * 16 + j, nr - 1)];
-                }
-            } else {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) rowv[ct] = tile_base + sl[ct];
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                const int64_t row = rowv[ct];
-#pragma unroll
-                for (int rb = 0; rb < HB; ++rb)
-                    h[rb][ct] = *reinterpret_cast<const f32x4 *>(a.row_bias + row * WIDTH + 16 * rb + 4 * q);
-            }
-        } else {
-#pragma unroll
-            for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
+        init_h_from_row_bias<HB, WIDTH, CT>(a, n, tile, t_end, j, q, sl, idx_nx, h);
         if (tile + 1 < t_end) load_in_x6<KIN, INL, CT>(a, tile + 1, j, q, raw_nx);
         // ---- layer 0
         first_layer_x6<KIN, CT>(h, img0, raw, nI, lane);
@@ -485,49 +518,27 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
     stage_in16_image<HB>(h_img0, b.params + b.w0_col, b.w0_ld, b.w0_mask0, 64 * NW);
     stage_chain_image<HB, 2>(h_imgH, b.params + b.rest_off, WIDTH, WIDTH, 64 * NW);
     stage_chain_image<1, 2>(h_imgO, b.params + b.rest_off + WIDTH * WIDTH, WIDTH, 16, 64 * NW);
-    if (threadIdx.x < 64) {
-        u32x4 t[2];
-        neg_identity(threadIdx.x, t);
-        img[C::NEGI + threadIdx.x] = t[0];
-        img[C::NEGI + 64 + threadIdx.x] = t[1];
-    }
+    stage_neg_identity(img + C::NEGI);
     __syncthreads();
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
     a.n = lse::clamp_count(a.n, a.n_dev);
     const int64_t n = a.n;
-    const int64_t n_tiles = (n + TS - 1) / TS;
-    const int64_t total_waves = (int64_t)gridDim.x * NW;
-    const int64_t per = (n_tiles + total_waves - 1) / total_waves;
-    const int64_t w_id = (int64_t)blockIdx.x * NW + wave;
-    const int64_t t_begin = min(n_tiles, w_id * per), t_end = min(n_tiles, t_begin + per);
+    int64_t t_begin, t_end;
+    wave_tile_range<CT, NW>(n, wave, t_begin, t_end);
     const int oc = b.out_cols;
-    struct NegI {          // "minus identity" operands from LDS, as in mlp_fwd3_kernel
-        const u32x4 *p;
-        __device__ __forceinline__ u32x4 operator[](int k) const { return p[64 * k]; }
-    };
     const NegI nI{img + C::NEGI + lane};
 
     f32x4 raw_nx[CT][2];
     if (t_begin < t_end) load_in_x6<32, INL, CT>(a, t_begin, j, q, raw_nx);
     int idx_nx[CT] = {};
-    if (b.row_bias && b.row_bias_idx && t_begin < t_end) {
-        const int64_t b0 = t_begin * TS;
-        const int nr = (int)min((int64_t)TS, n - b0);
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) idx_nx[ct] = b.row_bias_idx[b0 + min(ct * 16 + j, nr - 1)];
-    }
+    if (b.row_bias && b.row_bias_idx && t_begin < t_end) request_bias_rows<CT>(b.row_bias_idx, n, t_begin * TS, j, idx_nx);
     for (int64_t tile = t_begin; tile < t_end; ++tile) {
         const int64_t tile_base = tile * TS;
-        const int n_rem = (int)min((int64_t)TS, n - tile_base);
         int sl[CT];
         bool valid[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            valid[ct] = ct * 16 + j < n_rem;
-            sl[ct] = valid[ct] ? ct * 16 + j : n_rem - 1;
-        }
+        tile_lanes<CT>(n, tile_base, j, sl, valid);
         f32x4 o[1][CT];
         // ================= base: 32 -> 64 -> 16, density head =================
         {
@@ -573,34 +584,7 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
         // ================= head: 16 (+ per-row bias) -> 64 -> 64 -> 16, input = o[0][ct] =================
         {
             f32x4 h[HB][CT];
-            if (b.row_bias) {
-                int64_t rowv[CT];
-                if (b.row_bias_idx) {      // this tile's rows were requested during the previous tile; the next tile's are requested now
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) rowv[ct] = idx_nx[ct];
-                    if (tile + 1 < t_end) {
-                        const int64_t nb_ = tile_base + TS;
-                        const int nr = (int)min((int64_t)TS, n - nb_);
-#pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) idx_nx[ct] = b.row_bias_idx[nb_ + min(ct * 16 + j, nr - 1)];
-                    }
-                } else {
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) rowv[ct] = tile_base + sl[ct];
-                }
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    const int64_t row = rowv[ct];
-#pragma unroll
-                    for (int rb = 0; rb < HB; ++rb)
-                        h[rb][ct] = *reinterpret_cast<const f32x4 *>(b.row_bias + row * WIDTH + 16 * rb + 4 * q);
-                }
-            } else {
-#pragma unroll
-                for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
+            init_h_from_row_bias<HB, WIDTH, CT>(b, n, tile, t_end, j, q, sl, idx_nx, h);
             f32x4 rawh[CT][1];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) rawh[ct][0] = o[0][ct];
@@ -740,15 +724,217 @@ __device__ __forceinline__ void combos16_lds(F rd, u32x4 (&c)[3])
     c[2] = (u32x4){h1[0], h1[1], m1[0], m1[1]};
 }
 
-template <int KIN, int NHL, int CT, int NW>
-struct X6Bwd {
+// ---- what mlp_bwd3_kernel and mlp_bwd_input_kernel share: each stage below is written once and called by both ----
+
+// the shapes both kernels are built for (width 64): the head 16 -> 64 -> 64 -> 16 on a row-major input, the base 32 -> 64 -> 16
+__host__ __device__ constexpr bool x6_recompute_shape(int n_in, int width, int n_hidden_layers, int in_layout)
+{
+    return width == 64 && ((n_in == 16 && n_hidden_layers == 2 && in_layout == LSE_IN_ROWMAJOR) || (n_in == 32 && n_hidden_layers == 1));
+}
+
+// LDS, weight side: the plain piece images [W0 | W1 | Wo], then the two "minus identity" operands
+template <int KIN, int NHL>
+struct X6BwdImg {
     static constexpr int S0 = KIN / 16;
     static constexpr int W0_PIECE = 64 * 32 * S0, W1_PIECE = (NHL == 2) ? 64 * 128 : 0, WO_PIECE = 16 * 128;
     static constexpr int W_BYTES = 3 * (W0_PIECE + W1_PIECE + WO_PIECE);
+    static constexpr int NI_BYTES = 2 * 1024;                 // one 16-byte entry per lane and operand
+};
+
+// the layer-0 input of a tile as the B operands of the first layer's products (one member is used: k = 16 or k = 32)
+template <int CT>
+struct InPieces {
+    PiecesB16 x16[CT];
+    u32x4 x[CT][3];
+};
+// cut the layer-0 input of a tile into those operands
+template <int KIN, int CT>
+__device__ __forceinline__ void split_input(const f32x4 (&raw)[CT][KIN / 16], const NegI &nI, InPieces<CT> &xin)
+{
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        if constexpr (KIN == 16) split_in16(raw[ct][0], nI, xin.x16[ct]);
+        else split_pair(raw[ct][0], raw[ct][1], nI, xin.x[ct]);
+    }
+}
+
+
+// pieces of two accumulator row blocks 2s2, 2s2+1 (= one k slab of the next product), both column tiles: the base shape (MS)
+template <bool MS, int CT>
+__device__ __forceinline__ void split_blocks(const NegI &nI, int s2, const f32x4 (&c0)[CT], const f32x4 (&c1)[CT], PiecesB<4> (&x)[CT])
+{
+    if constexpr (MS) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) split_pair(c0[ct], c1[ct], nI, x[ct].p[s2]);
+    }
+}
+// head shape (registers are scarce): one block at a time, as soon as it is complete -- the same two remainder MFMAs per block as
+// the paired form (the unused half of the B operand is zero)
+template <bool MS, int CT>
+__device__ __forceinline__ void split_block_single(const NegI &nI, int s2, int b, const f32x4 (&c)[CT], PiecesB<4> (&x)[CT])
+{
+    if constexpr (!MS) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            uint32_t hi[2], mid[2], lo[2];
+            split_half(c[ct], nI, hi, mid, lo);
+#pragma unroll
+            for (int w2 = 0; w2 < 2; ++w2) {
+                x[ct].p[s2][0][2 * b + w2] = hi[w2];
+                x[ct].p[s2][1][2 * b + w2] = mid[w2];
+                x[ct].p[s2][2][2 * b + w2] = lo[w2];
+            }
+        }
+    }
+}
+
+// The weight images of a workgroup and this lane's view of them: staging, per-lane byte offsets, readers.
+template <int KIN, int NHL>
+struct X6BwdW {
+    using C = X6BwdImg<KIN, NHL>;
+    uint8_t *imgW0, *imgW1, *imgWo;
+    NegI nI;
+    // Per-lane byte offsets, computed once: every LDS address is one of these + a compile-time constant (the DS instructions'
+    // immediate offset), so the address arithmetic costs no registers inside the tile loop.
+    //   "row" accesses   : image row 16X + j, 8-byte chunk q of segment seg          (128-byte rows: so_j[seg] + 2048 X)
+    //   "transposed" ones: image row 8X + 4q + tq, 8-byte chunk tp of segment seg    (128-byte rows: so_t[seg] + 1024 X)
+    int so_j[4], so_t[4];
+    int sm_j, sm_t;          // 32-byte rows (small tile, 16-column W0)
+    int w0b_j, w0b_t[2];     // 64-byte rows (32-column W0): 16-byte row read / transposed
+
+    // cut the three matrices into LDS (all NW waves), write the "minus identity" operands, barrier
+    template <int NW>
+    __device__ __forceinline__ void stage(float *lds, const MlpArgs &a)
+    {
+        imgW0 = reinterpret_cast<uint8_t *>(lds);
+        imgW1 = imgW0 + 3 * C::W0_PIECE;
+        imgWo = imgW1 + 3 * C::W1_PIECE;
+        const float *W0 = a.params + a.w0_col;
+        const float *W1 = a.params + a.rest_off;
+        const float *Wo = W1 + (NHL - 1) * 64 * 64;
+        stage_plain<64, KIN>(imgW0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
+        if constexpr (NHL == 2) stage_plain<64, 64>(imgW1, W1, 64, 0, 64 * NW);
+        stage_plain<16, 64>(imgWo, Wo, 64, 0, 64 * NW);
+        stage_neg_identity(reinterpret_cast<u32x4 *>(imgWo + 3 * C::WO_PIECE));
+        __syncthreads();
+    }
+    __device__ __forceinline__ void set_lane(int lane)
+    {
+        const int j = lane & 15, q = lane >> 4;
+        const int tq = j >> 2, tp = j & 3;               // transposed reads: this lane addresses row tq, chunk tp of its group's block
+        nI = NegI{reinterpret_cast<const u32x4 *>(imgWo + 3 * C::WO_PIECE) + lane};
+#pragma unroll
+        for (int seg = 0; seg < 4; ++seg) {
+            so_j[seg] = img_off<4>(j, seg, q);
+            so_t[seg] = img_off<4>(4 * q + tq, seg, tp);
+        }
+        sm_j = img_off<1>(j, 0, q);
+        sm_t = img_off<1>(4 * q + tq, 0, tp);
+        w0b_j = img_off<2>(j, q >> 1, 2 * (q & 1));
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) w0b_t[cb] = img_off<2>(4 * q + tq, cb, tp);
+    }
+
+    // chained-k row read of W1 (row 16rb + j): slots 0..3 = columns 32s + 4q .., slots 4..7 = columns 32s + 16 + 4q ..
+    __device__ __forceinline__ void row_chain_w1(int rb, int s, u32x4 (&o)[3]) const
+    {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const u32x2 lo = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s]));
+            const u32x2 hi = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s + 1]));
+            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
+        }
+    }
+    // chained-k TRANSPOSED reads (A = W^T): output rows = image columns 16cb + (lane & 15), slots = image rows 32s + ..
+    __device__ __forceinline__ void tr_chain_w1(int cb, int s, u32x4 (&o)[3]) const
+    {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const u32x2 lo = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + so_t[cb]));
+            const u32x2 hi = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + 2048 + so_t[cb]));
+            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
+        }
+    }
+    __device__ __forceinline__ void tr_chain_w0(int cb, int s, u32x4 (&o)[3]) const
+    {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const int base = (KIN == 16) ? sm_t : w0b_t[cb & 1];
+            const int row32 = 32 * (32 * C::S0);        // bytes of 32 image rows
+            const u32x2 lo = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + base));
+            const u32x2 hi = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + row32 / 2 + base));
+            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
+        }
+    }
+};
+
+// this tile's row-bias rows (32-bit offsets from the wave-uniform base that is returned) + the request of the next tile's
+template <bool BIAS, int CT>
+__device__ __forceinline__ const float *bias_rows_of_tile(const MlpArgs &a, int64_t n, int64_t tile, int64_t t_end, int j,
+                                                          const int (&sl)[CT], int (&brow_nx)[CT], int (&brow)[CT])
+{
+    if constexpr (BIAS) {
+        if (a.row_bias_idx) {       // this tile's rows were requested during the previous tile; request the next tile's now
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) brow[ct] = brow_nx[ct];
+            if (tile + 1 < t_end) request_bias_rows<CT>(a.row_bias_idx, n, tile * (16 * CT) + 16 * CT, j, brow_nx);
+        } else {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) brow[ct] = sl[ct];
+            return a.row_bias + tile * (16 * CT) * 64;
+        }
+    }
+    return a.row_bias;
+}
+
+// g = d(loss) / d(pre-activation output) of this lane's samples: d_out through the sigmoid (from `out`), plus the density head's
+// d_sigma on output 0 (selector, the +-15 clamp of trunc_exp); zero for the lanes past the end.  Every load of the tile is issued
+// before the first use (no load behind a branch on another load's value).
+template <int CT>
+__device__ __forceinline__ void out_grad_tile(const MlpArgs &a, int64_t tile_base, int oc, bool need_out, int q, const int (&sl)[CT],
+                                              const bool (&valid)[CT], f32x4 (&g)[CT])
+{
+    const float *dout_t = a.d_out + tile_base * oc;
+    const float *out_t = a.out ? a.out + tile_base * oc : nullptr;
+    f32x4 ovv[CT];
+    float dsgv[CT], o0v[CT];
+    uint32_t selv[CT];
+    const bool lane_sig = a.d_sigma != nullptr && q == 0;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int slc = sl[ct];
+        ovv[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (oc == 16) g[ct] = *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 16 + 4 * q));
+        else g[ct] = (q == 0) ? *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (need_out) {
+            if (oc == 16) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 16 + 4 * q));
+            else if (q == 0) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 4));
+        }
+        dsgv[ct] = lane_sig ? a.d_sigma[tile_base + slc] : 0.f;
+        o0v[ct] = (lane_sig && !need_out) ? out_t[(unsigned)(slc * oc)] : 0.f;
+        selv[ct] = (lane_sig && a.selector) ? (uint32_t)a.selector[tile_base + slc] : 1u;
+    }
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        f32x4 ov = ovv[ct];
+        if (lane_sig && !need_out) ov[0] = o0v[ct];
+        const float dsg = selv[ct] != 0u ? dsgv[ct] : 0.f;
+        const float x0 = fminf(fmaxf(ov[0], -15.f), 15.f);
+        if (need_out) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) g[ct][r] = g[ct][r] * ov[r] * (1.f - ov[r]);
+        }
+        if (lane_sig) g[ct][0] += dsg * a.density_scale * expf(x0);
+        if (!valid[ct]) g[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+template <int KIN, int NHL, int CT, int NW>
+struct X6Bwd : X6BwdImg<KIN, NHL> {
+    using I = X6BwdImg<KIN, NHL>;
     static constexpr int BUF_PIECE = 16 * CT * 128, SM_PIECE = 16 * CT * 32;
     static constexpr int WAVE_BYTES = 3 * (BUF_PIECE + SM_PIECE);
-    static constexpr int NI_BYTES = 2 * 1024;                 // the two "minus identity" A operands, one 16-byte entry per lane
-    static constexpr int lds_bytes = W_BYTES + NI_BYTES + NW * WAVE_BYTES;
+    static constexpr int lds_bytes = I::W_BYTES + I::NI_BYTES + NW * WAVE_BYTES;
 };
 
 // CT = column tiles (16 samples) per wave tile, NW = waves per workgroup (one workgroup per CU).  CT = 2 / NW = 8: the weight
@@ -769,56 +955,21 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 #else
 #define LSE_PHASE(name) do {} while (0)
 #endif
-    constexpr int TS = 16 * CT, HB = 4, WIDTH = 64, S0 = C::S0, KB0 = KIN / 16;
+    constexpr int TS = 16 * CT, HB = 4, WIDTH = 64, KB0 = KIN / 16;
     constexpr bool MS = (KIN == 32);      // remainder MFMAs on pairs of row blocks (base) / on single blocks (head: fewer live registers)
     static_assert((KIN == 16 && NHL == 2 && INL == LSE_IN_ROWMAJOR) || (KIN == 32 && NHL == 1), "head or base shape");
     extern __shared__ float lds[];
-    uint8_t *imgW0 = reinterpret_cast<uint8_t *>(lds);
-    uint8_t *imgW1 = imgW0 + 3 * C::W0_PIECE;
-    uint8_t *imgWo = imgW1 + 3 * C::W1_PIECE;
-
-    const float *W0 = a.params + a.w0_col;
-    const float *W1 = a.params + a.rest_off;
-    const float *Wo = W1 + (NHL - 1) * WIDTH * WIDTH;
-    stage_plain<64, KIN>(imgW0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
-    if constexpr (NHL == 2) stage_plain<64, 64>(imgW1, W1, WIDTH, 0, 64 * NW);
-    stage_plain<16, 64>(imgWo, Wo, WIDTH, 0, 64 * NW);
-    if (threadIdx.x < 64) {
-        u32x4 t[2];
-        neg_identity(threadIdx.x, t);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(imgWo + 3 * C::WO_PIECE);
-        dst[threadIdx.x] = t[0];
-        dst[64 + threadIdx.x] = t[1];
-    }
-    __syncthreads();
+    X6BwdW<KIN, NHL> w;
+    w.template stage<NW>(lds, a);
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
-    const int tq = j >> 2, tp = j & 3;               // transposed reads: this lane addresses row tq, chunk tp of its group's block
-    // "minus identity" operands live in LDS (registers are the scarce resource of this kernel): read where a split needs them
-    const u32x4 *nI_lds = reinterpret_cast<const u32x4 *>(imgWo + 3 * C::WO_PIECE) + lane;
-    struct NegI {
-        const u32x4 *p;
-        __device__ __forceinline__ u32x4 operator[](int b) const { return p[64 * b]; }
-    };
-    const NegI nI{nI_lds};
+    w.set_lane(lane);
+    const NegI &nI = w.nI;
+    uint8_t *const imgW0 = w.imgW0, *const imgWo = w.imgWo;
+    const int (&so_j)[4] = w.so_j, (&so_t)[4] = w.so_t, sm_j = w.sm_j, sm_t = w.sm_t;
     uint8_t *buf = imgWo + 3 * C::WO_PIECE + C::NI_BYTES + wave * C::WAVE_BYTES;      // [piece][32 samples][64 neurons]
     uint8_t *sm = buf + 3 * C::BUF_PIECE;                               // [piece][32 samples][16 columns]
-    // Per-lane byte offsets, computed once: every LDS address below is one of these + a compile-time constant (the DS
-    // instructions' immediate offset), so the address arithmetic costs no registers inside the tile loop.
-    //   "row" accesses   : image row 16X + j, 8-byte chunk q of segment seg          (128-byte rows: so_j[seg] + 2048 X)
-    //   "transposed" ones: image row 8X + 4q + tq, 8-byte chunk tp of segment seg    (128-byte rows: so_t[seg] + 1024 X)
-    int so_j[4], so_t[4];
-#pragma unroll
-    for (int seg = 0; seg < 4; ++seg) {
-        so_j[seg] = img_off<4>(j, seg, q);
-        so_t[seg] = img_off<4>(4 * q + tq, seg, tp);
-    }
-    const int sm_j = img_off<1>(j, 0, q), sm_t = img_off<1>(4 * q + tq, 0, tp);   // 32-byte rows (small tile, 16-column W0)
-    const int w0b_j = img_off<2>(j, q >> 1, 2 * (q & 1));                        // 64-byte rows (32-column W0): 16-byte row read
-    int w0b_t[2];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) w0b_t[cb] = img_off<2>(4 * q + tq, cb, tp);
 
     f32x4 accO[1][HB], acc1[(NHL == 2) ? HB : 1][(NHL == 2) ? HB : 1], acc0[HB][KB0];
 #pragma unroll
@@ -834,6 +985,8 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 
     a.n = lse::clamp_count(a.n, a.n_dev);
     const int64_t n = a.n, ns = a.n_stride;
+    // (wave_tile_range and, below, the first request_bias_rows and tile_lanes are written out in this kernel: called as functions
+    // they reorder the head instantiations and cost the head launch 1 %, DESIGN_HISTORY.md)
     const int64_t n_tiles = (n + TS - 1) / TS;
     const int64_t total_waves = (int64_t)gridDim.x * NW;
     const int64_t per = (n_tiles + total_waves - 1) / total_waves;
@@ -922,59 +1075,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 #pragma unroll
         for (int p = 0; p < 3; ++p) lds_write8(sm + (p * C::SM_PIECE + 512 * ct + sm_j), h.p[p][0], h.p[p][1]);
     };
-    // chained-k row read of W1 (row 16rb + j): slots 0..3 = columns 32s + 4q .., slots 4..7 = columns 32s + 16 + 4q ..
-    auto row_chain_w1 = [&](int rb, int s, u32x4 (&o)[3]) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const u32x2 lo = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s]));
-            const u32x2 hi = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s + 1]));
-            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-        }
-    };
-    // chained-k TRANSPOSED reads (A = W^T): output rows = image columns 16cb + (lane & 15), slots = image rows 32s + ..
-    auto tr_chain_w1 = [&](int cb, int s, u32x4 (&o)[3]) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const u32x2 lo = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + so_t[cb]));
-            const u32x2 hi = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + 2048 + so_t[cb]));
-            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-        }
-    };
-    auto tr_chain_w0 = [&](int cb, int s, u32x4 (&o)[3]) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const int base = (KIN == 16) ? sm_t : w0b_t[cb & 1];
-            const int row32 = 32 * (32 * S0);        // bytes of 32 image rows
-            const u32x2 lo = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + base));
-            const u32x2 hi = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + row32 / 2 + base));
-            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-        }
-    };
-
-    // pieces of two accumulator row blocks 2s2, 2s2+1 (= one k slab of the next product), both column tiles
-    auto split_blocks = [&](int s2, const f32x4 (&c0)[CT], const f32x4 (&c1)[CT], PiecesB<HB> (&x)[CT]) {
-        if constexpr (MS) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) split_pair(c0[ct], c1[ct], nI, x[ct].p[s2]);
-        }
-    };
-    // head shape (registers are scarce): one block at a time, as soon as it is complete -- the same two remainder MFMAs per
-    // block as the paired form (the unused half of the B operand is zero)
-    auto split_block_single = [&](int s2, int b, const f32x4 (&c)[CT], PiecesB<HB> (&x)[CT]) {
-        if constexpr (!MS) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                uint32_t hi[2], mid[2], lo[2];
-                split_half(c[ct], nI, hi, mid, lo);
-#pragma unroll
-                for (int w2 = 0; w2 < 2; ++w2) {
-                    x[ct].p[s2][0][2 * b + w2] = hi[w2];
-                    x[ct].p[s2][1][2 * b + w2] = mid[w2];
-                    x[ct].p[s2][2][2 * b + w2] = lo[w2];
-                }
-            }
-        }
-    };
     auto write_buf_rb = [&](int rb, const PiecesB<HB> (&x)[CT]) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
@@ -1017,75 +1117,17 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
         f32x4 raw[CT][KIN / 16];
         load_in_x6<KIN, INL, CT>(a, tile, j, q, raw);
         // per-row bias: row of this lane's sample per column tile (accumulator layout), as a 32-bit offset from a wave-uniform base
-        const float *rbase = a.row_bias;
         int brow[CT] = {};
-        if constexpr (BIAS) {
-            if (a.row_bias_idx) {       // this tile's rows were requested during the previous tile; request the next tile's now
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) brow[ct] = brow_nx[ct];
-                if (tile + 1 < t_end) {
-                    const int64_t nb_ = tile_base + TS;
-                    const int nr = (int)min((int64_t)TS, n - nb_);
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) brow_nx[ct] = a.row_bias_idx[nb_ + min(ct * 16 + j, nr - 1)];
-                }
-            } else {
-                rbase = a.row_bias + tile_base * WIDTH;
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) brow[ct] = sl[ct];
-            }
-        }
+        const float *rbase = bias_rows_of_tile<BIAS, CT>(a, n, tile, t_end, j, sl, brow_nx, brow);
         f32x4 g[CT];
-        {
-            // every load of the tile is issued before the first use (no load behind a branch on another load's value)
-            const float *dout_t = a.d_out + tile_base * oc;
-            const float *out_t = a.out ? a.out + tile_base * oc : nullptr;
-            f32x4 ovv[CT];
-            float dsgv[CT], o0v[CT];
-            uint32_t selv[CT];
-            const bool lane_sig = a.d_sigma != nullptr && q == 0;
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                const int slc = sl[ct];
-                ovv[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (oc == 16) g[ct] = *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 16 + 4 * q));
-                else g[ct] = (q == 0) ? *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (need_out) {
-                    if (oc == 16) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 16 + 4 * q));
-                    else if (q == 0) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 4));
-                }
-                dsgv[ct] = lane_sig ? a.d_sigma[tile_base + slc] : 0.f;
-                o0v[ct] = (lane_sig && !need_out) ? out_t[(unsigned)(slc * oc)] : 0.f;
-                selv[ct] = (lane_sig && a.selector) ? (uint32_t)a.selector[tile_base + slc] : 1u;
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                f32x4 ov = ovv[ct];
-                if (lane_sig && !need_out) ov[0] = o0v[ct];
-                const float dsg = selv[ct] != 0u ? dsgv[ct] : 0.f;
-                const float x0 = fminf(fmaxf(ov[0], -15.f), 15.f);
-                if (need_out) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) g[ct][r] = g[ct][r] * ov[r] * (1.f - ov[r]);
-                }
-                if (lane_sig) g[ct][0] += dsg * a.density_scale * expf(x0);
-                if (!valid[ct]) g[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-        }
+        out_grad_tile<CT>(a, tile_base, oc, need_out, q, sl, valid, g);
         // ---- first hidden layer again, one row block at a time: relu(W0 in + bias) -> mask bits + pieces
         LSE_PHASE("h0");
         PiecesB<HB> x[CT];
         uint32_t m0[CT] = {}, m1[CT] = {};      // ReLU masks, bit 4rb + r
         {
-            PiecesB16 xin16[CT];
-            u32x4 xin[CT][3];
-            if constexpr (KIN == 16) {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) split_in16(raw[ct][0], nI, xin16[ct]);
-            } else {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) split_pair(raw[ct][0], raw[ct][1], nI, xin[ct]);
-            }
+            InPieces<CT> xin;
+            split_input<KIN, CT>(raw, nI, xin);
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 f32x4 h[2][CT];
@@ -1101,18 +1143,18 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
                         u32x4 wc[3];
                         combos16_lds([&](int p) { return lds_read8(imgW0 + (p * C::W0_PIECE + 512 * rb + sm_j)); }, wc);
 #pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = LSE_MFMA_BF(wc[2], xin16[ct].c[2], h[b][ct]);
+                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = LSE_MFMA_BF(wc[2], xin.x16[ct].c[2], h[b][ct]);
 #pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = LSE_MFMA_BF(wc[1], xin16[ct].c[1], h[b][ct]);
+                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = LSE_MFMA_BF(wc[1], xin.x16[ct].c[1], h[b][ct]);
 #pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = LSE_MFMA_BF(wc[0], xin16[ct].c[0], h[b][ct]);
+                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = LSE_MFMA_BF(wc[0], xin.x16[ct].c[0], h[b][ct]);
                     } else {
                         u32x4 wa[3];
 #pragma unroll
                         for (int p = 0; p < 3; ++p)      // slots = columns 8q .. 8q+7: 16 contiguous bytes inside one segment
-                            wa[p] = *reinterpret_cast<const u32x4 *>(imgW0 + (p * C::W0_PIECE + 1024 * rb + w0b_j));
+                            wa[p] = *reinterpret_cast<const u32x4 *>(imgW0 + (p * C::W0_PIECE + 1024 * rb + w.w0b_j));
 #pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = mfma6(wa, xin[ct], h[b][ct]);
+                        for (int ct = 0; ct < CT; ++ct) h[b][ct] = mfma6(wa, xin.x[ct], h[b][ct]);
                     }
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct)
@@ -1121,10 +1163,10 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
                             h[b][ct][r] = relu_bits(h[b][ct][r]);
                             m0[ct] |= (h[b][ct][r] > 0.f ? 1u : 0u) << (4 * rb + r);
                         }
-                    split_block_single(s2, b, h[b], x);
+                    split_block_single<MS>(nI, s2, b, h[b], x);
                     if constexpr (!MS) LSE_X6_SB();
                 }
-                split_blocks(s2, h[0], h[1], x);
+                split_blocks<MS>(nI, s2, h[0], h[1], x);
                 LSE_X6_SB();
             }
         }
@@ -1143,7 +1185,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
                         u32x4 wa[3];
-                        row_chain_w1(rb, s, wa);
+                        w.row_chain_w1(rb, s, wa);
 #pragma unroll
                         for (int ct = 0; ct < CT; ++ct) h[b][ct] = mfma6(wa, x[ct].p[s], h[b][ct]);
                     }
@@ -1154,13 +1196,13 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
                             h[b][ct][r] = relu_bits(h[b][ct][r]);
                             m1[ct] |= (h[b][ct][r] > 0.f ? 1u : 0u) << (4 * rb + r);
                         }
-                    split_block_single(s2, b, h[b], x1);
+                    split_block_single<MS>(nI, s2, b, h[b], x1);
                     if constexpr (!MS) {
                         write_buf_rb(rb, x1);
                         LSE_X6_SB();
                     }
                 }
-                split_blocks(s2, h[0], h[1], x1);
+                split_blocks<MS>(nI, s2, h[0], h[1], x1);
                 if constexpr (MS) {
                     write_buf_rb(2 * s2, x1);
                     write_buf_rb(2 * s2 + 1, x1);
@@ -1233,13 +1275,13 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dh[b][ct][r] = relu_gate(dh[b][ct][r], m, 4 * rb + r);
                 }
-                split_block_single(s2, b, dh[b], x);
+                split_block_single<MS>(nI, s2, b, dh[b], x);
                 if constexpr (!MS) {
                     write_buf_rb(rb, x);
                     LSE_X6_SB();
                 }
             }
-            split_blocks(s2, dh[0], dh[1], x);
+            split_blocks<MS>(nI, s2, dh[0], dh[1], x);
             if constexpr (MS) {
                 write_buf_rb(2 * s2, x);
                 write_buf_rb(2 * s2 + 1, x);
@@ -1321,7 +1363,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
                         u32x4 wa[3];
-                        tr_chain_w1(cb, s, wa);
+                        w.tr_chain_w1(cb, s, wa);
 #pragma unroll
                         for (int ct = 0; ct < CT; ++ct) d0[b][ct] = mfma6(wa, x[ct].p[s], d0[b][ct]);
                     }
@@ -1331,14 +1373,14 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
                         for (int r = 0; r < 4; ++r) d0[b][ct][r] = relu_gate(d0[b][ct][r], m0[ct], 4 * cb + r);
                     if constexpr (!MS) {
                         PiecesB<HB> y1[CT];
-                        split_block_single(s2, b, d0[b], y1);
+                        split_block_single<MS>(nI, s2, b, d0[b], y1);
                         write_buf_rb(cb, y1);
                         LSE_X6_SB();
                     }
                 }
                 if constexpr (MS) {
                     PiecesB<HB> y[CT];
-                    split_blocks(s2, d0[0], d0[1], y);
+                    split_blocks<MS>(nI, s2, d0[0], d0[1], y);
                     write_buf_rb(2 * s2, y);
                     write_buf_rb(2 * s2 + 1, y);
                 }
@@ -1449,7 +1491,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     u32x4 wa[3];
-                    tr_chain_w0(cb, s, wa);
+                    w.tr_chain_w0(cb, s, wa);
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct) di[ct] = mfma6(wa, x[ct].p[s], di[ct]);
                 }
@@ -1518,13 +1560,15 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 }
 
 // ------------------------------------------------------------------------------------------------------
-// backward for FROZEN parameters: d(input) and d(row_bias) alone (lse_mlp_bwd_input).  The tile walk, the loads, the output
-// gradient preamble, the recomputed hidden layers and the three transposed-weight products are those of mlp_bwd3_kernel, product
-// by product in the same order, so d_in carries the same bits.  Nothing of the weight-gradient side is left: no dWo / dW1 / dW0
-// products, no second evaluation of H0^T, no per-wave LDS tile (the pieces of one product's accumulator are the B operand of the
-// next and stay in registers, as in the forward kernels), no accumulators that live across tiles except the 16 floats of the
-// running row-bias sum, no reduction tree and no parameter-sized output.  LDS = the plain weight piece images + the two
-// "minus identity" operands.
+// backward for FROZEN parameters: d(input) and d(row_bias) alone (lse_mlp_bwd_input).  The tile walk, the row-bias look-ahead,
+// the output-gradient preamble, the weight staging, the input split, the LDS readers and the splits are the definitions
+// mlp_bwd3_kernel calls, and the products come in its order, so d_in carries the same bits.  Two row blocks are still written
+// out in both kernels and have to be kept in step by hand: the recomputed first layer's and dH_last's (as shared functions they
+// moved the head's mlp_bwd3_kernel by 2 %; DESIGN_HISTORY.md).  mlp_bwd3_kernel also keeps its own text of the tile walk
+// and of the row-bias request in front of the loop.
+// Nothing of the weight-gradient side is here: no per-wave LDS tile (the pieces of one product's accumulator are the B operand
+// of the next and stay in registers), no accumulators that live across tiles except the 16 floats of the running row-bias sum,
+// no reduction tree, no parameter-sized output.
 //
 // d_row_bias[row] += sum over the row's samples of dH0 (what mlp_bwd3_kernel reads from a free column of its dW0 product): every
 // lane keeps the running sum of its own samples over the column tiles that belong wholly to the current row; when the row
@@ -1535,12 +1579,9 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void mlp_bwd3_kernel(MlpArgs
 constexpr int kBwdInNW = 4, kBwdInWavesPerSimd = 3;
 
 template <int KIN, int NHL>
-struct X6BwdIn {
-    static constexpr int S0 = KIN / 16;
-    static constexpr int W0_PIECE = 64 * 32 * S0, W1_PIECE = (NHL == 2) ? 64 * 128 : 0, WO_PIECE = 16 * 128;
-    static constexpr int W_BYTES = 3 * (W0_PIECE + W1_PIECE + WO_PIECE);
-    static constexpr int NI_BYTES = 2 * 1024;                 // the two "minus identity" A operands, one 16-byte entry per lane
-    static constexpr int lds_bytes = W_BYTES + NI_BYTES;      // head 38 912 B, base 20 480 B
+struct X6BwdIn : X6BwdImg<KIN, NHL> {
+    using I = X6BwdImg<KIN, NHL>;
+    static constexpr int lds_bytes = I::W_BYTES + I::NI_BYTES;      // head 38 912 B, base 20 480 B
     static constexpr int NW = kBwdInNW, CT = 2, WAVES_PER_SIMD = kBwdInWavesPerSimd;
 };
 
@@ -1549,58 +1590,22 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
 {
     using C = X6BwdIn<KIN, NHL>;
     constexpr int CT = C::CT, NW = C::NW;
-    constexpr int TS = 16 * CT, HB = 4, WIDTH = 64, S0 = C::S0, KB0 = KIN / 16;
+    constexpr int TS = 16 * CT, HB = 4, WIDTH = 64, KB0 = KIN / 16;
     constexpr bool MS = (KIN == 32);      // remainder MFMAs on pairs of row blocks (base) / on single blocks (head), as in mlp_bwd3_kernel
-    static_assert((KIN == 16 && NHL == 2 && INL == LSE_IN_ROWMAJOR) || (KIN == 32 && NHL == 1), "head or base shape");
+    static_assert(x6_recompute_shape(KIN, WIDTH, NHL, INL), "head or base shape");
     extern __shared__ float lds[];
-    uint8_t *imgW0 = reinterpret_cast<uint8_t *>(lds);
-    uint8_t *imgW1 = imgW0 + 3 * C::W0_PIECE;
-    uint8_t *imgWo = imgW1 + 3 * C::W1_PIECE;
-
-    const float *W0 = a.params + a.w0_col;
-    const float *W1 = a.params + a.rest_off;
-    const float *Wo = W1 + (NHL - 1) * WIDTH * WIDTH;
-    stage_plain<64, KIN>(imgW0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
-    if constexpr (NHL == 2) stage_plain<64, 64>(imgW1, W1, WIDTH, 0, 64 * NW);
-    stage_plain<16, 64>(imgWo, Wo, WIDTH, 0, 64 * NW);
-    if (threadIdx.x < 64) {
-        u32x4 t[2];
-        neg_identity(threadIdx.x, t);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(imgWo + 3 * C::WO_PIECE);
-        dst[threadIdx.x] = t[0];
-        dst[64 + threadIdx.x] = t[1];
-    }
-    __syncthreads();       // the only barrier: the images are read-only from here on
+    X6BwdW<KIN, NHL> w;
+    w.template stage<NW>(lds, a);       // the only barrier: the images are read-only from here on
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
-    const int tq = j >> 2, tp = j & 3;               // transposed reads: this lane addresses row tq, chunk tp of its group's block
-    const u32x4 *nI_lds = reinterpret_cast<const u32x4 *>(imgWo + 3 * C::WO_PIECE) + lane;
-    struct NegI {
-        const u32x4 *p;
-        __device__ __forceinline__ u32x4 operator[](int b) const { return p[64 * b]; }
-    };
-    const NegI nI{nI_lds};
-    // per-lane byte offsets into the images (see mlp_bwd3_kernel)
-    int so_j[4], so_t[4];
-#pragma unroll
-    for (int seg = 0; seg < 4; ++seg) {
-        so_j[seg] = img_off<4>(j, seg, q);
-        so_t[seg] = img_off<4>(4 * q + tq, seg, tp);
-    }
-    const int sm_j = img_off<1>(j, 0, q), sm_t = img_off<1>(4 * q + tq, 0, tp);
-    const int w0b_j = img_off<2>(j, q >> 1, 2 * (q & 1));
-    int w0b_t[2];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) w0b_t[cb] = img_off<2>(4 * q + tq, cb, tp);
+    w.set_lane(lane);
+    const NegI &nI = w.nI;
 
     a.n = lse::clamp_count(a.n, a.n_dev);
     const int64_t n = a.n, ns = a.n_stride;
-    const int64_t n_tiles = (n + TS - 1) / TS;
-    const int64_t total_waves = (int64_t)gridDim.x * NW;
-    const int64_t per = (n_tiles + total_waves - 1) / total_waves;
-    const int64_t w_id = (int64_t)blockIdx.x * NW + wave;
-    const int64_t t_begin = min(n_tiles, w_id * per), t_end = min(n_tiles, t_begin + per);
+    int64_t t_begin, t_end;
+    wave_tile_range<CT, NW>(n, wave, t_begin, t_end);
     const bool need_out = a.out_activation == LSE_ACT_SIGMOID;
     const int oc = a.out_cols;
     const bool want_bias = BIAS && a.d_row_bias != nullptr;
@@ -1627,130 +1632,20 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
         for (int mb = 0; mb < HB; ++mb) bsum[mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
     };
 
-    auto row_chain_w1 = [&](int rb, int s, u32x4 (&o)[3]) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const u32x2 lo = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s]));
-            const u32x2 hi = lds_read8(imgW1 + (p * C::W1_PIECE + 2048 * rb + so_j[2 * s + 1]));
-            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-        }
-    };
-    auto tr_chain_w1 = [&](int cb, int s, u32x4 (&o)[3]) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const u32x2 lo = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + so_t[cb]));
-            const u32x2 hi = lds_tr_read(imgW1 + (p * C::W1_PIECE + 4096 * s + 2048 + so_t[cb]));
-            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-        }
-    };
-    auto tr_chain_w0 = [&](int cb, int s, u32x4 (&o)[3]) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const int base = (KIN == 16) ? sm_t : w0b_t[cb & 1];
-            const int row32 = 32 * (32 * S0);        // bytes of 32 image rows
-            const u32x2 lo = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + base));
-            const u32x2 hi = lds_tr_read(imgW0 + (p * C::W0_PIECE + row32 * s + row32 / 2 + base));
-            o[p] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-        }
-    };
-    // pieces of two accumulator row blocks 2s2, 2s2+1 (= one k slab of the next product), both column tiles
-    auto split_blocks = [&](int s2, const f32x4 (&c0)[CT], const f32x4 (&c1)[CT], PiecesB<HB> (&x)[CT]) {
-        if constexpr (MS) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) split_pair(c0[ct], c1[ct], nI, x[ct].p[s2]);
-        }
-    };
-    auto split_block_single = [&](int s2, int b, const f32x4 (&c)[CT], PiecesB<HB> (&x)[CT]) {
-        if constexpr (!MS) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                uint32_t hi[2], mid[2], lo[2];
-                split_half(c[ct], nI, hi, mid, lo);
-#pragma unroll
-                for (int w2 = 0; w2 < 2; ++w2) {
-                    x[ct].p[s2][0][2 * b + w2] = hi[w2];
-                    x[ct].p[s2][1][2 * b + w2] = mid[w2];
-                    x[ct].p[s2][2][2 * b + w2] = lo[w2];
-                }
-            }
-        }
-    };
-
     int brow_nx[CT] = {};
-    if (BIAS && a.row_bias_idx && t_begin < t_end) {
-        const int64_t b0 = t_begin * TS;
-        const int nr = (int)min((int64_t)TS, n - b0);
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) brow_nx[ct] = a.row_bias_idx[b0 + min(ct * 16 + j, nr - 1)];
-    }
+    if (BIAS && a.row_bias_idx && t_begin < t_end) request_bias_rows<CT>(a.row_bias_idx, n, t_begin * TS, j, brow_nx);
     for (int64_t tile = t_begin; tile < t_end; ++tile) {
         const int64_t tile_base = tile * TS;
-        const int n_rem = (int)min((int64_t)TS, n - tile_base);       // valid samples of this tile (wave-uniform, >= 1)
         int sl[CT];
         bool valid[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            valid[ct] = ct * 16 + j < n_rem;
-            sl[ct] = valid[ct] ? ct * 16 + j : n_rem - 1;
-        }
+        tile_lanes<CT>(n, tile_base, j, sl, valid);
         // ---- loads
         f32x4 raw[CT][KIN / 16];
         load_in_x6<KIN, INL, CT>(a, tile, j, q, raw);
-        const float *rbase = a.row_bias;
         int brow[CT] = {};
-        if constexpr (BIAS) {
-            if (a.row_bias_idx) {       // this tile's rows were requested during the previous tile; request the next tile's now
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) brow[ct] = brow_nx[ct];
-                if (tile + 1 < t_end) {
-                    const int64_t nb_ = tile_base + TS;
-                    const int nr = (int)min((int64_t)TS, n - nb_);
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) brow_nx[ct] = a.row_bias_idx[nb_ + min(ct * 16 + j, nr - 1)];
-                }
-            } else {
-                rbase = a.row_bias + tile_base * WIDTH;
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) brow[ct] = sl[ct];
-            }
-        }
-        // ---- output gradient (the preamble of mlp_bwd3_kernel, expression by expression)
+        const float *rbase = bias_rows_of_tile<BIAS, CT>(a, n, tile, t_end, j, sl, brow_nx, brow);
         f32x4 g[CT];
-        {
-            const float *dout_t = a.d_out + tile_base * oc;
-            const float *out_t = a.out ? a.out + tile_base * oc : nullptr;
-            f32x4 ovv[CT];
-            float dsgv[CT], o0v[CT];
-            uint32_t selv[CT];
-            const bool lane_sig = a.d_sigma != nullptr && q == 0;
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                const int slc = sl[ct];
-                ovv[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (oc == 16) g[ct] = *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 16 + 4 * q));
-                else g[ct] = (q == 0) ? *reinterpret_cast<const f32x4 *>(dout_t + (unsigned)(slc * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (need_out) {
-                    if (oc == 16) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 16 + 4 * q));
-                    else if (q == 0) ovv[ct] = *reinterpret_cast<const f32x4 *>(out_t + (unsigned)(slc * 4));
-                }
-                dsgv[ct] = lane_sig ? a.d_sigma[tile_base + slc] : 0.f;
-                o0v[ct] = (lane_sig && !need_out) ? out_t[(unsigned)(slc * oc)] : 0.f;
-                selv[ct] = (lane_sig && a.selector) ? (uint32_t)a.selector[tile_base + slc] : 1u;
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                f32x4 ov = ovv[ct];
-                if (lane_sig && !need_out) ov[0] = o0v[ct];
-                const float dsg = selv[ct] != 0u ? dsgv[ct] : 0.f;
-                const float x0 = fminf(fmaxf(ov[0], -15.f), 15.f);
-                if (need_out) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) g[ct][r] = g[ct][r] * ov[r] * (1.f - ov[r]);
-                }
-                if (lane_sig) g[ct][0] += dsg * a.density_scale * expf(x0);
-                if (!valid[ct]) g[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-        }
+        out_grad_tile<CT>(a, tile_base, oc, need_out, q, sl, valid, g);
         // ---- which column tiles feed the running row sum (wave-uniform): one row per tile, as in mlp_bwd3_kernel
         bool whole[CT] = {};
         if (want_bias) {
@@ -1789,15 +1684,8 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
         PiecesB<HB> x[CT];
         uint32_t m0[CT] = {}, m1[CT] = {};      // ReLU masks, bit 4rb + r
         {
-            PiecesB16 xin16[CT];
-            u32x4 xin[CT][3];
-            if constexpr (KIN == 16) {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) split_in16(raw[ct][0], nI, xin16[ct]);
-            } else {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) split_pair(raw[ct][0], raw[ct][1], nI, xin[ct]);
-            }
+            InPieces<CT> xin;
+            split_input<KIN, CT>(raw, nI, xin);
 #pragma unroll
             for (int rb = 0; rb < HB; ++rb) {
                 f32x4 h[CT];
@@ -1808,20 +1696,20 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
                 }
                 if constexpr (KIN == 16) {
                     u32x4 wc[3];
-                    combos16_lds([&](int p) { return lds_read8(imgW0 + (p * C::W0_PIECE + 512 * rb + sm_j)); }, wc);
+                    combos16_lds([&](int p) { return lds_read8(w.imgW0 + (p * C::W0_PIECE + 512 * rb + w.sm_j)); }, wc);
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[2], xin16[ct].c[2], h[ct]);
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[2], xin.x16[ct].c[2], h[ct]);
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[1], xin16[ct].c[1], h[ct]);
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[1], xin.x16[ct].c[1], h[ct]);
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[0], xin16[ct].c[0], h[ct]);
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = LSE_MFMA_BF(wc[0], xin.x16[ct].c[0], h[ct]);
                 } else {
                     u32x4 wa[3];
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
-                        wa[p] = *reinterpret_cast<const u32x4 *>(imgW0 + (p * C::W0_PIECE + 1024 * rb + w0b_j));
+                        wa[p] = *reinterpret_cast<const u32x4 *>(w.imgW0 + (p * C::W0_PIECE + 1024 * rb + w.w0b_j));
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) h[ct] = mfma6(wa, xin[ct], h[ct]);
+                    for (int ct = 0; ct < CT; ++ct) h[ct] = mfma6(wa, xin.x[ct], h[ct]);
                 }
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct)
@@ -1831,7 +1719,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
                         m0[ct] |= (h[ct][r] > 0.f ? 1u : 0u) << (4 * rb + r);
                     }
                 // (the base needs the mask alone: its hidden layer feeds no further product here)
-                if constexpr (NHL == 2) split_block_single(rb >> 1, rb & 1, h, x);
+                if constexpr (NHL == 2) split_block_single<MS>(nI, rb >> 1, rb & 1, h, x);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -1845,7 +1733,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     u32x4 wa[3];
-                    row_chain_w1(rb, s, wa);
+                    w.row_chain_w1(rb, s, wa);
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct) h[ct] = mfma6(wa, x[ct].p[s], h[ct]);
                 }
@@ -1868,7 +1756,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
                 for (int b = 0; b < 2; ++b) {
                     const int rb = 2 * s2 + b;
                     u32x4 wc[3];
-                    combos16_lds([&](int p) { return lds_tr_read(imgWo + (p * C::WO_PIECE + so_t[rb])); }, wc);
+                    combos16_lds([&](int p) { return lds_tr_read(w.imgWo + (p * C::WO_PIECE + w.so_t[rb])); }, wc);
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct) {
                         f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1880,10 +1768,10 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
                         for (int r = 0; r < 4; ++r) dh[b][ct][r] = relu_gate(dh[b][ct][r], m, 4 * rb + r);
                     }
                     if constexpr (NHL == 1) bias_block(rb, dh[b]);
-                    split_block_single(s2, b, dh[b], x);
+                    split_block_single<MS>(nI, s2, b, dh[b], x);
                     if constexpr (!MS) __builtin_amdgcn_sched_barrier(0);
                 }
-                split_blocks(s2, dh[0], dh[1], x);
+                split_blocks<MS>(nI, s2, dh[0], dh[1], x);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -1898,7 +1786,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
                         u32x4 wa[3];
-                        tr_chain_w0(cb, s, wa);
+                        w.tr_chain_w0(cb, s, wa);
 #pragma unroll
                         for (int ct = 0; ct < CT; ++ct) di[ct] = mfma6(wa, z[ct].p[s], di[ct]);
                     }
@@ -1931,7 +1819,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
 #pragma unroll
                 for (int cb = 0; cb < HB; ++cb) {
                     u32x4 wa[3];
-                    tr_chain_w1(cb, s, wa);
+                    w.tr_chain_w1(cb, s, wa);
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct) d0[cb][ct] = mfma6(wa, x[ct].p[s], d0[cb][ct]);
                     __builtin_amdgcn_sched_barrier(0);
@@ -1960,7 +1848,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
                 PiecesB<HB> y[CT];
 #pragma unroll
                 for (int cb = 0; cb < HB; ++cb) {
-                    split_block_single(cb >> 1, cb & 1, d0[cb], y);
+                    split_block_single<MS>(nI, cb >> 1, cb & 1, d0[cb], y);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 d_in_of(y);

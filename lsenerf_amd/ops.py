@@ -9,6 +9,7 @@ from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import ctypes
+import functools
 import time
 
 import torch
@@ -665,11 +666,39 @@ def frozen_wgrad_scratch(params: torch.Tensor) -> torch.Tensor:
     return s
 
 
+def _x6_shape(meta: MlpMeta) -> bool:      # what mlp_x6.h recomputes: head 16 -> 64 -> 64 -> 16 row-major, base 32 -> 64 -> 16
+    return meta.width == 64 and ((meta.n_in == 16 and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR)
+                                 or (meta.n_in == 32 and meta.n_hidden_layers == 1))
+
+
 def mlp_input_only_shape(meta: MlpMeta) -> bool:
-    """The calls ``lse_mlp_bwd_input`` serves: the two shapes of the recompute-all backward (act_tiled = 3) in bf16x6 arithmetic."""
-    return (meta.width == 64 and meta.arith == _lib.LSE_MLP_ARITH_AUTO
-            and ((meta.n_in == 16 and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR)
-                 or (meta.n_in == 32 and meta.n_hidden_layers == 1)))
+    """The calls ``lse_mlp_bwd_input`` and ``lse_mlp_fwd_pair`` serve: a recompute shape whose forward runs in bf16x6 arithmetic."""
+    return _x6_shape(meta) and meta.arith == _lib.LSE_MLP_ARITH_AUTO
+
+
+def _bias_grad_in_kernel(bias_grad: bool, bias_sorted: bool) -> bool:      # a needed row-bias gradient can be reduced in-kernel
+    return not bias_grad or bool(FUSED_BIAS_GRAD and bias_sorted)
+
+
+def mlp_bwd_route(meta: MlpMeta, *, params_grad: bool, need_grad: bool, bias_grad: bool, bias_sorted: bool, has_count: bool,
+                  input_only: bool):
+    """What ``fused_mlp`` saves and which backward runs, ``(act_tiled, input_only_kernel)``; touches no tensor.  0 / 1: row-major /
+    tile-major saved activations.  2: the head-like case (two hidden layers, row-major input, trainable parameters), first hidden layer
+    recomputed.  3: nothing saved, mlp_x6.h recomputes every hidden layer -- head / base shape with trainable parameters, or frozen
+    ones under a device-side count (``has_count``: the saved-activation kernels have none; weight-gradient products go to
+    ``frozen_wgrad_scratch``) or under the caller's ``input_only``, whose backward is ``lse_mlp_bwd_input``.  2 and 3 need the bias
+    gradient, if any, reduced in-kernel."""
+    if not (FUSED_WGRAD and ACT_TILED):
+        return 0, False
+    if not (need_grad and _bias_grad_in_kernel(bias_grad, bias_sorted)):
+        return 1, False
+    input_only = bool(input_only) and not params_grad and mlp_input_only_shape(meta)
+    if RECOMPUTE_ALL and _x6_shape(meta) and (params_grad or has_count or input_only):
+        return 3, input_only
+    if RECOMPUTE_FIRST_LAYER and params_grad and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR \
+            and meta.n_in % 16 == 0:
+        return 2, False
+    return 1, False
 
 
 @torch.no_grad()
@@ -686,6 +715,30 @@ def mlp_bwd_input(params, x, meta: MlpMeta, n: int, out, out_cols: int, d_out, d
             _chk(row_bias_idx, torch.int32, "row_bias_idx", True), _f32(d_row_bias, "d_row_bias", True), n, _stream())
 
 
+def _mlp_bwd_recompute(params, x, meta: MlpMeta, n: int, out, out_cols: int, d_out, d_sigma, selector, density_scale, row_bias,
+                       row_bias_idx, n_dev, *, input_only: bool, want_params: bool, want_in: bool, want_bias: bool, scratch=None):
+    """The backward of one network on the route that saved nothing (act_tiled = 3): ``lse_mlp_bwd_input`` for frozen parameters
+    under ``input_only`` -- no launch when neither gradient is wanted, no scratch -- else ``lse_mlp_bwd``, whose weight-gradient
+    products go to the leaf's preallocated ``.grad`` (``_direct_grad``), to a fresh zeroed tensor, or, unwanted, to
+    ``scratch`` (the forward's ``frozen_wgrad_scratch``).  Returns what autograd receives for ``(params, x, row_bias)``."""
+    d_in = torch.empty_like(x) if want_in else None
+    d_bias = torch.zeros_like(row_bias) if want_bias else None
+    if input_only:
+        if d_in is not None or d_bias is not None:
+            mlp_bwd_input(params, x, meta, n, out, out_cols, d_out, d_sigma, selector, density_scale, d_in, row_bias, row_bias_idx,
+                          d_bias, n_dev)
+        return None, d_in, d_bias
+    direct = _direct_grad(params) if want_params else None
+    d_params = direct if direct is not None else (torch.zeros_like(params) if want_params else scratch)
+    desc = meta.desc()
+    _call_n("lse_mlp_bwd", n_dev, ctypes.byref(desc), _f32(params, "params"), _f32(x, "mlp input"), None, 3, _f32(out, "out"),
+            out_cols, _f32(d_out, "d_out"), _f32(d_sigma, "d_sigma", True), _chk(selector, torch.uint8, "selector", True),
+            float(density_scale or 0.0), None, None, None, _f32(d_in, "d_in", True), _f32(d_params, "d_params"),
+            _f32(row_bias, "row_bias", True), _chk(row_bias_idx, torch.int32, "row_bias_idx", True), _f32(d_bias, "d_bias", True),
+            n, _stream())
+    return (d_params if (want_params and direct is None) else None), d_in, d_bias
+
+
 class _MlpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, params, x, row_bias, row_bias_idx, bias_packed_info, selector, meta: MlpMeta, n: int, out_cols: int,
@@ -694,29 +747,13 @@ class _MlpFn(torch.autograd.Function):
         out = torch.empty((n, out_cols), dtype=torch.float32, device=dev)
         sigma = torch.empty(n, dtype=torch.float32, device=dev) if density_scale is not None else None
         need_grad = any(t is not None and t.requires_grad for t in (params, x, row_bias))
-        tiled = 1 if (FUSED_WGRAD and ACT_TILED) else 0
-        # two hidden layers on a row-major input (the head): the first hidden layer is not saved, the backward recomputes it
-        if tiled and RECOMPUTE_FIRST_LAYER and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR \
-                and meta.n_in % 16 == 0 and need_grad and params.requires_grad \
-                and (row_bias is None or not row_bias.requires_grad
-                     or (FUSED_BIAS_GRAD and row_bias_idx is not None and bias_packed_info is not None)):
-            tiled = 2     # (only the second-generation backward recomputes: it needs the bias gradient reduced in-kernel)
-        # third generation (mlp_x6.h): nothing is saved, the backward recomputes every hidden layer on the bf16 matrix cores
-        # (frozen parameters under a device-side count take it too -- the saved-activation kernels have no count; their weight
-        # gradients go to frozen_wgrad_scratch)
-        # (input_only: the caller's frozen parameters take the recomputing route whatever the count, for lse_mlp_bwd_input)
-        input_only = bool(input_only) and not params.requires_grad and mlp_input_only_shape(meta)
-        if tiled and RECOMPUTE_ALL and meta.width == 64 and need_grad and (params.requires_grad or n_dev is not None or input_only) \
-                and ((meta.n_in == 16 and meta.n_hidden_layers == 2 and meta.in_layout == _lib.LSE_IN_ROWMAJOR)
-                     or (meta.n_in == 32 and meta.n_hidden_layers == 1)) \
-                and (row_bias is None or not row_bias.requires_grad
-                     or (FUSED_BIAS_GRAD and row_bias_idx is not None and bias_packed_info is not None)):
-            tiled = 3
+        tiled, ctx.input_only = mlp_bwd_route(
+            meta, params_grad=params.requires_grad, need_grad=need_grad, bias_grad=row_bias is not None and row_bias.requires_grad,
+            bias_sorted=row_bias_idx is not None and bias_packed_info is not None, has_count=n_dev is not None, input_only=input_only)
         n_act = (n + 15) // 16 * 16 if tiled else n
         n_saved = meta.n_hidden_layers - (1 if tiled == 2 else 0)
         act = torch.empty((n_saved, n_act, meta.width), dtype=torch.float32, device=dev) if (need_grad and tiled != 3) else None
         ctx.act_tiled = tiled
-        ctx.input_only = input_only and tiled == 3        # d(input) / d(row_bias) alone: no weight-gradient products, no scratch
         ctx.wscratch = frozen_wgrad_scratch(params) if (tiled == 3 and not params.requires_grad and not ctx.input_only) else None
         desc = meta.desc()
         if n_dev is not None and need_grad and tiled != 3:
@@ -738,28 +775,26 @@ class _MlpFn(torch.autograd.Function):
         d_out = _c(d_out) if d_out is not None else torch.zeros((n, out_cols), dtype=torch.float32, device=dev)
         d_sigma = _c(d_sigma) if d_sigma is not None else None
         need_bias = row_bias is not None and ctx.needs_input_grad[2]
+        if ctx.act_tiled == 3:
+            grads = _mlp_bwd_recompute(params, x, meta, n, out, out_cols, d_out, d_sigma, selector, ctx.density_scale, row_bias,
+                                       row_bias_idx, ctx.n_dev, input_only=ctx.input_only, want_params=ctx.needs_input_grad[0],
+                                       want_in=ctx.needs_input_grad[1], want_bias=need_bias, scratch=ctx.wscratch)
+            return grads + (None,) * 9
         # sorted row indices (packed samples): the kernel reduces the bias gradient per row itself
-        fused_bias = FUSED_BIAS_GRAD and need_bias and row_bias_idx is not None and bias_packed_info is not None
+        fused_bias = need_bias and _bias_grad_in_kernel(True, row_bias_idx is not None and bias_packed_info is not None)
         d_bias = torch.zeros_like(row_bias) if fused_bias else None
         d_act0 = torch.empty((n, meta.width), dtype=torch.float32, device=dev) if (need_bias and not fused_bias) else None
         d_in = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        if ctx.input_only:       # frozen parameters, head / base shape (a bias gradient here is always the fused one: forward)
-            if d_in is not None or d_bias is not None:
-                mlp_bwd_input(params, x, meta, n, out, out_cols, d_out, d_sigma, selector, ctx.density_scale, d_in, row_bias,
-                              row_bias_idx, d_bias, ctx.n_dev)
-            return None, d_in, d_bias, None, None, None, None, None, None, None, None, None
         direct = _direct_grad(params) if (ctx.needs_input_grad[0] and (ctx.act_tiled or FUSED_WGRAD)) else None
         d_params = direct if direct is not None else (torch.zeros_like(params) if ctx.needs_input_grad[0] else None)
-        wgrad_out = d_params if (d_params is not None or ctx.act_tiled != 3) else ctx.wscratch     # act_tiled = 3 always forms them
         desc = meta.desc()
         scale = float(ctx.density_scale or 0.0)
         sel = _chk(selector, torch.uint8, "selector", True)
         if ctx.act_tiled or FUSED_WGRAD or d_params is None:
-            _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(desc), _f32(params, "params"), _f32(x, "mlp input"),
-                      _f32(act, "act", ctx.act_tiled == 3),
+            _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(desc), _f32(params, "params"), _f32(x, "mlp input"), _f32(act, "act"),
                       ctx.act_tiled, _f32(out, "out"), out_cols, _f32(d_out, "d_out"), _f32(d_sigma, "d_sigma", True), sel, scale,
                       None, None, _f32(d_act0, "d_act0", True), _f32(d_in, "d_in", True),
-                      _f32(wgrad_out, "d_params", True), _f32(row_bias, "row_bias", True),
+                      _f32(d_params, "d_params", True), _f32(row_bias, "row_bias", True),
                       _chk(row_bias_idx, torch.int32, "row_bias_idx", True) if (fused_bias or ctx.act_tiled >= 2) else None,
                       _f32(d_bias if fused_bias else None, "d_bias", True), n, _stream())
         else:   # reference structure: materialise d_act, then one G^T A reduction per layer (padded outputs only)
@@ -790,11 +825,8 @@ class _MlpFn(torch.autograd.Function):
 
 def _mlp_pair_shapes(base_meta: MlpMeta, head_meta: MlpMeta) -> bool:
     """The shapes lse_mlp_fwd_pair is built for: the recompute-all production pair (base 32 -> 64 -> 16, head 16 -> 64 -> 64 -> 16)."""
-    return (base_meta.n_in == 32 and base_meta.width == 64 and base_meta.n_hidden_layers == 1
-            and base_meta.out_activation == _lib.LSE_ACT_NONE
-            and head_meta.n_in == 16 and head_meta.width == 64 and head_meta.n_hidden_layers == 2
-            and head_meta.in_layout == _lib.LSE_IN_ROWMAJOR
-            and base_meta.arith == _lib.LSE_MLP_ARITH_AUTO and head_meta.arith == _lib.LSE_MLP_ARITH_AUTO)
+    return (mlp_input_only_shape(base_meta) and base_meta.n_in == 32 and base_meta.out_activation == _lib.LSE_ACT_NONE
+            and mlp_input_only_shape(head_meta) and head_meta.n_in == 16)
 
 
 class _MlpPairFn(torch.autograd.Function):
@@ -819,8 +851,8 @@ class _MlpPairFn(torch.autograd.Function):
         ctx.base_meta, ctx.head_meta, ctx.n, ctx.out_cols, ctx.density_scale, ctx.n_dev = \
             base_meta, head_meta, n, out_cols, density_scale, n_dev
         # frozen parameters: the recomputing backward still forms the weight-gradient products; they go where nothing reads them
-        need_grad = any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
         # (input_only: a frozen network's backward is lse_mlp_bwd_input, which forms none -- no scratch is created or touched)
+        need_grad = any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
         ctx.head_input_only = bool(input_only) and not head_params.requires_grad and mlp_input_only_shape(head_meta)
         ctx.base_input_only = bool(input_only) and not base_params.requires_grad and mlp_input_only_shape(base_meta)
         ctx.head_scratch = frozen_wgrad_scratch(head_params) if (need_grad and not head_params.requires_grad
@@ -834,60 +866,25 @@ class _MlpPairFn(torch.autograd.Function):
     def backward(ctx, d_h, d_sigma, d_out):
         base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, h, out = ctx.saved_tensors
         n, out_cols, dev = ctx.n, ctx.out_cols, base_params.device
-        # ---- head (the call of _MlpFn.backward at act_tiled = 3)
-        d_in_head, d_bias, d_hp_ret = None, None, None
-        if d_out is not None and ctx.head_input_only:
-            # frozen head: its d_in is wanted only where the base launch below will run (not in the embedding-only phase)
-            d_out = _c(d_out)
-            need_bias = row_bias is not None and ctx.needs_input_grad[4]
-            d_bias = torch.zeros_like(row_bias) if need_bias else None
-            d_in_head = torch.empty_like(h) if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else None
-            if d_in_head is not None or d_bias is not None:
-                mlp_bwd_input(head_params, h, ctx.head_meta, n, out, out_cols, d_out, None, None, 0.0, d_in_head, row_bias,
-                              row_bias_idx, d_bias, ctx.n_dev)
-        elif d_out is not None:
-            d_out = _c(d_out)
-            need_bias = row_bias is not None and ctx.needs_input_grad[4]
-            d_bias = torch.zeros_like(row_bias) if need_bias else None
-            d_in_head = torch.empty_like(h)
-            if ctx.needs_input_grad[3]:
-                direct = _direct_grad(head_params)
-                d_hp = direct if direct is not None else torch.zeros_like(head_params)
-                d_hp_ret = None if direct is not None else d_hp
-            else:
-                d_hp = ctx.head_scratch
-            hdesc = ctx.head_meta.desc()
-            _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(hdesc), _f32(head_params, "params"), _f32(h, "mlp input"), None, 3,
-                    _f32(out, "out"), out_cols, _f32(d_out, "d_out"), None, None, 0.0, None, None, None,
-                    _f32(d_in_head, "d_in"), _f32(d_hp, "d_params"), _f32(row_bias, "row_bias", True),
-                    _chk(row_bias_idx, torch.int32, "row_bias_idx", True), _f32(d_bias, "d_bias", True), n, _stream())
+        wants_base = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        # ---- head (a frozen input-only head's d_in is wanted only where the base launch below will run)
+        d_hp = d_in_head = d_bias = None
+        if d_out is not None:
+            d_hp, d_in_head, d_bias = _mlp_bwd_recompute(
+                head_params, h, ctx.head_meta, n, out, out_cols, _c(d_out), None, None, 0.0, row_bias, row_bias_idx, ctx.n_dev,
+                input_only=ctx.head_input_only, want_params=ctx.needs_input_grad[3], want_in=not ctx.head_input_only or wants_base,
+                want_bias=row_bias is not None and ctx.needs_input_grad[4], scratch=ctx.head_scratch)
         # ---- base: d_out = the head's d_in + whatever else consumed h
-        if d_h is not None and d_in_head is not None:
-            d_base = d_in_head + d_h
-        else:
-            d_base = d_in_head if d_in_head is not None else d_h
-        d_y, d_bp_ret = None, None
-        # (neither y nor the base parameters need a gradient -- a frozen field refining its embedding: no base launch at all)
-        if (d_base is not None or d_sigma is not None) and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+        d_base = d_in_head + d_h if (d_h is not None and d_in_head is not None) else (d_in_head if d_in_head is not None else d_h)
+        d_bp = d_y = None
+        # (a frozen field refining its embedding needs neither d_y nor base gradients: no base launch at all)
+        if (d_base is not None or d_sigma is not None) and wants_base:
             d_base = _c(d_base) if d_base is not None else torch.zeros((n, 16), dtype=torch.float32, device=dev)
-            d_sigma = _c(d_sigma) if d_sigma is not None else None
-            d_y = torch.empty_like(y) if ctx.needs_input_grad[1] else None
-            if ctx.base_input_only:      # frozen base: this branch runs for d_y alone
-                mlp_bwd_input(base_params, y, ctx.base_meta, n, h, 16, d_base, d_sigma, selector, ctx.density_scale, d_y,
-                              n_dev=ctx.n_dev)
-                return None, d_y, None, d_hp_ret, d_bias, None, None, None, None, None, None, None, None, None
-            if ctx.needs_input_grad[0]:
-                direct = _direct_grad(base_params)
-                d_bp = direct if direct is not None else torch.zeros_like(base_params)
-                d_bp_ret = None if direct is not None else d_bp
-            else:
-                d_bp = ctx.base_scratch
-            bdesc = ctx.base_meta.desc()
-            _call_n("lse_mlp_bwd", ctx.n_dev, ctypes.byref(bdesc), _f32(base_params, "params"), _f32(y, "mlp input"), None, 3,
-                    _f32(h, "out"), 16, _f32(d_base, "d_out"), _f32(d_sigma, "d_sigma", True),
-                    _chk(selector, torch.uint8, "selector", True), float(ctx.density_scale), None, None, None,
-                    _f32(d_y, "d_in", True), _f32(d_bp, "d_params"), None, None, None, n, _stream())
-        return d_bp_ret, d_y, None, d_hp_ret, d_bias, None, None, None, None, None, None, None, None, None
+            d_bp, d_y, _ = _mlp_bwd_recompute(
+                base_params, y, ctx.base_meta, n, h, 16, d_base, _c(d_sigma) if d_sigma is not None else None, selector,
+                ctx.density_scale, None, None, ctx.n_dev, input_only=ctx.base_input_only, want_params=ctx.needs_input_grad[0],
+                want_in=ctx.needs_input_grad[1], want_bias=False, scratch=ctx.base_scratch)
+        return d_bp, d_y, None, d_hp, d_bias, None, None, None, None, None, None, None, None, None
 
 
 def mlp_pair_usable(base_params, y, base_meta: MlpMeta, head_params, head_meta: MlpMeta, row_bias, row_bias_idx,
@@ -901,10 +898,12 @@ def mlp_pair_usable(base_params, y, base_meta: MlpMeta, head_params, head_meta: 
     need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
     if not need_grad:
         return True
-    # (frozen parameters recompute as well: their weight-gradient products land in frozen_wgrad_scratch)
-    return bool(FUSED_WGRAD and ACT_TILED and RECOMPUTE_ALL
-                and (row_bias is None or not row_bias.requires_grad
-                     or (FUSED_BIAS_GRAD and row_bias_idx is not None and bias_packed_info is not None)))
+    # the pair saves nothing, so frozen parameters recompute too, as they do under a device-side count: has_count=True
+    route = functools.partial(mlp_bwd_route, need_grad=True, has_count=True, input_only=False)
+    base = route(base_meta, params_grad=base_params.requires_grad, bias_grad=False, bias_sorted=False)
+    head = route(head_meta, params_grad=head_params.requires_grad, bias_grad=row_bias is not None and row_bias.requires_grad,
+                 bias_sorted=row_bias_idx is not None and bias_packed_info is not None)
+    return base[0] == 3 and head[0] == 3
 
 
 def fused_mlp_pair(base_params, y, selector, density_scale, base_meta: MlpMeta, head_params, head_meta: MlpMeta, n: int,
