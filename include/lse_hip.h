@@ -476,6 +476,58 @@ int lse_log_scale_correct_workspace(int32_t H, int32_t W, int64_t *h_bytes);
 int lse_log_scale_correct(const float *gt_planes, const float *rgb, int32_t H, int32_t W, const void *stats, int64_t stats_bytes,
                           float *coef, float *corrected, float *gray, lse_stream_t stream);
 
+/* ---- eval panels (csrc/panels.hip; ABI 6, additive): the images the reference's evaluation writes, as uint8, on the device -----
+ * No host read-back, no host loop over device data, no cooperative launch or spin wait; every device loop is bounded by the image
+ * size.  H * W < 2^30.  u8(v) below is (uint8) trunc(min(max(v * 255.0f, 0), 255)) with a NaN giving 0 (numpy's and torch's cast
+ * of a NaN to uint8 is undefined; 0 is this library's choice).
+ *   lse_gray8_planes: planes_a, planes_b f32 [3, H, W] (the planes of lse_eval_image_prep; planes_b nullable: one image) ->
+ *      out uint8 [2, H, W] (or [1, H, W]) = u8((0.2989f r + 0.5870f g) + 0.1140f b), each operation rounded: the grey of
+ *      lse_eval_image_prep.  (R:lse_nerf/lsenerf.py:463-464 takes the grey by a matmul whose order on a GPU is not knowable.)
+ *   lse_canny_classify: gray uint8 [n_images, H, W] -> classes uint8 [n_images, H, W], 0 = none, 1 = weak, 2 = strong: OpenCV's
+ *      Canny(image, low, high, apertureSize = 3, L2gradient = false) up to the hysteresis, restated from the published algorithm
+ *      (parity unpinned).  3 x 3 Sobel dx, dy with a replicated border; mag = |dx| + |dy|, 0 outside the image; a pixel is a
+ *      candidate when mag > low and strong when also mag > high (low > high are swapped); it must pass the non-maximum
+ *      suppression: with x = |dx|, y = |dy| << 15, tg22x = x * 13573: y < tg22x: mag > mag[left] and mag >= mag[right]; else
+ *      y > tg22x + (x << 16): mag > mag[up] and mag >= mag[down]; else s = ((dx ^ dy) < 0) ? -1 : 1 and mag > mag[up, j - s] and
+ *      mag > mag[down, j + s].  The strict / non-strict asymmetry is part of the contract.  All arithmetic is integer.
+ *   lse_canny_hysteresis: classes -> edges uint8 [n_images, H, W], 255 where the pixel is strong, or weak and 8-connected to a
+ *      strong one through weak and strong pixels, else 0.  A set, so independent of any order: two calls are bit-identical.
+ *      Union-find in three launches (merge inside a tile in LDS; merge across tile borders with 32-bit atomicMin on the labels;
+ *      flatten).  workspace: n_images * lse_canny_workspace bytes, 8-byte aligned, written before it is read (never assumed zero).
+ *      edges may alias classes.
+ *   lse_canny_u8: lse_canny_classify then lse_canny_hysteresis on one stream; the class map passes through `edges`.
+ *   lse_eval_panels: the writer's combined image (R:lse_nerf/lse_writer.py:32-64) of one eval image, grid uint8 [H, n_cols * W, 3].
+ *      `flags` selects the panels, laid out left to right in this order:
+ *        LSE_PANEL_IMG      2 W wide: gt_planes [3, H, W] (masked) beside rgb [H * W, 3] (unmasked); or, when pair_gt / pair_pred
+ *                           [H * W] are given, that grey pair of the event-only metric, each tiled to three channels
+ *        LSE_PANEL_DEPTH    ((1 - clip((depth - near) / ((far - near) + 1e-10f), 0, 1)) * acc) + (1 - acc), depth and accumulation
+ *                           [H * W]; near / far = min / max of depth (a NaN is handed on), by a fixed-order two-stage reduction
+ *                           without atomics that leaves them in workspace[0], workspace[1] (f32)
+ *        LSE_PANEL_ERR_MAP  make_error_map of gt_planes and pred_planes, norm_cnst 6, the grey as in lse_gray8_planes
+ *        LSE_PANEL_OVERLAY  edges uint8 [2, H, W] (ground truth, prediction): white; black where either is set; then channel 0 =
+ *                           255 on the ground truth's edges and channel 2 = 255 on the prediction's (both: magenta)
+ *        LSE_PANEL_EV_OUT   ev_out [H * W, ev_channels], ev_channels 1 (tiled to three) or 3
+ *      Every value is the float expression of lsenerf_amd/evaluation.py with each operation rounded once in f32, then u8().
+ *      Inputs of unselected panels may be NULL.  workspace: lse_eval_panels_workspace bytes, 8-byte aligned, written. */
+#define LSE_PANEL_IMG 1
+#define LSE_PANEL_DEPTH 2
+#define LSE_PANEL_ERR_MAP 4
+#define LSE_PANEL_OVERLAY 8
+#define LSE_PANEL_EV_OUT 16
+int lse_gray8_planes(const float *planes_a, const float *planes_b, int32_t H, int32_t W, uint8_t *out, lse_stream_t stream);
+int lse_canny_workspace(int32_t H, int32_t W, int64_t *h_bytes);
+int lse_canny_classify(const uint8_t *gray, int32_t n_images, int32_t H, int32_t W, int32_t low, int32_t high, uint8_t *classes,
+                       lse_stream_t stream);
+int lse_canny_hysteresis(const uint8_t *classes, int32_t n_images, int32_t H, int32_t W, void *workspace, int64_t workspace_bytes,
+                         uint8_t *edges, lse_stream_t stream);
+int lse_canny_u8(const uint8_t *gray, int32_t n_images, int32_t H, int32_t W, int32_t low, int32_t high, void *workspace,
+                 int64_t workspace_bytes, uint8_t *edges, lse_stream_t stream);
+int lse_eval_panels_workspace(int32_t H, int32_t W, int64_t *h_bytes);
+int lse_eval_panels(const float *gt_planes, const float *pred_planes, const float *rgb, const float *pair_gt, const float *pair_pred,
+                    const float *depth, const float *accumulation, const uint8_t *edges, const float *ev_out, int32_t ev_channels,
+                    int32_t H, int32_t W, int32_t flags, void *workspace, int64_t workspace_bytes, uint8_t *grid,
+                    lse_stream_t stream);
+
 /* ---- occupancy grid (nerfacc OccGridEstimator._update) --------------------------- */
 /* occs[id] = max(occs[id]*ema_decay, occ_new); duplicate ids resolve to the maximum over the duplicates (upstream:
  * an arbitrary one of them wins).  workspace: n floats. */

@@ -25,6 +25,7 @@ LSE_TRAVERSE_FMA_SETUP = 1
 LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
 LSE_PREP_EVENT_STATS = 1
 LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
+LSE_PANEL_IMG, LSE_PANEL_DEPTH, LSE_PANEL_ERR_MAP, LSE_PANEL_OVERLAY, LSE_PANEL_EV_OUT = 1, 2, 4, 8, 16
 
 
 class GridDesc(Structure):
@@ -167,6 +168,13 @@ SIGNATURES = {
     "lse_eval_image_prep": [P, I32, P, I32, P, I32, I32, I32, P, P, P, I64, P],
     "lse_log_scale_correct_workspace": [I32, I32, POINTER(c_int64)],
     "lse_log_scale_correct": [P, P, I32, I32, P, I64, P, P, P, P],
+    "lse_gray8_planes": [P, P, I32, I32, P, P],
+    "lse_canny_workspace": [I32, I32, POINTER(c_int64)],
+    "lse_canny_classify": [P, I32, I32, I32, I32, I32, P, P],
+    "lse_canny_hysteresis": [P, I32, I32, I32, P, I64, P, P],
+    "lse_canny_u8": [P, I32, I32, I32, I32, I32, P, I64, P, P],
+    "lse_eval_panels_workspace": [I32, I32, POINTER(c_int64)],
+    "lse_eval_panels": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, I64, P, P],
     "lse_render_weight_fwd": [P, P, P, P, I32, P, P, P, P],
     "lse_render_weight_bwd": [P, P, P, P, I32, P, P, P, P],
     "lse_loss_epilogue_fwd": [POINTER(EpilogueDesc), P, P, I32, P, P, P, P, I32, P, P, P, POINTER(MapperMlp), POINTER(MapperMlp), P, P],

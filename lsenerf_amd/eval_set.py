@@ -11,6 +11,10 @@ image: ``lse_camera_rays`` builds the rays from a device pose table, ``render_fl
 metric) fits the prediction to the ground truth in log space, and ``lse_image_metrics`` writes its two scalars into row ``i`` of a
 device table.  Nothing waits for the device until the last image is enqueued: then one overflow read, the column means on the
 device and ONE read-back of table plus means.
+
+``PanelSet`` adds the images the reference's evaluation writes: per image the uint8 grid of its writer's combined picture (overlay
+of Canny edges included) from ``lse_gray8_planes`` / ``lse_canny_u8`` / ``lse_eval_panels``, copied asynchronously into a row of
+a pinned host buffer -- still without a wait inside the loop.
 """
 from __future__ import annotations
 
@@ -82,7 +86,68 @@ def camera_bundle(eval_set: EvalSet, i: int) -> RayBundle:
                      camera_indices=torch.full((H, W, 1), cam, dtype=torch.long, device=dev), times=times, metadata=meta)
 
 
-def _image_dict(outputs: Dict[str, Tensor], gt_planes: Tensor, pred_planes: Tensor, pair=None) -> Dict[str, Tensor]:
+class PanelSet:
+    """uint8 panels of a whole eval set, in the layout of the reference's writer (R:lse_nerf/lse_writer.py:32-64: every image of
+    the dictionary but "accumulation" as ``clamp(v * 255, 0, 255)`` uint8, concatenated along the width).
+
+        panel_set = PanelSet(eval_set)                                  # keys: a subset of ops.PANEL_KEYS, in that order
+        model.evaluate_set(eval_set, panels=panel_set)
+        panel_set.host[i]                                               # [H, Wtot, 3] uint8: comb_imgs/00i.png plus the overlay column
+
+    Holds a device buffer for one image's grid and a pinned host buffer for the set.  ``evaluate_set`` launches the grey / Canny /
+    panel kernels behind the metrics of image ``i`` and issues ONE asynchronous device-to-host copy of the grid into row ``i``; it
+    adds no wait: the rows are valid after the wait ``evaluate_set`` ends with (copies and kernels share one stream).  "ev_out" is
+    a column only when the model renders it (the writer walks the dictionary's keys); ``columns`` names what the last set produced
+    and ``host`` is shaped to it.  "overlay" does not need ``config.eval_overlay``.  Writing files stays the caller's business."""
+
+    def __init__(self, eval_set: EvalSet, keys=ops.PANEL_KEYS):
+        keys = tuple(keys)
+        if not keys or any(k not in ops.PANEL_KEYS for k in keys):
+            raise ValueError(f"PanelSet: keys must be a non-empty subset of {ops.PANEL_KEYS}, got {keys}")
+        d = eval_set.data
+        self.keys = tuple(k for k in ops.PANEL_KEYS if k in keys)
+        self.n, self.H, self.W = d.n_images, d.H, d.W
+        dev = eval_set.device
+        cells = self.H * ops.panel_columns(self.keys) * self.W * 3          # sized for every key; a set without "ev_out" uses less
+        self._dev = torch.empty(cells, dtype=torch.uint8, device=dev)
+        self._host = torch.empty(self.n * cells, dtype=torch.uint8, pin_memory=True)
+        self._gray = torch.empty((2, self.H, self.W), dtype=torch.uint8, device=dev)
+        self._edges = torch.empty((2, self.H, self.W), dtype=torch.uint8, device=dev)
+        self._canny_ws = torch.empty(ops.canny_workspace_bytes(self.H, self.W, 2) // 8, dtype=torch.int64, device=dev)
+        self._ws = torch.empty(ops.eval_panels_workspace_bytes(self.H, self.W) // 4, dtype=torch.float32, device=dev)
+        self.columns: Tuple[str, ...] = ()
+        self.host: Optional[Tensor] = None
+
+    def _begin(self, outputs: Dict[str, Tensor]) -> None:
+        """Fix the columns of this set from the first image's outputs and shape ``host`` to them (host work only)."""
+        self.columns = tuple(k for k in self.keys if k != "ev_out" or outputs.get("ev_out") is not None)
+        if not self.columns:
+            raise ValueError("PanelSet: the only key is \"ev_out\" and the model renders none")
+        self._cells = self.H * ops.panel_columns(self.columns) * self.W * 3
+        self.host = self._host[:self.n * self._cells].view(self.n, self.H, -1, 3)
+
+    def edges(self, gt_planes: Tensor, pred_planes: Tensor) -> Tensor:
+        """uint8 [2, H, W]: the Canny edges (50, 200) of the 8-bit grey ground truth and prediction (buffers of this object)."""
+        ops.gray8_planes(gt_planes, pred_planes, out=self._gray)
+        return ops.canny_edges(self._gray, out=self._edges, workspace=self._canny_ws)
+
+    def add(self, i: int, outputs: Dict[str, Tensor], gt_planes: Tensor, pred_planes: Tensor, pair=None) -> Tensor:
+        """Enqueue the grid of image ``i`` and its copy into ``host[i]``; returns the device grid [H, Wtot, 3] (overwritten by the
+        next image).  ``outputs``: the [H, W, C] outputs; ``pair``: the grey pair of the event-only metric as "img"."""
+        if i == 0 or self.host is None:
+            self._begin(outputs)
+        edges = self.edges(gt_planes, pred_planes) if "overlay" in self.columns else None
+        ev = outputs.get("ev_out") if "ev_out" in self.columns else None
+        grid = self._dev[:self._cells].view(self.H, -1, 3)
+        ops.eval_panels(self.columns, self.H, self.W, gt_planes=gt_planes, pred_planes=pred_planes,
+                        rgb=outputs["rgb"].to(torch.float32).contiguous(), pair=pair,
+                        depth=outputs["depth"].contiguous(), accumulation=outputs["accumulation"].contiguous(), edges=edges,
+                        ev_out=None if ev is None else ev.to(torch.float32).contiguous(), out=grid, workspace=self._ws)
+        self.host[i].copy_(grid, non_blocking=True)
+        return grid
+
+
+def _image_dict(outputs: Dict[str, Tensor], gt_planes: Tensor, pred_planes: Tensor, pair=None, overlay=None) -> Dict[str, Tensor]:
     """The reference's image dictionary (``evaluation.image_metrics_and_images``) from the metric planes; ``pair`` = (grey ground
     truth, corrected prediction) [1, 1, H, W]: the "img" of the event-only metric (R:lse_nerf/lse_pipeline.py:171-181)."""
     image, rgb = gt_planes[0].permute(1, 2, 0), pred_planes[0].permute(1, 2, 0)          # masked, [H, W, 3]
@@ -93,6 +158,8 @@ def _image_dict(outputs: Dict[str, Tensor], gt_planes: Tensor, pred_planes: Tens
     images = {"img": img, "accumulation": evaluation.gray_colormap(outputs["accumulation"]),
               "depth": evaluation.depth_gray_map(outputs["depth"], outputs["accumulation"]),
               "err_map": evaluation.make_error_map(image, rgb)}
+    if overlay is not None:
+        images["overlay"] = overlay
     if outputs.get("ev_out") is not None:
         images["ev_out"] = outputs["ev_out"]
     return images
@@ -100,8 +167,8 @@ def _image_dict(outputs: Dict[str, Tensor], gt_planes: Tensor, pred_planes: Tens
 
 @torch.no_grad()
 def evaluate_set(model, eval_set: EvalSet, events_only: bool = False,
-                 on_image: Optional[Callable[[int, Dict[str, Tensor], Dict[str, Tensor]], None]] = None
-                 ) -> Tuple[Dict[str, float], List[Dict[str, float]]]:
+                 on_image: Optional[Callable[[int, Dict[str, Tensor], Dict[str, Tensor]], None]] = None,
+                 panels: Optional[PanelSet] = None) -> Tuple[Dict[str, float], List[Dict[str, float]]]:
     """``(average, per_image)`` over every image of ``eval_set`` (R:lse_nerf/lse_pipeline.py:186-233): ``per_image[i]`` holds
     "psnr" (10 log10(1 / mse), float32 on the device), "ssim", and "lpips" only where ``model.lpips.available``; ``average`` their
     float32 column means (taken on the device) plus "num_rays_per_sec" and "fps".
@@ -119,11 +186,19 @@ def evaluate_set(model, eval_set: EvalSet, events_only: bool = False,
 
     ``on_image(i, outputs, images)``: called per image with the [H, W, C] outputs and the reference's image dictionary ("img",
     "accumulation", "depth", "err_map", "ev_out" when rendered; with ``events_only`` "img" is the grey pair).  The tensors are on
-    the device, are not read back here, and those of the dictionary alias buffers the next image overwrites."""
+    the device, are not read back here, and those of the dictionary alias buffers the next image overwrites.  With
+    ``config.eval_overlay`` the dictionary also holds "overlay" (``evaluation.make_overlay``), after "err_map".
+
+    ``panels``: a ``PanelSet`` of this eval set.  Behind the metrics of image ``i`` its uint8 grid is computed on the device and
+    copied asynchronously into ``panels.host[i]``; the metrics are untouched and no wait is added -- the rows are valid when this
+    function returns."""
     d = eval_set.data
     n, H, W = d.n_images, d.H, d.W
     if n == 0:
         raise ValueError("empty eval set")
+    if panels is not None and (panels.n, panels.H, panels.W) != (n, H, W):
+        raise ValueError(f"the PanelSet holds {panels.n} images of {panels.H} x {panels.W}, the eval set {n} of {H} x {W}")
+    want_overlay = on_image is not None and bool(getattr(getattr(model, "config", None), "eval_overlay", False))
     dev = eval_set.device
     lpips = model.lpips
     has_lpips = bool(getattr(lpips, "available", True))
@@ -155,9 +230,14 @@ def evaluate_set(model, eval_set: EvalSet, events_only: bool = False,
             ops.image_metrics(a, b, out=table[i], workspace=ws)          # (ground truth, prediction): the reference's order
             if has_lpips:
                 table[i, _LPIPS] = lpips(a.expand(-1, 3, -1, -1), b.expand(-1, 3, -1, -1)) if events_only else lpips(a, b)
-            if on_image is not None:
+            if on_image is not None or panels is not None:
                 outputs = {k: v.reshape(H, W, -1) for k, v in out.items()}
-                on_image(i, outputs, _image_dict(outputs, gt_pl, pr_pl, (gray, corrected) if events_only else None))
+                img_pair = (gray, corrected) if events_only else None
+            if panels is not None:
+                panels.add(i, outputs, gt_pl, pr_pl, img_pair)
+            if on_image is not None:
+                overlay = evaluation.make_overlay(gt_pl, pr_pl) if want_overlay else None
+                on_image(i, outputs, _image_dict(outputs, gt_pl, pr_pl, img_pair, overlay))
         model.occupancy_grid.check_deferred_overflow()          # the one overflow read of the set
         table[:, _PSNR] = 10.0 * torch.log10(1.0 / table[:, _MSE])
         rows = torch.cat([table, table.mean(dim=0, keepdim=True)]).tolist()          # the one read-back

@@ -9,7 +9,8 @@
   route composites each chunk in segments of the ray and stops evaluating the field on rays that have become opaque
   (``_render_early_stop``; opt-in, still without a host synchronisation inside the loops).
 * ``image_metrics_and_images`` -- R:lse_nerf/lsenerf.py:477-530 restated: psnr / ssim from one ``lse_image_metrics`` launch, lpips
-  when torchmetrics is importable, and the image dictionary (no "overlay": it needs OpenCV's Canny).
+  when torchmetrics is importable, and the image dictionary ("overlay" with ``config.eval_overlay``: Canny edges on the device).
+* ``make_overlay`` -- R:lse_nerf/lsenerf.py:462-475: where the rendered edges lie against the true ones (``ops.canny_edges``).
 * ``make_lpips`` -- torchmetrics' ``LearnedPerceptualImagePatchSimilarity(normalize=True)``, or a callable that names what is missing.
 """
 from __future__ import annotations
@@ -304,6 +305,20 @@ def depth_gray_map(depth: Tensor, accumulation: Tensor) -> Tensor:
 
 
 @torch.no_grad()
+def make_overlay(image_planes: Tensor, pred_planes: Tensor) -> Tensor:
+    """R:lse_nerf/lsenerf.py:462-475 on the device: float32 [H, W, 3] with values in {0, 1} -- white; black where the Canny edges
+    (50, 200) of the 8-bit grey ground truth or prediction lie; then red = 1 on the ground truth's edges and blue = 1 on the
+    prediction's (both: magenta).  ``image_planes`` / ``pred_planes``: float32 [3, H, W] or [1, 3, H, W], the masked images as
+    ``ops.eval_image_prep`` writes them.  The reference returns ``overlay / 255`` in float64; its values are 0 and 1 as well, so
+    these are the same numbers in float32.  The edges are ``ops.canny_edges``: OpenCV's published algorithm restated, parity
+    unpinned (OpenCV is no dependency); the grey is ``lse_eval_image_prep``'s, as the reference's matmul order is not knowable."""
+    H, W = int(image_planes.shape[-2]), int(image_planes.shape[-1])
+    edges = ops.canny_edges(ops.gray8_planes(image_planes, pred_planes))
+    grid = ops.eval_panels(("overlay",), H, W, edges=edges)
+    return grid.to(torch.float32) / 255.0
+
+
+@torch.no_grad()
 def image_metrics_and_images(model, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]):
     dev = outputs["rgb"].device
     image = batch["image"].to(dev)
@@ -315,10 +330,12 @@ def image_metrics_and_images(model, outputs: Dict[str, Tensor], batch: Dict[str,
               "accumulation": gray_colormap(outputs["accumulation"]),
               "depth": depth_gray_map(outputs["depth"], outputs["accumulation"]),
               "err_map": make_error_map(image, rgb)}
-    if outputs.get("ev_out") is not None:
-        images["ev_out"] = outputs["ev_out"]
     img_b = torch.moveaxis(image, -1, 0)[None].float().contiguous()     # [H, W, C] -> [1, C, H, W]
     rgb_b = torch.moveaxis(rgb, -1, 0)[None].float().contiguous()
+    if getattr(getattr(model, "config", None), "eval_overlay", False):
+        images["overlay"] = make_overlay(img_b, rgb_b)
+    if outputs.get("ev_out") is not None:
+        images["ev_out"] = outputs["ev_out"]
     ssim, mse = ops.image_metrics(img_b, rgb_b)
     psnr = 10.0 * torch.log10(1.0 / mse)
     values = torch.stack([psnr, ssim]).tolist()

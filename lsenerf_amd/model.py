@@ -78,6 +78,10 @@ class LSENeRFModelConfig:
     # base segment length S, a positive multiple of 64 (checked at render time): the segments are S, S, 2S, 4S, ... samples long
     # (evaluation.segment_schedule), each a fixed set of launches whether or not a ray is still alive.
     eval_segment_samples: int = 128
+    # the reference's "overlay" image (R:lse_nerf/lsenerf.py:462-475: Canny edges of ground truth and prediction) in the image
+    # dictionaries of ``get_image_metrics_and_images`` and ``evaluate_set``'s ``on_image``, after "err_map".  Computed on the
+    # device (``ops.canny_edges``; OpenCV's published algorithm restated, parity unpinned).  Off: the dictionaries are as before.
+    eval_overlay: bool = False
 
     def __post_init__(self):   # R:lse_nerf/lsenerf.py:86-99
         if self.evs_mapping_method is None or str(self.evs_mapping_method).lower() == "none":
@@ -582,7 +586,7 @@ class LSENeRFModel(nn.Module):
         ``batch["msk"]`` when present).  metrics: "psnr" (10 log10(1 / mse)) and "ssim" from one ``lse_image_metrics`` launch, plus
         "lpips" only where torchmetrics is importable -- the key is omitted otherwise.  images: "img" (ground truth beside the
         unmasked prediction), "err_map", grey "accumulation" and "depth" maps, and "ev_out" when rendered.  The reference's
-        "overlay" needs OpenCV's Canny edges and is not produced."""
+        "overlay" (Canny edges of both images, ``evaluation.make_overlay``) is added with ``config.eval_overlay``."""
         return evaluation.image_metrics_and_images(self, outputs, batch)
 
     @torch.no_grad()
@@ -591,12 +595,13 @@ class LSENeRFModel(nn.Module):
         [H, W, C] outputs.  ``camera_opt_to_camera``: a pose correction as ``EdCameras.generate_rays`` takes it."""
         return evaluation.render_camera(self, cameras, camera_index, camera_opt_to_camera)
 
-    def evaluate_set(self, eval_set, events_only: bool = False, on_image=None):
+    def evaluate_set(self, eval_set, events_only: bool = False, on_image=None, panels=None):
         """``(average, per_image)`` metrics over a device-resident ``eval_set.EvalSet`` -- the reference pipeline's
         ``get_average_eval_image_metrics`` without host work or a wait per image; ``events_only``: its ``update_evs_only_metric``
-        (grey, scale-corrected psnr / ssim).  See ``lsenerf_amd.eval_set.evaluate_set``."""
+        (grey, scale-corrected psnr / ssim); ``panels``: an ``eval_set.PanelSet`` that receives every image's uint8 panel grid.  See
+        ``lsenerf_amd.eval_set.evaluate_set``."""
         from . import eval_set as _eval_set
-        return _eval_set.evaluate_set(self, eval_set, events_only=events_only, on_image=on_image)
+        return _eval_set.evaluate_set(self, eval_set, events_only=events_only, on_image=on_image, panels=panels)
 
     def _ngp_metrics_dict(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]) -> Dict[str, Tensor]:
         image = batch["image"].to(outputs["rgb"].device)

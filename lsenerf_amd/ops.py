@@ -1515,6 +1515,180 @@ def log_scale_correct(gt_planes: torch.Tensor, rgb: torch.Tensor, stats: torch.T
 
 
 # ----------------------------------------------------------------------------------------------------
+# eval panels: 8-bit grey, Canny edges, the writer's uint8 grid (csrc/panels.hip)
+# ----------------------------------------------------------------------------------------------------
+PANEL_KEYS = ("img", "depth", "err_map", "overlay", "ev_out")          # the grid's column order; "img" is two images wide
+_PANEL_FLAG = {"img": _lib.LSE_PANEL_IMG, "depth": _lib.LSE_PANEL_DEPTH, "err_map": _lib.LSE_PANEL_ERR_MAP,
+               "overlay": _lib.LSE_PANEL_OVERLAY, "ev_out": _lib.LSE_PANEL_EV_OUT}
+
+
+def _u8(t, name, allow_none=False):
+    return _chk(t, torch.uint8, name, allow_none)
+
+
+def _planes_hw(t: torch.Tensor, name: str) -> Tuple[int, int]:
+    if t.dim() < 3 or t.numel() != 3 * t.shape[-2] * t.shape[-1] or t.shape[-3] != 3:
+        raise ValueError(f"{name} must be [3, H, W] or [1, 3, H, W], got {tuple(t.shape)}")
+    return int(t.shape[-2]), int(t.shape[-1])
+
+
+def _images_u8(t: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    if t.dim() not in (2, 3) or t.numel() == 0:
+        raise ValueError(f"{name} must be a non-empty uint8 [H, W] or [n, H, W], got {tuple(t.shape)}")
+    return (1 if t.dim() == 2 else int(t.shape[0])), int(t.shape[-2]), int(t.shape[-1])
+
+
+def canny_workspace_bytes(H: int, W: int, n_images: int = 1) -> int:
+    v = ctypes.c_int64(0)
+    _lib.call("lse_canny_workspace", int(H), int(W), ctypes.byref(v))
+    return int(v.value) * int(n_images)
+
+
+def _canny_workspace(workspace, n, H, W, device, name):
+    nbytes = canny_workspace_bytes(H, W, n)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    elif workspace.numel() * workspace.element_size() < nbytes or workspace.element_size() != 8:
+        raise ValueError(f"{name}: an 8-byte-typed workspace of at least {nbytes} bytes expected (canny_workspace_bytes)")
+    if not workspace.is_cuda or not workspace.is_contiguous():
+        raise _lib.LseHipError(f"{name}: the workspace must be a contiguous tensor on the GPU; the HIP path has no CPU fallback")
+    return workspace, ctypes.c_void_p(workspace.data_ptr()), nbytes
+
+
+@torch.no_grad()
+def gray8_planes(planes_a: torch.Tensor, planes_b: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [2, H, W] (or [1, H, W] without ``planes_b``): ``clip(grey * 255, 0, 255)`` truncated, of the float32 [3, H, W] planes
+    ``eval_image_prep`` writes, grey = (0.2989 r + 0.5870 g) + 0.1140 b as that kernel takes it (lse_gray8_planes).  What the
+    reference's ``_make_overlay`` feeds ``cv2.Canny``; a NaN gives 0 (numpy's cast of a NaN is undefined)."""
+    H, W = _planes_hw(planes_a, "gray8_planes: planes_a")
+    if planes_b is not None and _planes_hw(planes_b, "gray8_planes: planes_b") != (H, W):
+        raise ValueError("gray8_planes: the two images differ in size")
+    n = 1 if planes_b is None else 2
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=planes_a.device)
+    elif out.numel() != n * H * W:
+        raise ValueError(f"gray8_planes: out must be [{n}, {H}, {W}]")
+    _lib.call("lse_gray8_planes", _f32(planes_a, "planes_a"), _f32(planes_b, "planes_b", allow_none=True), H, W, _u8(out, "out"),
+              _stream())
+    return out
+
+
+@torch.no_grad()
+def canny_classify(gray_u8: torch.Tensor, low: int = 50, high: int = 200, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The class map (0 none, 1 weak, 2 strong; uint8, shaped like the input) of ``gray_u8`` [H, W] or [n, H, W]: OpenCV's
+    ``Canny(image, low, high)`` (aperture 3, L1 gradient) up to the hysteresis, restated from the published algorithm -- parity
+    unpinned (lse_canny_classify).  ``low`` / ``high`` are floored to integers as OpenCV floors them."""
+    n, H, W = _images_u8(gray_u8, "canny_classify: gray_u8")
+    ptr = _u8(gray_u8, "gray_u8")
+    if out is None:
+        out = torch.empty_like(gray_u8)
+    elif out.shape != gray_u8.shape:
+        raise ValueError("canny_classify: out must have the input's shape")
+    _lib.call("lse_canny_classify", ptr, n, H, W, int(low // 1), int(high // 1), _u8(out, "out"), _stream())
+    return out
+
+
+@torch.no_grad()
+def canny_hysteresis(classes: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Edges (uint8 0 / 255, shaped like the input) of a class map: strong pixels, and weak ones 8-connected to a strong one through
+    weak and strong pixels (lse_canny_hysteresis: union-find on the device, three bounded launches, no host loop; the result is a
+    set, so two calls are bit-equal).  ``workspace``: an int64 / float64 device tensor of ``canny_workspace_bytes(H, W, n)`` bytes
+    (allocated when absent; its content does not matter).  ``out`` may be ``classes``."""
+    n, H, W = _images_u8(classes, "canny_hysteresis: classes")
+    ptr = _u8(classes, "classes")
+    if out is None:
+        out = torch.empty_like(classes)
+    elif out.shape != classes.shape:
+        raise ValueError("canny_hysteresis: out must have the input's shape")
+    workspace, ws_ptr, nbytes = _canny_workspace(workspace, n, H, W, classes.device, "canny_hysteresis")
+    _lib.call("lse_canny_hysteresis", ptr, n, H, W, ws_ptr, nbytes, _u8(out, "out"), _stream())
+    return out
+
+
+@torch.no_grad()
+def canny_edges(gray_u8: torch.Tensor, low: int = 50, high: int = 200, out: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``cv2.Canny(gray_u8, low, high)`` (uint8 0 / 255) of a uint8 [H, W] image or [n, H, W] stack on the device: ``canny_classify``
+    then ``canny_hysteresis`` on one stream (lse_canny_u8).  Restated from OpenCV's published algorithm; OpenCV is no dependency, so
+    that parity is UNPINNED -- the tests hold the kernels against a numpy twin.  The reference's ``detect_edges`` uses (50, 200)."""
+    n, H, W = _images_u8(gray_u8, "canny_edges: gray_u8")
+    ptr = _u8(gray_u8, "gray_u8")
+    if out is None:
+        out = torch.empty_like(gray_u8)
+    elif out.shape != gray_u8.shape:
+        raise ValueError("canny_edges: out must have the input's shape")
+    workspace, ws_ptr, nbytes = _canny_workspace(workspace, n, H, W, gray_u8.device, "canny_edges")
+    _lib.call("lse_canny_u8", ptr, n, H, W, int(low // 1), int(high // 1), ws_ptr, nbytes, _u8(out, "out"), _stream())
+    return out
+
+
+def eval_panels_workspace_bytes(H: int, W: int) -> int:
+    v = ctypes.c_int64(0)
+    _lib.call("lse_eval_panels_workspace", int(H), int(W), ctypes.byref(v))
+    return int(v.value)
+
+
+def panel_columns(keys) -> int:
+    """Width of the grid of ``keys`` in images ("img" counts two)."""
+    return sum(2 if k == "img" else 1 for k in PANEL_KEYS if k in keys)
+
+
+@torch.no_grad()
+def eval_panels(keys, H: int, W: int, gt_planes=None, pred_planes=None, rgb=None, pair=None, depth=None, accumulation=None,
+                edges=None, ev_out=None, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The uint8 grid [H, columns * W, 3] the reference's ``LSEWriter`` saves as its combined image, in one launch behind a
+    two-stage min / max of ``depth`` (lse_eval_panels).  ``keys`` selects among ``PANEL_KEYS``; the columns always come in that order:
+    "img" (``gt_planes`` [3, H, W] masked beside ``rgb`` [H * W, 3] unmasked, or the grey ``pair`` = (ground truth, prediction) of
+    the event-only metric), "depth" (``depth_gray_map(depth, accumulation)``), "err_map" (``make_error_map`` of ``gt_planes`` and
+    ``pred_planes``), "overlay" (from ``edges`` uint8 [2, H, W] = ``canny_edges(gray8_planes(gt_planes, pred_planes))``) and
+    "ev_out" ([H, W, 1 or 3]).  Every value is ``clamp(v * 255, 0, 255)`` truncated, v the float32 expression of ``evaluation.py``
+    with each operation rounded once; a NaN gives 0.  ``workspace``: float32, ``eval_panels_workspace_bytes`` bytes; its first
+    two elements hold the depth's (near, far) afterwards."""
+    keys = tuple(keys)
+    unknown = [k for k in keys if k not in _PANEL_FLAG]
+    if unknown or not keys:
+        raise ValueError(f"eval_panels: keys must be a non-empty subset of {PANEL_KEYS}, got {keys}")
+    H, W = int(H), int(W)
+    flags = 0
+    for k in keys:
+        flags |= _PANEL_FLAG[k]
+    n = H * W
+
+    def want(t, name, numel, dtype=torch.float32):
+        if t is None:
+            return None
+        if t.numel() != numel:
+            raise ValueError(f"eval_panels: {name} must hold {numel} elements for a {H} x {W} image, got {tuple(t.shape)}")
+        return _chk(t, dtype, name)
+    pair_gt, pair_pred = (None, None) if pair is None else pair
+    ev_channels = 0
+    if ev_out is not None:
+        ev_channels = int(ev_out.shape[-1])
+        if ev_channels not in (1, 3):
+            raise ValueError(f"eval_panels: ev_out must be [H, W, 1] or [H, W, 3], got {tuple(ev_out.shape)}")
+    given = [t for t in (gt_planes, pred_planes, rgb, pair_gt, depth, edges, ev_out) if t is not None]
+    if not given:
+        raise ValueError(f"eval_panels: no input for {keys}")
+    device = given[0].device
+    cols = panel_columns(keys)
+    if out is None:
+        out = torch.empty((H, cols * W, 3), dtype=torch.uint8, device=device)
+    elif out.numel() != n * cols * 3:
+        raise ValueError(f"eval_panels: out must be [{H}, {cols * W}, 3]")
+    nbytes = eval_panels_workspace_bytes(H, W)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    elif workspace.numel() * 4 < nbytes:
+        raise ValueError(f"eval_panels: workspace of {workspace.numel() * 4} bytes, {nbytes} needed")
+    _lib.call("lse_eval_panels", want(gt_planes, "gt_planes", 3 * n), want(pred_planes, "pred_planes", 3 * n), want(rgb, "rgb", 3 * n),
+              want(pair_gt, "pair[0]", n), want(pair_pred, "pair[1]", n), want(depth, "depth", n),
+              want(accumulation, "accumulation", n), want(edges, "edges", 2 * n, torch.uint8),
+              want(ev_out, "ev_out", n * max(ev_channels, 1)), ev_channels, H, W, flags, _f32(workspace, "workspace"), nbytes,
+              _u8(out, "out"), _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------
 # training epilogue: routing + mappers + losses
 # ----------------------------------------------------------------------------------------------------
 def _mapper_mlp_shapes(in_dim: int):

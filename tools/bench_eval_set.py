@@ -115,18 +115,19 @@ def measure(fn):
     return rows, wall, device_ms, len(events) / N_CAM, waits, ops.SYNC_STATS["count"] - s0
 
 
-results = {}
-for name, fn in ROUTES.items():
-    rows, wall, device_ms, calls, waits, sampler = measure(fn)
-    results[name] = (rows, sum(wall) / len(wall))
-    print(json.dumps({"route": name, "images": N_CAM, "rays_per_image": H * W, "chunk": CHUNK, "repeats": REPEATS,
-                      "wall_ms_per_image": round(sum(wall) / len(wall), 2), "wall_ms_per_image_runs": [round(w, 2) for w in wall],
-                      "device_ms_per_image": round(device_ms, 2), "library_calls_per_image": round(calls, 1),
-                      "waits_per_set": waits, "sampler_syncs_per_set": sampler,
-                      "mean_psnr": round(sum(r["psnr"] for r in rows) / N_CAM, 4),
-                      "mean_ssim": round(sum(r["ssim"] for r in rows) / N_CAM, 6)}), flush=True)
-rows_a, wall_a = results["a_render_camera_plus_image_metrics"]
-rows_b, wall_b = results["b_evaluate_set"]
-# (a)'s rays come from torch on the host, (b)'s from the device kernel: equal to rounding, so the metrics agree closely, not bit for bit
-diff = {k: max(abs(ra[k] - rb[k]) for ra, rb in zip(rows_a, rows_b)) for k in ("psnr", "ssim")}
-print(json.dumps({"a_vs_b_max_abs_diff": diff, "wall_ratio_a_over_b": round(wall_a / wall_b, 3)}), flush=True)
+if __name__ == "__main__":          # (tools/bench_eval_panels.py imports the scene above)
+    results = {}
+    for name, fn in ROUTES.items():
+        rows, wall, device_ms, calls, waits, sampler = measure(fn)
+        results[name] = (rows, sum(wall) / len(wall))
+        print(json.dumps({"route": name, "images": N_CAM, "rays_per_image": H * W, "chunk": CHUNK, "repeats": REPEATS,
+                          "wall_ms_per_image": round(sum(wall) / len(wall), 2), "wall_ms_per_image_runs": [round(w, 2) for w in wall],
+                          "device_ms_per_image": round(device_ms, 2), "library_calls_per_image": round(calls, 1),
+                          "waits_per_set": waits, "sampler_syncs_per_set": sampler,
+                          "mean_psnr": round(sum(r["psnr"] for r in rows) / N_CAM, 4),
+                          "mean_ssim": round(sum(r["ssim"] for r in rows) / N_CAM, 6)}), flush=True)
+    rows_a, wall_a = results["a_render_camera_plus_image_metrics"]
+    rows_b, wall_b = results["b_evaluate_set"]
+    # (a)'s rays come from torch on the host, (b)'s from the device kernel: equal to rounding, so the metrics agree closely, not bit for bit
+    diff = {k: max(abs(ra[k] - rb[k]) for ra, rb in zip(rows_a, rows_b)) for k in ("psnr", "ssim")}
+    print(json.dumps({"a_vs_b_max_abs_diff": diff, "wall_ratio_a_over_b": round(wall_a / wall_b, 3)}), flush=True)
