@@ -213,36 +213,25 @@ int lse_hash_bwd_levels(const lse_grid_desc *desc, const float *x01, const float
                         float *dtable, float *dx, int32_t dx_accumulate, int32_t level_begin, int32_t level_end,
                         int64_t n, const int64_t *n_dev, lse_stream_t stream);
 
-/* Kernel selection of the hash backward as CALL ARGUMENTS (so that two variants can be compared inside one process):
- *   impl          2 = lane-per-sample kernel, per-wave LDS sector cache keyed by GLOBAL sector id, the run ends of several
- *                     levels batched into one cache pass (default); 1 = one cache pass per level; 0 = 16-lanes-per-sample kernel
+/* Options of the hash backward as CALL ARGUMENTS (so that two settings can be compared inside one process):
+ *   impl          2 = lane-per-sample kernel with a per-wave LDS cache of 512 table sectors (32 B, paired by 64-B line, keyed by
+ *                     GLOBAL sector id), the run ends of several levels batched into one cache pass, one wave per workgroup
+ *                     (default; csrc/hashgrid.hip); 0 = 16-lanes-per-sample kernel (also taken when a level does not start on a
+ *                     64-byte line)
  *   stage_max     impl 2: with an empty queue, a level that ends more than stage_max runs in the wave passes unstaged (default 48;
  *                     56 is better when the step size is constant: profiles/r05_hash_bwd_thresholds_final.txt)
- *   gran          cache slots: 2 = 512 slots of one 32-B sector; 3 (impl 1 only) = 256 slots of one 64-B line; 4 (impl 2) =
- *                     512 sector slots PAIRED by 64-B line, flushed in slot order -- a float-atomic request costs the same for 4 .. 64
- *                     contiguous bytes (tools/micro/atomic_gran.hip), so sibling sectors leave as one request; 5 = the same with
- *                     256 slots (three workgroups per CU: faster cache passes, more collision requests -- equal at the metric size);
- *                     6 (impl 2, default) = 4 with the second-generation flush (list stored trip-major transposed, payload read and
- *                     zeroed by one LDS exchange, keys reset in bulk: 9 instead of 20 LDS instructions per 32 flushed slots);
- *                     -- in workgroups of ONE wave since round 5 (a workgroup's LDS is released when its last wave retires);
- *                     development build only: 8 = 6 with 320 slots in workgroups of four waves (12 waves per CU), 9 / 11 = 384
- *                     slots in workgroups of two / one waves (10 / 9 waves per CU), 10 = 448 slots, one wave (9 waves per CU),
- *                     12 / 13 = 512 slots in workgroups of four (the shape until round 5) / two waves
- *   few_runs      impl 1, 2: a wave that ends <= few_runs runs at a level adds them straight to memory (default 8; 3 is better when
+ *   few_runs      impl 2: a wave that ends <= few_runs runs at a level adds them straight to memory (default 8; 3 is better when
  *                     the step size is constant)
- *   second_probe  impl 1, 2: extra probe rounds (home slot + k * step, k = 1 .. second_probe) before a corner falls back to memory (default 3)
- *   rounds        impl 0: 16 / 32 / 64 rounds of 4 samples per wave (default 32)
- *   interleave_from_scale  impl 0: levels with scale >= this use the interleaved sample mapping (default: never)
- *   coarse_levels the levels below this one are processed first by a cache-free kernel at high occupancy (lane = sample, run
- *                     ends transposed through a 1.5 KB staging area, 16 lanes per run add straight to memory); every value is
- *                     correct, the split only moves time between the two kernels
+ *   second_probe  impl 2: extra probe rounds (home slot + 2 * k, k = 1 .. second_probe) before a corner falls back to memory (default 3)
  *   replicas, replica_levels, workspace, workspace_bytes
  *                 the coarsest levels are a few thousand 64-byte lines that EVERY wave of a launch adds to, and the memory-side
- *                 atomic units serialise requests to one line: the direct adds (few_runs path, coarse kernel) of the levels below
+ *                 atomic units serialise requests to one line: the direct adds (few_runs path) of the levels below
  *                 replica_levels (default 4: 1 MB of table) go to one of `replicas` (default 16, a power of two) zero-initialised copies
  *                 in `workspace`, chosen by the index of the wave's group of four, and a small kernel folds them into dtable at the end of the call
  *                 (leaving the workspace zero).  workspace == NULL (lse_hash_bwd, lse_hash_bwd_levels): no replicas, same values
- *   dbg           timing experiments only (bit 0: skip flush atomics, bit 1: skip run ends, bit 2: skip the scan) -> WRONG results
+ *   gran, rounds, dbg, interleave_from_scale, coarse_levels, prefetch
+ *                 RESERVED: they selected development variants that are retired (DESIGN_HISTORY.md).  Leave them at the value
+ *                 lse_hash_bwd_default_opts writes; any other value, and impl 1, is answered with LSE_E_UNSUPPORTED.
  * lse_hash_bwd / lse_hash_bwd_levels use lse_hash_bwd_default_opts(). */
 typedef struct lse_hash_bwd_opts {
     int32_t impl, gran, few_runs, second_probe, rounds, dbg;
@@ -252,7 +241,7 @@ typedef struct lse_hash_bwd_opts {
     int32_t replicas, replica_levels;
     void *workspace;            /* device memory, zero on entry, zero again when the call's kernels have run; NULL = no replicas */
     int64_t workspace_bytes;
-    int32_t prefetch;           /* gran 6: fetch level l+1's dy / table operands before level l's cache pass (see hashgrid.hip) */
+    int32_t prefetch;           /* reserved (see above) */
 } lse_hash_bwd_opts;
 void lse_hash_bwd_default_opts(lse_hash_bwd_opts *opts);
 /* bytes of `workspace` that lse_hash_bwd_ex needs for opts->replicas x the levels below opts->replica_levels (NULL = defaults).

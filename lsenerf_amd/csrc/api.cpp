@@ -31,8 +31,6 @@ static Option g_options[] = {
 #else
 static const Option g_options[] = {
 #endif
-    {"hash_fwd_mapping", 4},
-    {"hash_fwd_lds_levels", 0},
     {"compact_features_groups", 4},
     {"mlp_fwd_cfg", 28},
     {"mlp_bwd_cfg", 28},

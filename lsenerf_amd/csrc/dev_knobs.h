@@ -3,14 +3,10 @@
  *
  * Not part of the C-ABI: the library that ships (liblse_hip.so, include/lse_hip.h) has no global or thread-local state, does not
  * export these two functions and compiles the knobs below in as constants (csrc/api.cpp); the superseded kernel variants they
- * select (other tile shapes, the one-cache-pass-per-level hash backward, the cache-free coarse-level kernel, the LDS-resident hash
- * forward, earlier flush generations) exist in the development build only.  Used by the A/B tools under tools/ and by the tests
- * that hold every variant against the oracle (tests/test_gpu_parity.py, `_lib.dev_library()`).
+ * select (other MLP tile shapes, the generic MLP backward, the serial marcher) exist in the development build only.  The hash-grid
+ * kernels have no such variants: csrc/hashgrid.hip compiles to the same kernels in both builds.  Used by the A/B tools under tools/
+ * and by the tests that hold every variant against the oracle (tests/test_gpu_parity.py, `_lib.dev_library()`).
  *
- *   "hash_fwd_mapping"  workgroup -> (level, chunk) order of lse_hash_fwd: 4 = level-major, finest level first (default),
- *                       3 = level-major coarse first, 0 / 1 = XCD-bound levels, 2 = level-interleaved
- *   "hash_fwd_lds_levels"  k coarsest levels whose whole table fits one CU's LDS run in hash_fwd_lds_kernel (default 0;
- *                       bit-identical, 2 - 5 % slower: DESIGN.md appendix)
  *   "compact_features_groups"  level groups per launch of lse_compact_features (default 4)
  *   "mlp_fwd_cfg" / "mlp_bwd_cfg"  CT * 10 + NW tile shape of the f32-MFMA fused MLP kernels (default 28; 44 = A/B partner)
  *   "mlp_bwd_impl"      1 = contiguous-tiles fused backward (bias gradient inside the dW0 MFMAs; default), 0 = generic kernel

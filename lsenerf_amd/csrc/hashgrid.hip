@@ -112,48 +112,20 @@ __device__ __forceinline__ void pos_fract(float x, float scale, float &w, uint32
 }
 
 constexpr int kFwdThreads = 256;
-#ifndef LSE_FWD_ITEMS
-#define LSE_FWD_ITEMS 4
-#endif
-constexpr int kFwdItems = LSE_FWD_ITEMS;   // samples per lane -> 32 independent gathers in flight
+constexpr int kFwdItems = 4;   // samples per lane -> 32 independent gathers in flight
 
 __global__ __launch_bounds__(kFwdThreads) void hash_fwd_kernel(GridParams g, const float *__restrict__ x,
                                                                const float2 *__restrict__ table,
                                                                float2 *__restrict__ y, int64_t n_cap, int64_t chunks,
-                                                               int mapping, const int64_t *__restrict__ n_dev, int l_first)
+                                                               const int64_t *__restrict__ n_dev)
 {
     // n_cap: the level stride of y and the sample capacity the grid was sized for; n: the samples that exist (device-side
     // count when one is set: workgroups past it leave at once)
     const int64_t n = lse::clamp_count(n_cap, n_dev);
-    const int L = g.n_levels;
-    int level;
-    int64_t chunk;
+    // level-major, finest level first (short tail on a cheap level): see the file header
     const int bid = blockIdx.x;
-    if ((L & 7) == 0 && mapping == 0) {
-        // XCD-affine AND level-sequential: blockIdx % 8 fixes the level residue class, and because workgroups are
-        // dispatched in order, each XCD finishes all chunks of one level before starting its next one, so its 4 MiB
-        // L2 holds one 4 MB level table at a time.
-        const int64_t slot = bid >> 3;
-        level = (bid & 7) + 8 * (int)(slot / chunks);
-        chunk = slot % chunks;
-    } else if (mapping == 3) {
-        // level-major: all chunks of level 0, then level 1, ...  Workgroups are dispatched in order and dealt round-robin
-        // to the XCDs, so at any time all 8 XCDs work on the same level (or two neighbouring ones) and every L2 holds
-        // just that 4 MB table -- without binding whole levels to single XCDs, whose costs differ 3x between levels.
-        level = (int)(bid / chunks);
-        chunk = bid % chunks;
-    } else if (mapping == 4) {   // level-major, finest level first (short tail on a cheap level); levels < l_first are not part of
-        level = L - 1 - (int)(bid / chunks);       // this launch (grid sized for L - l_first levels: hash_fwd_lds_kernel serves them)
-        chunk = bid % chunks;
-    } else if ((L & 7) == 0 && mapping == 1) {   // XCD-affine, levels interleaved (A/B reference)
-        const int per = L >> 3;
-        const int slot = bid >> 3;
-        level = (bid & 7) + 8 * (slot % per);
-        chunk = slot / per;
-    } else {
-        level = bid % L;
-        chunk = bid / L;
-    }
+    const int level = g.n_levels - 1 - (int)(bid / chunks);
+    const int64_t chunk = bid % chunks;
     const LevelInfo li = level_info(g, level);
     const float2 *__restrict__ tab = table + li.offset;
     const int64_t base = chunk * (int64_t)(kFwdThreads * kFwdItems) + threadIdx.x;
@@ -195,83 +167,27 @@ __global__ __launch_bounds__(kFwdThreads) void hash_fwd_kernel(GridParams g, con
     }
 }
 
-// LDS-resident variant for the coarsest levels (BASELINE.json north_star: "coalesced HBM gathers with LDS-staged trilinear
-// interpolation"; option hash_fwd_lds_levels, A/B partner of the L2-resident schedule above).  A workgroup stages the WHOLE table of
-// one dense level in LDS with coalesced 8-byte loads (level 0: 16^3 = 32 KB, level 1: 23^3 = 95 KB; level 2 = 233 KB does not fit
-// the 160 KB of a CU), then walks a contiguous share of the samples: positions in, 8 ds_read_b64 gathers per sample, the same
-// multiply-adds in the same order as hash_fwd_kernel (bit-identical results), y out.  Consecutive samples of a ray fall into the same
-// coarse cell, so most gathers of a wave-instruction are LDS broadcasts.
-#ifdef LSE_DEV_KNOBS   // development build only (csrc/dev_knobs.h): superseded / A-B variant, not in liblse_hip.so
-constexpr int kFwdLdsThreads = 1024;
-__global__ __launch_bounds__(kFwdLdsThreads) void hash_fwd_lds_kernel(GridParams g, int level, const float *__restrict__ x,
-                                                                      const float2 *__restrict__ table, float2 *__restrict__ y,
-                                                                      int64_t n_cap, const int64_t *__restrict__ n_dev)
-{
-    extern __shared__ float2 s_tab[];
-    const int64_t n = lse::clamp_count(n_cap, n_dev);
-    const LevelInfo li = level_info(g, level);
-    const float2 *__restrict__ tab = table + li.offset;
-    for (uint32_t e = threadIdx.x; e < li.size; e += kFwdLdsThreads) s_tab[e] = tab[e];
-    __syncthreads();
-    // contiguous share of this workgroup, in steps of one sample per thread (adjacent lanes = adjacent samples of a ray)
-    const int64_t per = ((n + gridDim.x - 1) / gridDim.x + kFwdLdsThreads - 1) / kFwdLdsThreads * kFwdLdsThreads;
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = min(n, lo + per);
-    float2 *__restrict__ yl = y + (int64_t)level * n_cap;
-    for (int64_t i0 = lo; i0 < hi; i0 += 2 * kFwdLdsThreads) {
-        float w[2][3];
-        uint32_t p[2][3];
-        bool valid[2];
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int64_t i = i0 + it * kFwdLdsThreads + threadIdx.x;
-            valid[it] = i < hi;
-            const int64_t ii = valid[it] ? i : (hi - 1);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) pos_fract(x[ii * 3 + d], li.scale, w[it][d], p[it][d]);
-        }
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            uint32_t idx[8];
-            corner_indices(li, p[it][0], p[it][1], p[it][2], idx);
-            float2 v[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) v[c] = s_tab[idx[c]];
-            float2 r = make_float2(0.f, 0.f);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                float wt = 1.f;
-                wt *= (c & 1) ? w[it][0] : 1.f - w[it][0];
-                wt *= (c & 2) ? w[it][1] : 1.f - w[it][1];
-                wt *= (c & 4) ? w[it][2] : 1.f - w[it][2];
-                r.x = fmaf(wt, v[c].x, r.x);
-                r.y = fmaf(wt, v[c].y, r.y);
-            }
-            if (valid[it]) yl[i0 + it * kFwdLdsThreads + threadIdx.x] = r;
-        }
-    }
-}
-#endif  // LSE_DEV_KNOBS
-
-// Backward.  Lane mapping: 16 lanes per sample -- lane k of a 16-lane group owns (corner k>>1, feature k&1) -- and a
-// wave owns 64 consecutive samples of the packed (ray-sorted) stream, processed in 16 rounds of 4 samples.
+// Backward, generic kernel (opts.impl 0, and every grid whose levels do not start on 64-byte lines).  Lane mapping: 16 lanes per
+// sample -- lane k of a 16-lane group owns (corner k>>1, feature k&1) -- and a wave owns 4 * kRounds = 128 consecutive samples of
+// the packed (ray-sorted) stream, processed in kRounds rounds of 4 samples.
 //   * one atomic wave-instruction covers 4 samples x 8 corners x 2 features: the two features of an entry and the
 //     x / x+1 corner pair are neighbouring dwords, so the instruction touches far fewer 64-byte lines than lanes
 //     (memory-side float atomics are priced per line request, MI355X_MICROARCH.md "Global float atomics"; measured
 //     here: identical rate for agent / workgroup / wavefront scope, tools/micro/atomic_scope.hip);
 //   * every lane run-length accumulates (index, sum) in registers and only issues an atomic when its entry index
 //     changes between consecutive rounds;
-//   * which 4 samples share a round is chosen PER LEVEL (tools/sim_hash_bwd_requests.py models the request counts):
-//       blocked      group g walks samples 16g + r  -> long runs: best where consecutive samples share a cell (coarse/mid);
-//       interleaved  group g takes sample 4r + g     -> the instruction covers 4 CONSECUTIVE samples whose cells share
-//                    faces, i.e. lines: best at the fine levels (~25 % fewer line requests there);
-//   * positions are staged once per wave in LDS (either mapping reads them by sample id); d(x) is reduced over the 16
-//     lanes of a group and accumulated per sample in LDS by the group's first lane (plain read-add-write: within a
-//     round the 4 groups own 4 different samples, rounds are sequential).
-template <bool WITH_DX, int kRounds>
+//   * group g of a wave walks the samples kRounds * g + r: long runs wherever consecutive samples share a cell.  (Giving a round
+//     4 CONSECUTIVE samples instead models ~25 % fewer line requests at the fine levels, tools/sim_hash_bwd_requests.py, and was
+//     20 - 80 % slower in hardware: lanes of one instruction then hit the same addresses.  Retired, DESIGN_HISTORY.md.)
+//   * positions are staged once per wave in LDS; d(x) is reduced over the 16 lanes of a group and accumulated per sample
+//     in LDS by the group's first lane (plain read-add-write: within a round the 4 groups own 4 different samples, rounds
+//     are sequential).
+constexpr int kRounds = 32;      // rounds of 4 samples per wave of hash_bwd_kernel
+template <bool WITH_DX>
 __global__ __launch_bounds__(256) void hash_bwd_kernel(GridParams g, const float *__restrict__ x,
                                                        const float *__restrict__ dy,
                                                        const float *__restrict__ table, float *__restrict__ dtable,
-                                                       float *__restrict__ dx, int64_t n, float interleave_from_scale, int dbg)
+                                                       float *__restrict__ dx, int64_t n)
 {
     constexpr int kChunk = 4 * kRounds;        // samples per wave
     // SoA + one pad word per 16-lane group: the 4 groups of a wave touch slots kRounds apart, which would otherwise fall
@@ -299,7 +215,6 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(GridParams g, const float
 
     for (int l = g.l_begin; l < g.l_end; ++l) {
         const LevelInfo li = level_info(g, l);
-        const bool interleaved = li.scale >= interleave_from_scale;
         float *__restrict__ dt = dtable + 2 * (size_t)li.offset + f;
         const float *__restrict__ tab = WITH_DX ? table + 2 * (size_t)li.offset + f : nullptr;
         const float *__restrict__ dyl = dy + 2 * (size_t)l * n + f;
@@ -307,7 +222,7 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(GridParams g, const float
         float acc = 0.f;
 #pragma unroll 4
         for (int r = 0; r < kRounds; ++r) {
-            const int sl = interleaved ? (4 * r + grp) : (kRounds * grp + r);   // sample slot within the wave's 64
+            const int sl = kRounds * grp + r;   // sample slot within the wave's chunk
             const bool valid = wave_base + sl < n;
             float w0, w1, w2;
             uint32_t p0, p1, p2;
@@ -323,7 +238,7 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(GridParams g, const float
             if (idx == cur) {
                 acc += v;
             } else {
-                if (cur != kNone && !(dbg & 1)) atomicAdd(dt + 2 * (size_t)cur, acc);
+                if (cur != kNone) atomicAdd(dt + 2 * (size_t)cur, acc);
                 cur = idx;
                 acc = v;
             }
@@ -346,7 +261,7 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(GridParams g, const float
                 }
             }
         }
-        if (cur != kNone && !(dbg & 1)) atomicAdd(dt + 2 * (size_t)cur, acc);
+        if (cur != kNone) atomicAdd(dt + 2 * (size_t)cur, acc);
     }
     if (WITH_DX) {
         __builtin_amdgcn_wave_barrier();
@@ -365,7 +280,7 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(GridParams g, const float
 #undef LSE_SLOT
 }
 
-// Backward, line-cache variant (the default; LSE_HASH_BWD_IMPL=0 selects the kernel above, kept as the A/B reference).
+// Backward with a per-wave LDS cache of table sectors (the default, hash_bwd_batched_kernel below; opts.impl 0 selects the kernel above).
 // The 16-lanes-per-sample kernel recomputes the position maths 16x and sends ~19 line requests per sample to the
 // memory-side atomic units (it is bound by them: 4.4 ms with, 1.2 ms without the atomics).  Here:
 //   * lane = sample (64 consecutive samples of the packed, ray-sorted stream): the position maths, the 8 indices and
@@ -374,11 +289,11 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(GridParams g, const float
 //     early exit once no run is longer than the step, serial carry over the 3 row borders) leaves each run's 8 x 2
 //     corner sums in the run's last lane;
 //   * run ends add into a per-wave LDS cache of table SECTORS (key = entry index >> 2, payload 8 floats = one 32-B
-//     sector of 4 entries x 2 features; 512 slots, one probe): a 32-bit compare-and-swap claims the slot, a 64-bit
+//     sector of 4 entries x 2 features; 512 slots, 1 + second_probe probes): a 32-bit compare-and-swap claims the slot, a 64-bit
 //     compare-and-swap adds both features (ds_add_f32 runs at ~3 cycles per LANE on gfx950, tools/micro/lds_ops.hip);
 //     a corner whose slot belongs to another sector goes straight to memory, so the cache is purely an optimisation;
-//   * after each level the occupied slots (kept in a list) are flushed with one 8-lane x 32-B atomic per sector.
-//   * a wave that ends at most `few_runs` (6) runs at a level -- the coarse levels -- skips the cache: the run ends park
+//   * after each cache pass the occupied slots (kept in a list) are flushed with one 8-lane x 32-B atomic per sector;
+//   * a wave that ends at most `few_runs` (8) runs at a level -- the coarse levels -- skips the cache: the run ends park
 //     their 8 indices + 16 sums in LDS and the wave adds them to memory with 16 lanes per run (lane = corner x feature),
 //     because the ~500 instructions of the cache path would be spent on idle lanes (levels 0-3: 0.66 -> 0.37 ms).
 //   The memory-side atomic units are priced per 32-B sector request at ~20 G/s (rocprof WRITE_SIZE / 32 B tracks the
@@ -481,343 +396,51 @@ __device__ __forceinline__ void seg_scan_cross_rows(float (&v)[16], int open, in
     for (int k = 0; k < 16; ++k) LSE_FMAC_DPP(v[k], fb, "row_bcast:31 row_mask:0xc bank_mask:0xf");
 }
 
-#ifdef LSE_DEV_KNOBS   // development build only (csrc/dev_knobs.h): superseded / A-B variant, not in liblse_hip.so
-template <bool WITH_DX, int kSlots, int kEntLog2>
-__global__ __launch_bounds__(256) void hash_bwd_cached_kernel(GridParams g, const float *__restrict__ x,
-                                                              const float2 *__restrict__ dy,
-                                                              const float2 *__restrict__ table,
-                                                              float *__restrict__ dtable, float *__restrict__ dx,
-                                                              int64_t n, int dbg, int few_runs, int second_probe)
-{
-    constexpr int kRounds = 1;                 // one 64-sample round per wave
-    constexpr int kEnt = 1 << kEntLog2;        // table entries per cache slot (8 = 64-B line, 4 = 32-B sector)
-    constexpr int kPay = 2 * kEnt;             // payload floats per slot = lanes per slot in the flush
-    constexpr int kSlotBits = 31 - __builtin_clz((unsigned)kSlots);
-    constexpr int kChunk = 64 * kRounds;
-    __shared__ uint32_t s_key[4][kSlots];
-    __shared__ float s_val[4][kSlots * kPay];
-    __shared__ uint16_t s_list[4][kSlots];      // occupied slots
-    __shared__ uint32_t s_dummy32[4][64];
-    __shared__ uint64_t s_dummy64[4][64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t wave_base = ((int64_t)blockIdx.x * 4 + wave) * kChunk;
-    if (wave_base >= n) return;
-    lds_u32 *key = (lds_u32 *)&s_key[wave][0];
-    lds_f32 *val = (lds_f32 *)&s_val[wave][0];
-    lds_u16 *list = (lds_u16 *)&s_list[wave][0];
-    lds_u32 *dummy32 = (lds_u32 *)&s_dummy32[wave][lane];
-    lds_u64 *dummy64 = (lds_u64 *)&s_dummy64[wave][lane];
-    *dummy32 = kNoLine;
-    *dummy64 = 0;
-    for (int s = lane; s < kSlots; s += 64) key[s] = kNoLine;
-    for (int s = lane; s < kSlots * kPay; s += 64) val[s] = 0.f;
-
-    float px[kRounds][3], dacc[kRounds][3];
-    int64_t si[kRounds];
-    bool valid[kRounds];
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = wave_base + r * 64 + lane;
-        valid[r] = i < n;
-        si[r] = valid[r] ? i : n - 1;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            px[r][d] = x[si[r] * 3 + d];
-            dacc[r][d] = 0.f;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();   // the cache is private to this wave; DS ops of a wave execute in order
-
-    for (int l = g.l_begin; l < g.l_end; ++l) {
-        const LevelInfo li = level_info(g, l);
-        float *__restrict__ dt = dtable + 2 * (size_t)li.offset;
-        const float2 *__restrict__ tab = table + li.offset;
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r) {
-            float w0, w1, w2;
-            uint32_t p0, p1, p2;
-            pos_fract(px[r][0], li.scale, w0, p0);
-            pos_fract(px[r][1], li.scale, w1, p1);
-            pos_fract(px[r][2], li.scale, w2, p2);
-            float2 gy = dy[(int64_t)l * n + si[r]];
-            if (!valid[r]) gy = make_float2(0.f, 0.f);
-            uint32_t idx[8];
-            corner_indices(li, p0, p1, p2, idx);
-            float2 tv[8];
-            if (WITH_DX) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) tv[c] = tab[idx[c]];
-            }
-            // runs of lanes in the same cell
-            const uint32_t q0 = __shfl_up(p0, 1), q1 = __shfl_up(p1, 1), q2 = __shfl_up(p2, 1);
-            const int head = (lane == 0) || (q0 != p0) || (q1 != p1) || (q2 != p2);
-            const int next_head = __shfl_down(head, 1);
-            const bool run_end = (lane == 63) || next_head;
-            float v[16];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float wt = ((c & 1) ? w0 : 1.f - w0) * ((c & 2) ? w1 : 1.f - w1) * ((c & 4) ? w2 : 1.f - w2);
-                v[2 * c] = wt * gy.x;
-                v[2 * c + 1] = wt * gy.y;
-            }
-            if (!(dbg & 4)) {
-                // segmented inclusive scan: inside the 16-lane rows with DPP, then a serial carry across the 3 row borders
-                const int row_pos = lane & 15;
-                int flag = head | (row_pos == 0);   // "my partial sum already starts at my run's head (or my row's start)"
-                if (seg_scan_row_step<1>(v, flag, row_pos) && seg_scan_row_step<2>(v, flag, row_pos) &&
-                    seg_scan_row_step<4>(v, flag, row_pos))
-                    seg_scan_row_step<8>(v, flag, row_pos);
-                // `open` = no run head between my row's first lane and me (inclusive): my run continues from the row before
-                int open = !head;
-#pragma unroll
-                for (int off = 1; off < 16; off <<= 1) {
-                    const int o = (off == 1) ? row_shr_i32<1>(open) : (off == 2) ? row_shr_i32<2>(open)
-                                : (off == 4) ? row_shr_i32<4>(open) : row_shr_i32<8>(open);
-                    open &= (row_pos >= off) ? o : 1;
-                }
-                seg_scan_cross_rows(v, open, lane);
-            }
-            if (WITH_DX) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const float sx = (c & 1) ? w0 : 1.f - w0, sy = (c & 2) ? w1 : 1.f - w1, sz = (c & 4) ? w2 : 1.f - w2;
-                    const float t = li.scale * (gy.x * tv[c].x + gy.y * tv[c].y);
-                    dacc[r][0] += t * ((c & 1) ? 1.f : -1.f) * (sy * sz);
-                    dacc[r][1] += t * ((c & 2) ? 1.f : -1.f) * (sx * sz);
-                    dacc[r][2] += t * ((c & 4) ? 1.f : -1.f) * (sx * sy);
-                }
-            }
-            // ---- run ends add their 8 corner sums into the line cache, then the level's lines are flushed.
-            // The kernel is instruction-issue bound (rocprof: VALU+SALU+LDS issue ~ 3 ms of a 3.6 ms launch), so this part
-            // is written for few instructions: one probe per corner, no retry rounds (a lost slot goes straight to memory),
-            // every DS operation issued by all lanes (idle lanes aim at a private dummy word) so that a batch of 8 goes out
-            // back to back with one wait.
-            const uint64_t ends_mask = __builtin_amdgcn_ballot_w64(run_end && !(dbg & 2));
-            const int n_ends = __builtin_popcountll(ends_mask);
-            if (n_ends <= few_runs) {
-                // Coarse levels: a wave ends only a handful of runs, and almost all of the ~500 instructions of the cache
-                // path below would be spent on idle lanes.  Instead the run ends park their 8 indices + 16 sums in LDS
-                // (the zeroed payload area doubles as staging) and the wave re-reads them with 16 lanes per run -- lane =
-                // (corner, feature), 4 runs per instruction -- and adds straight to memory: the two features and the
-                // x / x+1 neighbours of an entry share requests inside the instruction.
-                if (n_ends > 0) {
-                    lds_u32 *stage = (lds_u32 *)val;           // [run][8 idx | 16 values]
-                    if (run_end && !(dbg & 2)) {
-                        const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ends_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends_mask, 0));
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) stage[rank * 24 + c] = idx[c];
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) stage[rank * 24 + 8 + k] = __float_as_uint(v[k]);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    const int k16 = lane & 15;
-                    for (int r0 = lane >> 4; r0 < n_ends; r0 += 4) {
-                        const uint32_t e = stage[r0 * 24 + (k16 >> 1)];
-                        const float a = __uint_as_float(stage[r0 * 24 + 8 + k16]);
-                        if (a != 0.f) atomicAdd(dt + 2 * (size_t)e + (k16 & 1), a);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    for (int s_ = lane; s_ < n_ends * 24; s_ += 64) stage[s_] = 0u;   // the payload area must read zero again
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                }
-            } else {
-                const bool act = run_end && !(dbg & 2);
-                uint32_t used = 0;   // occupied cache slots (wave-uniform)
-                if (__builtin_amdgcn_ballot_w64(act) != 0) {
-                    // multiplicative hash of the line id (a slot function linear in the cell coordinates was tried: more
-                    // collisions on ray-shaped line sets, tools/sim_hash_bwd_requests.py)
-                    uint32_t slot[8], old[8];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) slot[c] = (__umul24(idx[c] >> kEntLog2, 0x9E3779u) >> (24 - kSlotBits)) & (kSlots - 1);
-#pragma unroll
-                    for (int c = 0; c < 8; ++c)
-                        old[c] = lds_cas(act ? &key[slot[c]] : dummy32, kNoLine, act ? (idx[c] >> kEntLog2) : kNoLine);
-                    // float LDS atomics run at ~3 cycles per LANE on gfx950 (tools/micro/lds_ops.hip: ds_add_f32 194 cycles
-                    // per instruction, ds_cmpst_b64 22): add both features with one 64-bit compare-and-swap
-                    lds_u64 *va[8];
-                    bool to_mem[8], okc[8];
-                    uint64_t cur[8], prev[8];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        const bool claim = act && old[c] == kNoLine;
-                        const uint64_t cm = __builtin_amdgcn_ballot_w64(claim);
-                        if (cm) {
-                            if (claim)
-                                list[used + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0))] =
-                                    (uint16_t)slot[c];
-                            used += __builtin_popcountll(cm);
-                        }
-                        okc[c] = claim || (act && old[c] == (idx[c] >> kEntLog2));
-                        to_mem[c] = act && !okc[c];
-                    }
-                    if (second_probe) {
-                        // second chance in the neighbouring slot for the corners that lost their first one (batched the same way)
-                        bool any = false;
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) any = any || to_mem[c];
-                        if (__builtin_amdgcn_ballot_w64(any) != 0) {
-                            uint32_t old2[8];
-#pragma unroll
-                            for (int c = 0; c < 8; ++c)
-                                old2[c] = lds_cas(to_mem[c] ? &key[(slot[c] + 1) & (kSlots - 1)] : dummy32, kNoLine,
-                                                  to_mem[c] ? (idx[c] >> kEntLog2) : kNoLine);
-#pragma unroll
-                            for (int c = 0; c < 8; ++c) {
-                                const bool claim = to_mem[c] && old2[c] == kNoLine;
-                                const uint64_t cm = __builtin_amdgcn_ballot_w64(claim);
-                                if (cm) {
-                                    if (claim)
-                                        list[used + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0))] =
-                                            (uint16_t)((slot[c] + 1) & (kSlots - 1));
-                                    used += __builtin_popcountll(cm);
-                                }
-                                if (claim || (to_mem[c] && old2[c] == (idx[c] >> kEntLog2))) {
-                                    slot[c] = (slot[c] + 1) & (kSlots - 1);
-                                    okc[c] = true;
-                                    to_mem[c] = false;
-                                }
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int c = 0; c < 8; ++c)
-                        va[c] = okc[c] ? (lds_u64 *)&val[slot[c] * kPay + (idx[c] & (kEnt - 1)) * 2] : dummy64;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) cur[c] = *va[c];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) prev[c] = lds_cas(va[c], cur[c], add_pair(cur[c], v[2 * c], v[2 * c + 1]));
-                    bool retry = false;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) retry = retry || prev[c] != cur[c];
-                    if (__builtin_amdgcn_ballot_w64(retry) != 0) {   // rare: two lanes (or two corners of a lane) on one entry
-#pragma unroll
-                        for (int c = 0; c < 8; ++c)
-                            while (prev[c] != cur[c]) {
-                                cur[c] = prev[c];
-                                prev[c] = lds_cas(va[c], cur[c], add_pair(cur[c], v[2 * c], v[2 * c + 1]));
-                            }
-                    }
-                    // Corners whose slot is owned by another sector go straight to memory.  The two features of an entry are
-                    // written by a PAIR of lanes in one instruction (lane and lane^1 swap operands through DPP), so the
-                    // 8 bytes cost one request to the atomic units instead of two.
-                    const bool is_odd = lane & 1;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        if (__builtin_amdgcn_ballot_w64(to_mem[c]) == 0) continue;
-                        const uint32_t idx_n = (uint32_t)quad_swap1((int)idx[c]);
-                        const float v0_n = __int_as_float(quad_swap1(__float_as_int(v[2 * c])));
-                        const float v1_n = __int_as_float(quad_swap1(__float_as_int(v[2 * c + 1])));
-                        const bool tm_n = quad_swap1((int)to_mem[c]) != 0;
-                        // first instruction serves the even lanes' corners, second one the odd lanes'
-                        if (is_odd ? tm_n : to_mem[c]) atomicAdd(dt + 2 * (size_t)(is_odd ? idx_n : idx[c]) + is_odd, is_odd ? v1_n : v[2 * c]);
-                        if (is_odd ? to_mem[c] : tm_n) atomicAdd(dt + 2 * (size_t)(is_odd ? idx[c] : idx_n) + is_odd, is_odd ? v[2 * c + 1] : v0_n);
-                    }
-                }
-                // flush: 16 lanes per line, 4 lines per instruction, 16 lines per trip (loads first)
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                constexpr int kPer = 64 / kPay;   // slots per flush instruction
-                const int sub = lane & (kPay - 1);
-                for (uint32_t e0 = lane / kPay; e0 < used; e0 += 4 * kPer) {
-                    uint32_t ent[4], ln[4];
-                    float vv[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) ent[u] = (e0 + kPer * u < used) ? (uint32_t)list[e0 + kPer * u] : 0xFFFFFFFFu;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        ln[u] = (ent[u] != 0xFFFFFFFFu) ? key[ent[u]] : 0u;
-                        vv[u] = (ent[u] != 0xFFFFFFFFu) ? val[ent[u] * kPay + sub] : 0.f;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (vv[u] != 0.f && !(dbg & 1)) atomicAdd(dt + (size_t)ln[u] * kPay + sub, vv[u]);
-                    __builtin_amdgcn_wave_barrier();   // every lane of a slot has read the key before lane 0 resets it
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (ent[u] != 0xFFFFFFFFu) {
-                            val[ent[u] * kPay + sub] = 0.f;
-                            if (sub == 0) key[ent[u]] = kNoLine;
-                        }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-    }
-    if (WITH_DX) {
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r)
-            if (valid[r]) {
-                if (g.dx_accumulate) {
-                    dacc[r][0] += dx[si[r] * 3 + 0];
-                    dacc[r][1] += dx[si[r] * 3 + 1];
-                    dacc[r][2] += dx[si[r] * 3 + 2];
-                }
-                dx[si[r] * 3 + 0] = dacc[r][0];
-                dx[si[r] * 3 + 1] = dacc[r][1];
-                dx[si[r] * 3 + 2] = dacc[r][2];
-            }
-    }
-}
-#endif  // LSE_DEV_KNOBS
-
-// kPair: the memory-side units charge a float-atomic REQUEST per 64-byte LINE, whatever part of it the request covers
+// The batched sector-cache kernel (the default, opts.impl 2): the design above, with the run ends of SEVERAL levels sharing one cache pass.
+// Paired sectors: the memory-side units charge a float-atomic REQUEST per 64-byte LINE, whatever part of it the request covers
 // (tools/micro/atomic_gran.hip: 21 G requests/s for 4 ... 64 contiguous bytes, half of that for 128).  With 32-byte slots a line
-// whose two sectors were both touched is flushed as two requests.  kPair hashes the LINE to a pair of neighbouring slots (even /
-// odd sector) and builds the flush list by scanning the keys in slot order, so sibling sectors sit in neighbouring 8-lane groups
-// of one flush instruction and go out as ONE contiguous 64-byte request; the scan also replaces the per-corner list appends of
-// the insert path (fewer instructions per pass).
-// kFlush2 (round 3): the kernel is bound by the CU's LDS pipe -- every DS wave-instruction costs 7 .. 8 cycles of it
-// (13 / 22 for the 32- / 64-bit compare-and-swap; profiles/r02_micro_lds_ops.txt), a cache pass issued ~190 of them, 140 of
-// those in the flush (per 32 slots: 4 list reads, 4 key reads, 4 payload reads, 4 payload resets, 4 key resets), and
-// 256 waves x ~9 passes x 1500 cycles per CU is the 1.5 ms the ablation attributes to the cache passes.  Flush with fewer DS
-// instructions: the list is stored trip-major transposed, so the 4 slots a lane group handles in a trip are one 8-byte read;
-// the payload is read AND zeroed by one ds_wrxchg_rtn_b32; the keys are reset in bulk after the last trip (2 x ds_write_b128
-// per lane).  Per 32 slots: 1 + 4 + 4 = 9 instead of 20 DS instructions, per pass ~75 instead of ~140 in the flush.
-// kPrefetch (round 3): vmcnt retires in order, and a no-return atomic stays counted for ~3000 cycles when every CU is issuing them
-// (MI355X_MICROARCH.md).  A level's dy load and table gathers, issued at the top of the level right behind the previous level's
-// flush atomics, can therefore not be consumed before those atomics have retired: every level begins with that wait.  With
-// kPrefetch the loads of level l+1 are issued right after the scan of level l -- BEFORE level l's cache pass -- and are waited for
-// just before the pass sends its first atomic (an empty asm that consumes the registers places the s_waitcnt there): by then they
-// have had the whole insert phase to arrive, and the atomics get the whole next level to retire.
-// kAlign (round 3): the two sectors of a line leave as ONE request only when their list entries sit in neighbouring lane groups of the
-// SAME flush instruction; in slot order a sibling pair straddles an 8-entry boundary one time in eight.  With kAlign every occupied
-// pair bucket takes an even-aligned pair of list positions (an absent sibling is an idle entry), so a line is never split.
-// kWaves: waves per workgroup.  Nothing below synchronises across waves (every wave owns its cache), so the workgroup size only sets
-// the granularity at which LDS is handed out: 4 x 512 slots = 80 KB -> 8 waves per CU; 2 x 384 slots = 30.5 KB -> 10 waves per CU.
-template <bool WITH_DX, int kSlots, int kEntLog2, bool kPair = false, bool kFlush2 = false, bool kPrefetch = false, bool kAlign = false,
-          int kWaves = 4>
-__global__ __launch_bounds__(64 * kWaves) void hash_bwd_batched_kernel(GridParams g, const float *__restrict__ x,
+// whose two sectors were both touched would be flushed as two requests, so the LINE is hashed to a pair of neighbouring slots (even /
+// odd sector) and the flush list is built by scanning the keys in slot order: sibling sectors sit in neighbouring 8-lane groups of
+// one flush instruction and go out as ONE contiguous 64-byte request; the scan also replaces per-corner list appends in the insert path.
+// Second-generation flush: the kernel is bound by the CU's LDS pipe -- every DS wave-instruction costs 7 .. 8 cycles of it (13 / 22
+// for the 32- / 64-bit compare-and-swap; profiles/r02_micro_lds_ops.txt) -- so the flush is written for few DS instructions: the list
+// is stored trip-major transposed, so the 4 slots a lane group handles in a trip are one 8-byte read; the payload is read AND zeroed
+// by one ds_wrxchg_rtn_b32; the keys are reset in bulk after the last trip (2 x ds_write_b128 per lane).  Per 32 slots: 1 + 4 + 4 = 9
+// DS instructions (a list read, key read, payload read, payload reset and key reset per slot took 20).
+// One wave per workgroup: nothing below synchronises across waves (every wave owns its cache), so the workgroup size only sets the
+// granularity at which LDS is handed out and released.  A workgroup's LDS is released when its last wave retires, and waves differ in
+// how many cache passes their samples need: in workgroups of four a CU held 20 KB per early finisher idle (samples in the contracted
+// shell 2.53 -> 2.40 ms, headline, M-packed and the default configuration within +-1 %: profiles/r05_hash_bwd_workgroup_size.txt).
+// Retired variants of this kernel (DESIGN_HISTORY.md; last present in commit eb3e47d):
+//   * one cache pass per level, with 256 slots of a 64-byte line or 512 unpaired sectors: 3.54 / 3.23 ms, 2.91 with the few-runs
+//     path, where batching the levels reached 2.7 (the comment above; no profile file was kept);
+//   * paired slots with the first-generation flush: 2.75 against 2.71 ms (profiles/r04_hash_bwd_defaults_recheck.txt, gran 4);
+//   * the next level's operands fetched ahead of the cache pass: +-0 (profiles/r03_hash_bwd_prefetch.txt, r05_hash_bwd_prefetch_retest.txt);
+//   * pair-aligned flush lists: identical request counts, 2 - 3 % slower (profiles/r03_hash_bwd_aligned_pairs.txt);
+//   * 256 / 320 / 384 / 448 slots and workgroups of 2 / 4 waves: flat or slower (profiles/r05_hash_bwd_slots320.txt,
+//     r05_hash_bwd_workgroup_size.txt);
+//   * a cache-free high-occupancy kernel for the coarse levels: +-2 % (profiles/r03_hash_bwd_coarse_kernel_attribution.txt).
+template <bool WITH_DX>
+__global__ __launch_bounds__(64) void hash_bwd_batched_kernel(GridParams g, const float *__restrict__ x,
                                                               const float2 *__restrict__ dy,
                                                               const float2 *__restrict__ table,
                                                               float *__restrict__ dtable, float *__restrict__ dx,
-                                                              int64_t n_cap, int dbg, int few_runs, int second_probe, int stage_max,
+                                                              int64_t n_cap, int few_runs, int second_probe, int stage_max,
                                                               float *__restrict__ ws, const int64_t *__restrict__ n_dev)
 {
     const int64_t n = lse::clamp_count(n_cap, n_dev);      // n_cap stays the level stride of dy
-    constexpr int kRounds = 1;                 // one 64-sample round per wave
-    constexpr int kEnt = 1 << kEntLog2;        // table entries per cache slot (8 = 64-B line, 4 = 32-B sector)
+    constexpr int kSlots = 512;                // cache slots per wave
+    constexpr int kEntLog2 = 2;
+    constexpr int kEnt = 1 << kEntLog2;        // table entries per cache slot (4 = one 32-B sector)
     constexpr int kPay = 2 * kEnt;             // payload floats per slot = lanes per slot in the flush
     constexpr int kSlotBits = 31 - __builtin_clz((unsigned)kSlots);
-    constexpr bool kPow2 = (kSlots & (kSlots - 1)) == 0;     // 320 slots (three workgroups per CU): multiply-high instead of masks
-    static_assert(kPow2 || (kPair && kFlush2 && kSlots % 64 == 0), "non-power-of-two caches: paired slots, second-generation flush");
-    constexpr int kChunk = 64 * kRounds;
-    constexpr int kStep = kPair ? 2 : 1;        // second probe: the next slot of the same parity
-    auto wrap = [](uint32_t sl) -> uint32_t {   // sl < 2 * kSlots
-        if constexpr (kPow2) return sl & (uint32_t)(kSlots - 1);
-        else return sl >= (uint32_t)kSlots ? sl - (uint32_t)kSlots : sl;
-    };
+    constexpr int kWaves = 1;                  // waves per workgroup (the launch bound above)
+    constexpr int kChunk = 64;                 // samples per wave: lane = sample
+    static_assert(kPay == 8 && kSlots == 512, "flush: 8 lanes per slot, bulk key reset of 8 keys per lane");
     __shared__ uint32_t s_key[kWaves][kSlots];
     __shared__ float s_val[kWaves][kSlots * kPay];
     __shared__ uint16_t s_list[kWaves][kSlots];      // occupied slots
-    // LDS is handed out in 1280-byte portions: 448 slots fit nine times into a CU only when the idle lanes' 32-bit dummy word is the
-    // low half of their 64-bit one (either holds don't-care values between uses: every use overwrites or ignores it)
-    constexpr bool kTightLds = kSlots == 448;
-    __shared__ uint32_t s_dummy32[kTightLds ? 1 : kWaves][64];
+    __shared__ uint32_t s_dummy32[kWaves][64];
     __shared__ uint64_t s_dummy64[kWaves][64];
     __shared__ uint32_t s_perm[kWaves][64];          // rank -> lane of the run ends being staged
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -827,21 +450,18 @@ __global__ __launch_bounds__(64 * kWaves) void hash_bwd_batched_kernel(GridParam
     // x + 8 of EVERY ray, a static load imbalance between XCDs.  Workgroup b therefore takes position (b % 8) * ceil(B / 8) + b / 8
     // of the B positions the samples actually fill (device-side count: a captured step's capacity is larger): every XCD walks one
     // contiguous eighth, i.e. whole rays whatever their length.  Inside-box rays 2.39 -> 2.19 ms, the reference's default
-    // configuration 1.51 -> 1.47, headline +-0.3 % (profiles/r05_hash_bwd_xcd_mapping.txt).  (dbg & 32, development build: the
-    // identity mapping, for A/B.)
+    // configuration 1.51 -> 1.47, headline +-0.3 % (profiles/r05_hash_bwd_xcd_mapping.txt).
     int64_t wg = blockIdx.x;
-    if (!(dbg & 32)) {
-        const int64_t positions = (n + (int64_t)kChunk * kWaves - 1) / ((int64_t)kChunk * kWaves);
-        const int64_t per_xcd = (positions + 7) >> 3;
-        if ((wg >> 3) >= per_xcd) return;      // (the grid covers the capacity, rounded up to a multiple of 8)
-        wg = (wg & 7) * per_xcd + (wg >> 3);
-    }
+    const int64_t positions = (n + (int64_t)kChunk * kWaves - 1) / ((int64_t)kChunk * kWaves);
+    const int64_t per_xcd = (positions + 7) >> 3;
+    if ((wg >> 3) >= per_xcd) return;      // (the grid covers the capacity, rounded up to a multiple of 8)
+    wg = (wg & 7) * per_xcd + (wg >> 3);
     const int64_t wave_base = (wg * kWaves + wave) * kChunk;
     if (wave_base >= n) return;
     lds_u32 *key = (lds_u32 *)&s_key[wave][0];
     lds_f32 *val = (lds_f32 *)&s_val[wave][0];
     lds_u16 *list = (lds_u16 *)&s_list[wave][0];
-    lds_u32 *dummy32 = kTightLds ? (lds_u32 *)&s_dummy64[wave][lane] : (lds_u32 *)&s_dummy32[wave][lane];
+    lds_u32 *dummy32 = (lds_u32 *)&s_dummy32[wave][lane];
     lds_u64 *dummy64 = (lds_u64 *)&s_dummy64[wave][lane];
     lds_u32 *perm = (lds_u32 *)&s_perm[wave][0];
     *dummy32 = kNoLine;
@@ -849,19 +469,14 @@ __global__ __launch_bounds__(64 * kWaves) void hash_bwd_batched_kernel(GridParam
     for (int s = lane; s < kSlots; s += 64) key[s] = kNoLine;
     for (int s = lane; s < kSlots * kPay; s += 64) val[s] = 0.f;
 
-    float px[kRounds][3], dacc[kRounds][3];
-    int64_t si[kRounds];
-    bool valid[kRounds];
+    const int64_t i = wave_base + lane;
+    const bool valid = i < n;
+    const int64_t si = valid ? i : n - 1;
+    float px[3], dacc[3];
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = wave_base + r * 64 + lane;
-        valid[r] = i < n;
-        si[r] = valid[r] ? i : n - 1;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            px[r][d] = x[si[r] * 3 + d];
-            dacc[r][d] = 0.f;
-        }
+    for (int d = 0; d < 3; ++d) {
+        px[d] = x[si * 3 + d];
+        dacc[d] = 0.f;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();   // the cache is private to this wave; DS ops of a wave execute in order
@@ -878,251 +493,157 @@ __global__ __launch_bounds__(64 * kWaves) void hash_bwd_batched_kernel(GridParam
     for (int k = 0; k < 16; ++k) q_v[k] = 0.f;
     int fill = 0;
 
-    // (kPrefetch) level l+1's operands, fetched while level l's cache pass runs
-    float nw0 = 0.f, nw1 = 0.f, nw2 = 0.f;
-    uint32_t np0 = 0, np1 = 0, np2 = 0, nidx[8];
-    float2 ngy = make_float2(0.f, 0.f), ntv[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        nidx[c] = 0u;
-        ntv[c] = make_float2(0.f, 0.f);
-    }
-    bool pending_touch = false;     // wave-uniform: loads of the next level are in flight and not yet waited for
-    auto fetch_next = [&](int l) {
-        const LevelInfo nli = level_info(g, l);
-        pos_fract(px[0][0], nli.scale, nw0, np0);
-        pos_fract(px[0][1], nli.scale, nw1, np1);
-        pos_fract(px[0][2], nli.scale, nw2, np2);
-        ngy = dy[(int64_t)l * n_cap + si[0]];
-        corner_indices(nli, np0, np1, np2, nidx);
-        if (WITH_DX) {
-            const float2 *__restrict__ ntab = table + nli.offset;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) ntv[c] = ntab[nidx[c]];
-        }
-        pending_touch = true;
-    };
-    auto touch_next = [&]() {
-        if (!kPrefetch || !pending_touch) return;
-        asm volatile("" ::"v"(ngy.x), "v"(ngy.y));
-        if (WITH_DX) {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) asm volatile("" ::"v"(ntv[c].x), "v"(ntv[c].y));
-        }
-        pending_touch = false;
-    };
-
     auto insert_pass = [&](const bool act, const uint32_t (&gi)[8], const float (&vv)[16]) {
         uint32_t used = 0;   // occupied cache slots (wave-uniform)
-            if (__builtin_amdgcn_ballot_w64(act) != 0) {
-                // multiplicative hash of the line id (a slot function linear in the cell coordinates was tried: more
-                // collisions on ray-shaped line sets, tools/sim_hash_bwd_requests.py)
-                uint32_t slot[8], old[8];
+        if (__builtin_amdgcn_ballot_w64(act) != 0) {
+            // multiplicative hash of the LINE id picks the pair bucket, the sector's parity the slot inside it (a slot function
+            // linear in the cell coordinates was tried: more collisions on ray-shaped line sets, tools/sim_hash_bwd_requests.py)
+            uint32_t slot[8], old[8];
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    if constexpr (kPair && !kPow2)      // pair bucket = floor(hash / 2^24 * (kSlots / 2)): the top bits of the product
-                        slot[c] = (((__umul24(gi[c] >> (kEntLog2 + 1), 0x9E3779u) & 0xFFFFFFu) * (uint32_t)(kSlots / 2)) >> 24 << 1) |
-                                  ((gi[c] >> kEntLog2) & 1u);
-                    else if constexpr (kPair)
-                        slot[c] = (((__umul24(gi[c] >> (kEntLog2 + 1), 0x9E3779u) >> (25 - kSlotBits)) & (kSlots / 2 - 1)) << 1) |
-                                  ((gi[c] >> kEntLog2) & 1u);
-                    else
-                        slot[c] = (__umul24(gi[c] >> kEntLog2, 0x9E3779u) >> (24 - kSlotBits)) & (kSlots - 1);
-                }
-                uint32_t keyc[8];      // the sector a corner belongs to = the cache key
+            for (int c = 0; c < 8; ++c)
+                slot[c] = (((__umul24(gi[c] >> (kEntLog2 + 1), 0x9E3779u) >> (25 - kSlotBits)) & (kSlots / 2 - 1)) << 1) |
+                          ((gi[c] >> kEntLog2) & 1u);
+            uint32_t keyc[8];      // the sector a corner belongs to = the cache key
 #pragma unroll
-                for (int c = 0; c < 8; ++c) keyc[c] = gi[c] >> kEntLog2;
+            for (int c = 0; c < 8; ++c) keyc[c] = gi[c] >> kEntLog2;
 #pragma unroll
-                for (int c = 0; c < 8; ++c)
-                    old[c] = lds_cas(act ? &key[slot[c]] : dummy32, kNoLine, act ? keyc[c] : kNoLine);
-                // float LDS atomics run at ~3 cycles per LANE on gfx950 (tools/micro/lds_ops.hip: ds_add_f32 194 cycles
-                // per instruction, ds_cmpst_b64 22): add both features with one 64-bit compare-and-swap
-                lds_u64 *va[8];
-                // ONE piece of state per corner: to_mem = "active and not (yet) at home in a slot".  (Until round 5 a second array --
-                // okc -- and exec-masked update blocks carried the same information: ~300 instructions per probe round, half of
-                // them scalar mask bookkeeping; selects on one mask per corner need ~90.)
-                bool to_mem[8];
-                uint64_t cur[8], prev[8];
+            for (int c = 0; c < 8; ++c)
+                old[c] = lds_cas(act ? &key[slot[c]] : dummy32, kNoLine, act ? keyc[c] : kNoLine);
+            // float LDS atomics run at ~3 cycles per LANE on gfx950 (tools/micro/lds_ops.hip: ds_add_f32 194 cycles
+            // per instruction, ds_cmpst_b64 22): add both features with one 64-bit compare-and-swap
+            lds_u64 *va[8];
+            // ONE piece of state per corner: to_mem = "active and not (yet) at home in a slot", updated with selects (a second
+            // array and exec-masked update blocks cost ~300 instructions per probe round, half of them scalar mask bookkeeping;
+            // selects on one mask per corner need ~90)
+            bool to_mem[8];
+            uint64_t cur[8], prev[8];
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const bool home = (old[c] == kNoLine) || (old[c] == keyc[c]);      // claimed the slot, or found its own sector there
-                    if constexpr (!kPair) {
-                        const bool claim = act && old[c] == kNoLine;
-                        const uint64_t cm = __builtin_amdgcn_ballot_w64(claim);
-                        if (cm) {
-                            if (claim)
-                                list[used + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0))] =
-                                    (uint16_t)slot[c];
-                            used += __builtin_popcountll(cm);
-                        }
-                    }
-                    to_mem[c] = act && !home;
-                }
-                for (int pr = 0; pr < second_probe; ++pr) {
-                    // another chance in the next slot for the corners that lost the previous one (batched the same way); a loser keeps
-                    // its home slot, so round pr probes home + (pr + 1) * kStep (until round 3 every round after the first probed the
-                    // same neighbour again and could not win anything)
-                    bool any = false;
+            for (int c = 0; c < 8; ++c) {
+                const bool home = (old[c] == kNoLine) || (old[c] == keyc[c]);      // claimed the slot, or found its own sector there
+                to_mem[c] = act && !home;
+            }
+            for (int pr = 0; pr < second_probe; ++pr) {
+                // another chance in the next slot of the same parity for the corners that lost the previous one (batched the same
+                // way); a loser keeps its home slot, so round pr probes home + 2 * (pr + 1)
+                bool any = false;
 #pragma unroll
-                    for (int c = 0; c < 8; ++c) any = any || to_mem[c];
-                    // rounds after the first only when at least 8 lanes still hold a loser: a round costs the whole wave its
-                    // instructions whatever the number of losers, and where the kernel is bound by its own instructions (samples in
-                    // the contracted shell: 2.57 -> 2.71 ms with unconditional rounds, 2.66 with the threshold) a handful of direct adds
-                    // is cheaper; the atomic-bound regimes keep their gain (default configuration 1.51 -> 1.48 ms either way)
-                    const int min_losers = pr == 0 ? 1 : 8;
-                    if (__builtin_popcountll(__builtin_amdgcn_ballot_w64(any)) >= min_losers) {
-                        uint32_t old2[8], nxt[8];
-                        const uint32_t hop = (uint32_t)(pr + 1) * kStep;
+                for (int c = 0; c < 8; ++c) any = any || to_mem[c];
+                // rounds after the first only when at least 8 lanes still hold a loser: a round costs the whole wave its
+                // instructions whatever the number of losers, and where the kernel is bound by its own instructions (samples in
+                // the contracted shell: 2.57 -> 2.71 ms with unconditional rounds, 2.66 with the threshold) a handful of direct adds
+                // is cheaper; the atomic-bound regimes keep their gain (default configuration 1.51 -> 1.48 ms either way)
+                const int min_losers = pr == 0 ? 1 : 8;
+                if (__builtin_popcountll(__builtin_amdgcn_ballot_w64(any)) >= min_losers) {
+                    uint32_t old2[8], nxt[8];
+                    const uint32_t hop = (uint32_t)(pr + 1) * 2;
 #pragma unroll
-                        for (int c = 0; c < 8; ++c) nxt[c] = wrap(slot[c] + hop);
-#pragma unroll
-                        for (int c = 0; c < 8; ++c)
-                            old2[c] = lds_cas(to_mem[c] ? &key[nxt[c]] : dummy32, kNoLine, to_mem[c] ? keyc[c] : kNoLine);
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) {
-                            const bool won = to_mem[c] && ((old2[c] == kNoLine) || (old2[c] == keyc[c]));
-                            if constexpr (!kPair) {
-                                const bool claim = to_mem[c] && old2[c] == kNoLine;
-                                const uint64_t cm = __builtin_amdgcn_ballot_w64(claim);
-                                if (cm) {
-                                    if (claim)
-                                        list[used + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0))] =
-                                            (uint16_t)nxt[c];
-                                    used += __builtin_popcountll(cm);
-                                }
-                            }
-                            slot[c] = won ? nxt[c] : slot[c];
-                            to_mem[c] = to_mem[c] && !won;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    // address for every lane, then ONE select (left to itself the compiler guards each address with its own
-                    // exec-masked block: 29 s_and_saveexec + 17 branches for the eight corners)
-                    uint32_t home_p = (uint32_t)(uintptr_t)(lds_u64 *)&val[slot[c] * kPay + (gi[c] & (kEnt - 1)) * 2];
-                    asm volatile("" : "+v"(home_p));
-                    va[c] = (act && !to_mem[c]) ? (lds_u64 *)(uintptr_t)home_p : dummy64;
-                }
-#pragma unroll
-                for (int c = 0; c < 8; ++c) cur[c] = *va[c];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) prev[c] = lds_cas(va[c], cur[c], add_pair(cur[c], vv[2 * c], vv[2 * c + 1]));
-                bool retry = false;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) retry = retry || prev[c] != cur[c];
-                if (__builtin_amdgcn_ballot_w64(retry) != 0) {   // rare: two lanes (or two corners of a lane) on one entry
+                    for (int c = 0; c < 8; ++c) nxt[c] = (slot[c] + hop) & (uint32_t)(kSlots - 1);
 #pragma unroll
                     for (int c = 0; c < 8; ++c)
-                        while (prev[c] != cur[c]) {
-                            cur[c] = prev[c];
-                            prev[c] = lds_cas(va[c], cur[c], add_pair(cur[c], vv[2 * c], vv[2 * c + 1]));
-                        }
-                }
-                // Corners whose slot is owned by another sector go straight to memory.  The two features of an entry are
-                // written by a PAIR of lanes in one instruction (lane and lane^1 swap operands through DPP), so the
-                // 8 bytes cost one request to the atomic units instead of two.
-                const bool is_odd = lane & 1;
-                touch_next();      // (kPrefetch) the next level's loads are consumed before this pass's first atomic
+                        old2[c] = lds_cas(to_mem[c] ? &key[nxt[c]] : dummy32, kNoLine, to_mem[c] ? keyc[c] : kNoLine);
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    if (__builtin_amdgcn_ballot_w64(to_mem[c]) == 0) continue;
-                    const uint32_t gi_n = (uint32_t)quad_swap1((int)gi[c]);
-                    const float v0_n = __int_as_float(quad_swap1(__float_as_int(vv[2 * c])));
-                    const float v1_n = __int_as_float(quad_swap1(__float_as_int(vv[2 * c + 1])));
-                    const bool tm_n = quad_swap1((int)to_mem[c]) != 0;
-                    // first instruction serves the even lanes' corners, second one the odd lanes'
-                    if (is_odd ? tm_n : to_mem[c]) atomicAdd(dtable + 2 * (size_t)(is_odd ? gi_n : gi[c]) + is_odd, is_odd ? v1_n : vv[2 * c]);
-                    if (is_odd ? to_mem[c] : tm_n) atomicAdd(dtable + 2 * (size_t)(is_odd ? gi[c] : gi_n) + is_odd, is_odd ? vv[2 * c + 1] : v0_n);
+                    for (int c = 0; c < 8; ++c) {
+                        const bool won = to_mem[c] && ((old2[c] == kNoLine) || (old2[c] == keyc[c]));
+                        slot[c] = won ? nxt[c] : slot[c];
+                        to_mem[c] = to_mem[c] && !won;
+                    }
                 }
             }
-            // flush: 16 lanes per line, 4 lines per instruction, 16 lines per trip (loads first)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                // address for every lane, then ONE select (left to itself the compiler guards each address with its own
+                // exec-masked block: 29 s_and_saveexec + 17 branches for the eight corners)
+                uint32_t home_p = (uint32_t)(uintptr_t)(lds_u64 *)&val[slot[c] * kPay + (gi[c] & (kEnt - 1)) * 2];
+                asm volatile("" : "+v"(home_p));
+                va[c] = (act && !to_mem[c]) ? (lds_u64 *)(uintptr_t)home_p : dummy64;
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) cur[c] = *va[c];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) prev[c] = lds_cas(va[c], cur[c], add_pair(cur[c], vv[2 * c], vv[2 * c + 1]));
+            bool retry = false;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) retry = retry || prev[c] != cur[c];
+            if (__builtin_amdgcn_ballot_w64(retry) != 0) {   // rare: two lanes (or two corners of a lane) on one entry
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    while (prev[c] != cur[c]) {
+                        cur[c] = prev[c];
+                        prev[c] = lds_cas(va[c], cur[c], add_pair(cur[c], vv[2 * c], vv[2 * c + 1]));
+                    }
+            }
+            // Corners whose slot is owned by another sector go straight to memory.  The two features of an entry are
+            // written by a PAIR of lanes in one instruction (lane and lane^1 swap operands through DPP), so the
+            // 8 bytes cost one request to the atomic units instead of two.
+            const bool is_odd = lane & 1;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                if (__builtin_amdgcn_ballot_w64(to_mem[c]) == 0) continue;
+                const uint32_t gi_n = (uint32_t)quad_swap1((int)gi[c]);
+                const float v0_n = __int_as_float(quad_swap1(__float_as_int(vv[2 * c])));
+                const float v1_n = __int_as_float(quad_swap1(__float_as_int(vv[2 * c + 1])));
+                const bool tm_n = quad_swap1((int)to_mem[c]) != 0;
+                // first instruction serves the even lanes' corners, second one the odd lanes'
+                if (is_odd ? tm_n : to_mem[c]) atomicAdd(dtable + 2 * (size_t)(is_odd ? gi_n : gi[c]) + is_odd, is_odd ? v1_n : vv[2 * c]);
+                if (is_odd ? to_mem[c] : tm_n) atomicAdd(dtable + 2 * (size_t)(is_odd ? gi[c] : gi_n) + is_odd, is_odd ? vv[2 * c + 1] : v0_n);
+            }
+        }
+        // flush list: the occupied slots in slot order, so that sibling sectors of a line become list neighbours
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int s0 = 0; s0 < kSlots; s0 += 64) {
+            const bool occ = key[s0 + lane] != kNoLine;
+            const uint64_t om = __builtin_amdgcn_ballot_w64(occ);
+            if (occ) {
+                uint32_t pos = used + __builtin_amdgcn_mbcnt_hi((uint32_t)(om >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)om, 0));
+                // trip-major transposed: list position i of trip i / 32 is handled by lane group i % 8 as its (i % 32) / 8-th slot
+                pos = (pos & ~31u) + ((pos & 7u) << 2) + ((pos >> 3) & 3u);
+                list[pos] = (uint16_t)(s0 + lane);
+            }
+            used += __builtin_popcountll(om);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // flush: 8 lanes per sector, 8 sectors per instruction, 32 per trip
+        const int sub = lane & (kPay - 1);
+        const uint32_t gq = (uint32_t)lane >> 3;
+        for (uint32_t t0 = 0; t0 < used; t0 += 32) {
+            const uint64_t four = *(lds_u64 *)&list[t0 + 4 * gq];
+            uint32_t sl[4], ln[4];
+            float fv[4];
+            bool ok[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t e = (uint32_t)(four >> (16 * u)) & 0xFFFFu;
+                ok[u] = t0 + 8 * u + gq < used;
+                sl[u] = ok[u] ? e : (uint32_t)lane;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ln[u] = key[sl[u]];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)       // read + zero in one DS instruction; idle lanes swap their private dummy word
+                fv[u] = __hip_atomic_exchange(ok[u] ? &val[sl[u] * kPay + sub] : (lds_f32 *)dummy32, 0.f, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_WAVEFRONT);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (ok[u] && fv[u] != 0.f) atomicAdd(dtable + (size_t)ln[u] * kPay + sub, fv[u]);
+        }
+        if (used) {      // every occupied key was in the list: reset all of them, 8 keys per lane
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            if constexpr (kPair) {      // occupied slots in slot order: sibling sectors of a line become list neighbours
-#pragma unroll
-                for (int s0 = 0; s0 < kSlots; s0 += 64) {
-                    const bool occ = key[s0 + lane] != kNoLine;
-                    // kAlign: both slots of an occupied pair bucket (lanes 2b, 2b + 1) take a list position
-                    const bool take = kAlign ? (occ || quad_swap1((int)occ) != 0) : occ;
-                    const uint64_t om = __builtin_amdgcn_ballot_w64(take);
-                    if (take) {
-                        uint32_t pos = used + __builtin_amdgcn_mbcnt_hi((uint32_t)(om >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)om, 0));
-                        // trip-major transposed: list position i of trip i / 32 is handled by lane group i % 8 as its (i % 32) / 8-th slot
-                        if constexpr (kFlush2) pos = (pos & ~31u) + ((pos & 7u) << 2) + ((pos >> 3) & 3u);
-                        list[pos] = occ ? (uint16_t)(s0 + lane) : (uint16_t)0xFFFFu;      // 0xFFFF: the absent sibling of a pair
-                    }
-                    used += __builtin_popcountll(om);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            constexpr int kPer = 64 / kPay;   // slots per flush instruction
-            const int sub = lane & (kPay - 1);
-            if constexpr (kFlush2) {
-                static_assert(!kFlush2 || (kPair && kPay == 8 && kSlots >= 256 && kSlots <= 512 && kSlots % 64 == 0),
-                              "flush v2: 256 .. 512 paired 32-byte slots (bulk key reset: 8 keys per lane)");
-                const uint32_t gq = (uint32_t)lane >> 3;
-                touch_next();
-                for (uint32_t t0 = 0; t0 < used; t0 += 32) {
-                    const uint64_t four = *(lds_u64 *)&list[t0 + 4 * gq];
-                    uint32_t sl[4], ln[4];
-                    float vv[4];
-                    bool ok[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const uint32_t e = (uint32_t)(four >> (16 * u)) & 0xFFFFu;
-                        ok[u] = t0 + 8 * u + gq < used && (!kAlign || e != 0xFFFFu);
-                        sl[u] = ok[u] ? e : (uint32_t)lane;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) ln[u] = key[sl[u]];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)       // read + zero in one DS instruction; idle lanes swap their private dummy word
-                        vv[u] = __hip_atomic_exchange(ok[u] ? &val[sl[u] * kPay + sub] : (lds_f32 *)dummy32, 0.f, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_WAVEFRONT);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (ok[u] && vv[u] != 0.f && !(dbg & 1)) atomicAdd(dtable + (size_t)ln[u] * kPay + sub, vv[u]);
-                }
-                if (used) {      // every occupied key was in the list: reset all of them, 8 keys per lane
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                    typedef __attribute__((address_space(3))) u32x4_t lds_u32x4;
-                    lds_u32x4 *k4 = (lds_u32x4 *)key;
-                    const u32x4_t none = {kNoLine, kNoLine, kNoLine, kNoLine};
-                    k4[lane] = none;
-                    if (kSlots == 512 || lane < (kSlots - 256) / 4) k4[64 + lane] = none;
-                    *dummy32 = kNoLine;      // (the exchange above left 0.f in the idle lanes' dummy word)
-                }
-            } else
-            for (uint32_t e0 = lane / kPay; e0 < used; e0 += 4 * kPer) {
-                uint32_t ent[4], ln[4];
-                float vv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) ent[u] = (e0 + kPer * u < used) ? (uint32_t)list[e0 + kPer * u] : 0xFFFFFFFFu;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    ln[u] = (ent[u] != 0xFFFFFFFFu) ? key[ent[u]] : 0u;
-                    vv[u] = (ent[u] != 0xFFFFFFFFu) ? val[ent[u] * kPay + sub] : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (vv[u] != 0.f && !(dbg & 1)) atomicAdd(dtable + (size_t)ln[u] * kPay + sub, vv[u]);
-                __builtin_amdgcn_wave_barrier();   // every lane of a slot has read the key before lane 0 resets it
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (ent[u] != 0xFFFFFFFFu) {
-                        val[ent[u] * kPay + sub] = 0.f;
-                        if (sub == 0) key[ent[u]] = kNoLine;
-                    }
-            }
+            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+            typedef __attribute__((address_space(3))) u32x4_t lds_u32x4;
+            lds_u32x4 *k4 = (lds_u32x4 *)key;
+            const u32x4_t none = {kNoLine, kNoLine, kNoLine, kNoLine};
+            k4[lane] = none;
+            k4[64 + lane] = none;
+            *dummy32 = kNoLine;      // (the exchange above left 0.f in the idle lanes' dummy word)
+        }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     };
 
-    if (kPrefetch && g.l_begin < g.l_end) fetch_next(g.l_begin);
     for (int l = g.l_begin; l < g.l_end; ++l) {
         const LevelInfo li = level_info(g, l);
         // (few-runs path only)  The coarsest levels are a few thousand lines that every wave of the launch adds to: the
@@ -1133,299 +654,143 @@ __global__ __launch_bounds__(64 * kWaves) void hash_bwd_batched_kernel(GridParam
                                      ? ws + (size_t)((blockIdx.x * kWaves / 4) & (unsigned)g.rep_mask) * g.rep_stride + 2 * (size_t)li.offset
                                      : dtable + 2 * (size_t)li.offset;
         const float2 *__restrict__ tab = table + li.offset;
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r) {
-            float w0, w1, w2;
-            uint32_t p0, p1, p2;
-            float2 gy;
-            uint32_t idx[8];
-            float2 tv[8];
-            if constexpr (kPrefetch) {      // fetched during the previous level's cache pass (or by the prologue)
-                w0 = nw0; w1 = nw1; w2 = nw2;
-                p0 = np0; p1 = np1; p2 = np2;
-                gy = ngy;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    idx[c] = nidx[c];
-                    tv[c] = ntv[c];
-                }
-                pending_touch = false;
-            } else {
-                pos_fract(px[r][0], li.scale, w0, p0);
-                pos_fract(px[r][1], li.scale, w1, p1);
-                pos_fract(px[r][2], li.scale, w2, p2);
-                gy = dy[(int64_t)l * n_cap + si[r]];
-                corner_indices(li, p0, p1, p2, idx);
-                if (WITH_DX) {
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) tv[c] = tab[idx[c]];
-                }
-            }
-            if (!valid[r]) gy = make_float2(0.f, 0.f);
-            // runs of lanes in the same cell
-            const uint32_t q0 = wave_shr1(p0), q1 = wave_shr1(p1), q2 = wave_shr1(p2);
-            const int head = (lane == 0) || (q0 != p0) || (q1 != p1) || (q2 != p2);
-            const int next_head = wave_shl1(head);
-            const bool run_end = (lane == 63) || next_head;
-            float v[16];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float wt = ((c & 1) ? w0 : 1.f - w0) * ((c & 2) ? w1 : 1.f - w1) * ((c & 4) ? w2 : 1.f - w2);
-                v[2 * c] = wt * gy.x;
-                v[2 * c + 1] = wt * gy.y;
-            }
-            if (!(dbg & 4)) {
-                // segmented inclusive scan: inside the 16-lane rows with DPP, then a serial carry across the 3 row borders
-                const int row_pos = lane & 15;
-                int flag = head | (row_pos == 0);   // "my partial sum already starts at my run's head (or my row's start)"
-                if (seg_scan_row_step<1>(v, flag, row_pos) && seg_scan_row_step<2>(v, flag, row_pos) &&
-                    seg_scan_row_step<4>(v, flag, row_pos))
-                    seg_scan_row_step<8>(v, flag, row_pos);
-                // `open` = no run head between my row's first lane and me (inclusive): my run continues from the row before
-                int open = !head;
-#pragma unroll
-                for (int off = 1; off < 16; off <<= 1) {
-                    const int o = (off == 1) ? row_shr_i32<1>(open) : (off == 2) ? row_shr_i32<2>(open)
-                                : (off == 4) ? row_shr_i32<4>(open) : row_shr_i32<8>(open);
-                    open &= (row_pos >= off) ? o : 1;
-                }
-                seg_scan_cross_rows(v, open, lane);
-            }
-            if (WITH_DX) {
-                // d(x): t_c = <dy, table[c]>; along each axis the difference of the two faces, weighted by the other two axes
-                const float a0 = 1.f - w0, a1 = 1.f - w1, a2 = 1.f - w2;
-                float t[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) t[c] = gy.x * tv[c].x + gy.y * tv[c].y;
-                const float d0 = a2 * (a1 * (t[1] - t[0]) + w1 * (t[3] - t[2])) + w2 * (a1 * (t[5] - t[4]) + w1 * (t[7] - t[6]));
-                const float d1 = a2 * (a0 * (t[2] - t[0]) + w0 * (t[3] - t[1])) + w2 * (a0 * (t[6] - t[4]) + w0 * (t[7] - t[5]));
-                const float d2 = a1 * (a0 * (t[4] - t[0]) + w0 * (t[5] - t[1])) + w1 * (a0 * (t[6] - t[2]) + w0 * (t[7] - t[3]));
-                dacc[r][0] = fmaf(li.scale, d0, dacc[r][0]);
-                dacc[r][1] = fmaf(li.scale, d1, dacc[r][1]);
-                dacc[r][2] = fmaf(li.scale, d2, dacc[r][2]);
-            }
-            if constexpr (kPrefetch) {
-                if (l + 1 < g.l_end) fetch_next(l + 1);      // the next level's loads go out before this level's cache pass
-            }
-            // ---- run ends add their 8 corner sums into the line cache, then the level's lines are flushed.
-            // The kernel is instruction-issue bound (rocprof: VALU+SALU+LDS issue ~ 3 ms of a 3.6 ms launch), so this part
-            // is written for few instructions: one probe per corner, no retry rounds (a lost slot goes straight to memory),
-            // every DS operation issued by all lanes (idle lanes aim at a private dummy word) so that a batch of 8 goes out
-            // back to back with one wait.
-            const uint64_t ends_mask = __builtin_amdgcn_ballot_w64(run_end && !(dbg & 2));
-            const int n_ends = __builtin_popcountll(ends_mask);
-            if (n_ends <= few_runs) {
-                // Coarse levels: a wave ends only a handful of runs, and almost all of the ~500 instructions of the cache
-                // path below would be spent on idle lanes.  Instead the run ends park their 8 indices + 16 sums in LDS
-                // (the zeroed payload area doubles as staging) and the wave re-reads them with 16 lanes per run -- lane =
-                // (corner, feature), 4 runs per instruction -- and adds straight to memory: the two features and the
-                // x / x+1 neighbours of an entry share requests inside the instruction.
-                if (n_ends > 0) {
-                    lds_u32 *stage = (lds_u32 *)val;           // [run][8 idx | 16 values]
-                    if (run_end && !(dbg & 2)) {
-                        const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ends_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends_mask, 0));
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) stage[rank * 24 + c] = idx[c];
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) stage[rank * 24 + 8 + k] = __float_as_uint(v[k]);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    const int k16 = lane & 15;
-                    touch_next();
-                    for (int r0 = lane >> 4; r0 < n_ends; r0 += 4) {
-                        const uint32_t e = stage[r0 * 24 + (k16 >> 1)];
-                        const float a = __uint_as_float(stage[r0 * 24 + 8 + k16]);
-                        if (a != 0.f && !(dbg & 16)) atomicAdd(dt + 2 * (size_t)e + (k16 & 1), a);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    for (int s_ = lane; s_ < n_ends * 24; s_ += 64) stage[s_] = 0u;   // the payload area must read zero again
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                }
-            } else {
-                uint32_t gidx[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) gidx[c] = li.offset + idx[c];
-                if (fill + n_ends > 64) {               // the queue cannot take this level: run the pending pass first
-                    insert_pass(lane < fill, q_idx, q_v);
-                    fill = 0;
-                }
-                if (fill == 0 && n_ends > stage_max) {
-                    // fine level: most lanes end a run -- pass straight from the lanes that hold them (no compaction)
-                    insert_pass(run_end && !(dbg & 2), gidx, v);
-                } else {
-                    // append: queue lane fill + r takes the r-th run end of this level (rank -> lane through LDS, then 24
-                    // ds_bpermute moves); the pass runs when the queue is full, at a fine level, or after the last level
-                    if (run_end && !(dbg & 2))
-                        perm[__builtin_amdgcn_mbcnt_hi((uint32_t)(ends_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends_mask, 0))] = (uint32_t)lane;
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    const int r = lane - fill;
-                    const bool take = r >= 0 && r < n_ends;
-                    const int src = take ? (int)perm[r] : lane;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        const uint32_t t = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)gidx[c]);
-                        q_idx[c] = take ? t : q_idx[c];
-                    }
-#pragma unroll
-                    for (int k2 = 0; k2 < 16; ++k2) {
-                        const float t = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v[k2])));
-                        q_v[k2] = take ? t : q_v[k2];
-                    }
-                    fill += n_ends;
-                    __builtin_amdgcn_wave_barrier();
-                }
-            }
-        }
-    }
-    if (fill > 0) insert_pass(lane < fill, q_idx, q_v);
-    if (WITH_DX) {
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r)
-            if (valid[r]) {
-                if (g.dx_accumulate) {
-                    dacc[r][0] += dx[si[r] * 3 + 0];
-                    dacc[r][1] += dx[si[r] * 3 + 1];
-                    dacc[r][2] += dx[si[r] * 3 + 2];
-                }
-                dx[si[r] * 3 + 0] = dacc[r][0];
-                dx[si[r] * 3 + 1] = dacc[r][1];
-                dx[si[r] * 3 + 2] = dacc[r][2];
-            }
-    }
-}
-
-
-// Coarse levels (round 3).  Inside the fused launch above, every level below ~9 costs 0.09 ms although a wave ends only 1 .. 10
-// runs there and sends 0.1 .. 0.4 lines per sample to memory (gpurun_out/r3a): those levels pay for the fine levels'
-// machinery -- the 80 KB of LDS per workgroup that hold the sector cache cap the kernel at two waves per SIMD, and at that
-// occupancy nothing hides the latency of the eight table gathers, the dy load and the scan's DPP chain of a level.  This
-// kernel has no cache: lane = sample, the same segmented scan leaves each run's 8 x 2 corner sums in the run's last lane, the
-// run ends are transposed through a 1.5 KB per-wave staging area (16 runs per trip) and added to memory with 16 lanes per run
-// (lane = corner x feature: the two features and the x / x+1 neighbours of an entry share one request).  6 KB of LDS per
-// workgroup and < 128 registers: the occupancy is set by the registers, and the waves of a SIMD hide each other's latencies.
-// Any level is handled correctly (a fine level just sends more requests than the cache would), so the split level is a
-// tuning parameter of the launch (lse_hash_bwd_opts.coarse_levels), not a correctness condition.
-#ifdef LSE_DEV_KNOBS   // development build only (csrc/dev_knobs.h): superseded / A-B variant, not in liblse_hip.so
-template <bool WITH_DX>
-__global__ __launch_bounds__(256) void hash_bwd_coarse_kernel(GridParams g, const float *__restrict__ x,
-                                                              const float2 *__restrict__ dy,
-                                                              const float2 *__restrict__ table,
-                                                              float *__restrict__ dtable, float *__restrict__ dx,
-                                                              int64_t n_cap, int dbg, float *__restrict__ ws,
-                                                              const int64_t *__restrict__ n_dev)
-{
-    const int64_t n = lse::clamp_count(n_cap, n_dev);      // n_cap stays the level stride of dy
-    constexpr int kBatch = 16;                      // run ends per staging trip
-    __shared__ uint32_t s_stage[4][kBatch * 24];    // [run][8 idx | 16 sums]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t wave_base = ((int64_t)blockIdx.x * 4 + wave) * 64;
-    if (wave_base >= n) return;                     // (no workgroup barrier anywhere below)
-    lds_u32 *stage = (lds_u32 *)&s_stage[wave][0];
-    const int64_t i0 = wave_base + lane;
-    const bool valid = i0 < n;
-    const int64_t si = valid ? i0 : n - 1;
-    const float px0 = x[si * 3 + 0], px1 = x[si * 3 + 1], px2 = x[si * 3 + 2];
-    float dacc0 = 0.f, dacc1 = 0.f, dacc2 = 0.f;
-    const int k16 = lane & 15, sub_run = lane >> 4;
-
-    for (int l = g.l_begin; l < g.l_end; ++l) {
-        const LevelInfo li = level_info(g, l);
-        float *__restrict__ dt = (ws != nullptr && l < g.rep_levels)
-                                     ? ws + (size_t)(blockIdx.x & (unsigned)g.rep_mask) * g.rep_stride + 2 * (size_t)li.offset
-                                     : dtable + 2 * (size_t)li.offset;
-        const float2 *__restrict__ tab = table + li.offset;
         float w0, w1, w2;
         uint32_t p0, p1, p2;
-        pos_fract(px0, li.scale, w0, p0);
-        pos_fract(px1, li.scale, w1, p1);
-        pos_fract(px2, li.scale, w2, p2);
-        float2 gy = dy[(int64_t)l * n_cap + si];
-        if (!valid) gy = make_float2(0.f, 0.f);
         uint32_t idx[8];
-        corner_indices(li, p0, p1, p2, idx);
         float2 tv[8];
-        if (WITH_DX && !(dbg & 8)) {
+        pos_fract(px[0], li.scale, w0, p0);
+        pos_fract(px[1], li.scale, w1, p1);
+        pos_fract(px[2], li.scale, w2, p2);
+        float2 gy = dy[(int64_t)l * n_cap + si];
+        corner_indices(li, p0, p1, p2, idx);
+        if (WITH_DX) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) tv[c] = tab[idx[c]];
         }
+        if (!valid) gy = make_float2(0.f, 0.f);
+        // runs of lanes in the same cell
         const uint32_t q0 = wave_shr1(p0), q1 = wave_shr1(p1), q2 = wave_shr1(p2);
         const int head = (lane == 0) || (q0 != p0) || (q1 != p1) || (q2 != p2);
         const int next_head = wave_shl1(head);
-        const bool run_end = ((lane == 63) || next_head) && !(dbg & 2);
+        const bool run_end = (lane == 63) || next_head;
         float v[16];
-        const float a0 = 1.f - w0, a1 = 1.f - w1, a2 = 1.f - w2;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const float wt = ((c & 1) ? w0 : a0) * ((c & 2) ? w1 : a1) * ((c & 4) ? w2 : a2);
+            const float wt = ((c & 1) ? w0 : 1.f - w0) * ((c & 2) ? w1 : 1.f - w1) * ((c & 4) ? w2 : 1.f - w2);
             v[2 * c] = wt * gy.x;
             v[2 * c + 1] = wt * gy.y;
         }
-        if (!(dbg & 4)) {
-            const int row_pos = lane & 15;
-            int flag = head | (row_pos == 0);
-            if (seg_scan_row_step<1>(v, flag, row_pos) && seg_scan_row_step<2>(v, flag, row_pos) &&
-                seg_scan_row_step<4>(v, flag, row_pos))
-                seg_scan_row_step<8>(v, flag, row_pos);
-            int open = !head;
+        // segmented inclusive scan: inside the 16-lane rows with DPP, then a serial carry across the 3 row borders
+        const int row_pos = lane & 15;
+        int flag = head | (row_pos == 0);   // "my partial sum already starts at my run's head (or my row's start)"
+        if (seg_scan_row_step<1>(v, flag, row_pos) && seg_scan_row_step<2>(v, flag, row_pos) &&
+            seg_scan_row_step<4>(v, flag, row_pos))
+            seg_scan_row_step<8>(v, flag, row_pos);
+        // `open` = no run head between my row's first lane and me (inclusive): my run continues from the row before
+        int open = !head;
 #pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const int o = (off == 1) ? row_shr_i32<1>(open) : (off == 2) ? row_shr_i32<2>(open)
-                            : (off == 4) ? row_shr_i32<4>(open) : row_shr_i32<8>(open);
-                open &= (row_pos >= off) ? o : 1;
-            }
-            seg_scan_cross_rows(v, open, lane);
+        for (int off = 1; off < 16; off <<= 1) {
+            const int o = (off == 1) ? row_shr_i32<1>(open) : (off == 2) ? row_shr_i32<2>(open)
+                        : (off == 4) ? row_shr_i32<4>(open) : row_shr_i32<8>(open);
+            open &= (row_pos >= off) ? o : 1;
         }
-        if (WITH_DX && !(dbg & 8)) {
+        seg_scan_cross_rows(v, open, lane);
+        if (WITH_DX) {
             // d(x): t_c = <dy, table[c]>; along each axis the difference of the two faces, weighted by the other two axes
+            const float a0 = 1.f - w0, a1 = 1.f - w1, a2 = 1.f - w2;
             float t[8];
 #pragma unroll
             for (int c = 0; c < 8; ++c) t[c] = gy.x * tv[c].x + gy.y * tv[c].y;
             const float d0 = a2 * (a1 * (t[1] - t[0]) + w1 * (t[3] - t[2])) + w2 * (a1 * (t[5] - t[4]) + w1 * (t[7] - t[6]));
             const float d1 = a2 * (a0 * (t[2] - t[0]) + w0 * (t[3] - t[1])) + w2 * (a0 * (t[6] - t[4]) + w0 * (t[7] - t[5]));
             const float d2 = a1 * (a0 * (t[4] - t[0]) + w0 * (t[5] - t[1])) + w1 * (a0 * (t[6] - t[2]) + w0 * (t[7] - t[3]));
-            dacc0 = fmaf(li.scale, d0, dacc0);
-            dacc1 = fmaf(li.scale, d1, dacc1);
-            dacc2 = fmaf(li.scale, d2, dacc2);
+            dacc[0] = fmaf(li.scale, d0, dacc[0]);
+            dacc[1] = fmaf(li.scale, d1, dacc[1]);
+            dacc[2] = fmaf(li.scale, d2, dacc[2]);
         }
+        // ---- run ends add their 8 corner sums into the sector cache, or straight to memory where the wave ends only a few.
+        // The kernel is instruction-issue bound (rocprof: VALU+SALU+LDS issue ~ 3 ms of a 3.6 ms launch), so this part
+        // is written for few instructions: every DS operation is issued by all lanes (idle lanes aim at a private dummy
+        // word) so that a batch of 8 goes out back to back with one wait.
         const uint64_t ends_mask = __builtin_amdgcn_ballot_w64(run_end);
         const int n_ends = __builtin_popcountll(ends_mask);
-        const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ends_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends_mask, 0));
-        for (int b0 = 0; b0 < n_ends; b0 += kBatch) {
-            const int r = rank - b0;
-            if (run_end && r >= 0 && r < kBatch) {
+        if (n_ends <= few_runs) {
+            // Coarse levels: a wave ends only a handful of runs, and almost all of the ~500 instructions of the cache
+            // path below would be spent on idle lanes.  Instead the run ends park their 8 indices + 16 sums in LDS
+            // (the zeroed payload area doubles as staging) and the wave re-reads them with 16 lanes per run -- lane =
+            // (corner, feature), 4 runs per instruction -- and adds straight to memory: the two features and the
+            // x / x+1 neighbours of an entry share requests inside the instruction.
+            if (n_ends > 0) {
+                lds_u32 *stage = (lds_u32 *)val;           // [run][8 idx | 16 values]
+                if (run_end) {
+                    const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ends_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends_mask, 0));
 #pragma unroll
-                for (int c = 0; c < 8; ++c) stage[r * 24 + c] = idx[c];
+                    for (int c = 0; c < 8; ++c) stage[rank * 24 + c] = idx[c];
 #pragma unroll
-                for (int k = 0; k < 16; ++k) stage[r * 24 + 8 + k] = __float_as_uint(v[k]);
+                    for (int k = 0; k < 16; ++k) stage[rank * 24 + 8 + k] = __float_as_uint(v[k]);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const int k16 = lane & 15;
+                for (int r0 = lane >> 4; r0 < n_ends; r0 += 4) {
+                    const uint32_t e = stage[r0 * 24 + (k16 >> 1)];
+                    const float a = __uint_as_float(stage[r0 * 24 + 8 + k16]);
+                    if (a != 0.f) atomicAdd(dt + 2 * (size_t)e + (k16 & 1), a);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                for (int s_ = lane; s_ < n_ends * 24; s_ += 64) stage[s_] = 0u;   // the payload area must read zero again
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int cnt = min(kBatch, n_ends - b0);
-            for (int r0 = sub_run; r0 < cnt; r0 += 4) {
-                const uint32_t e = stage[r0 * 24 + (k16 >> 1)];
-                const float a = __uint_as_float(stage[r0 * 24 + 8 + k16]);
-                if (a != 0.f && !(dbg & 1)) atomicAdd(dt + 2 * (size_t)e + (k16 & 1), a);
+        } else {
+            uint32_t gidx[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) gidx[c] = li.offset + idx[c];
+            if (fill + n_ends > 64) {               // the queue cannot take this level: run the pending pass first
+                insert_pass(lane < fill, q_idx, q_v);
+                fill = 0;
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();      // the next trip (or level) overwrites the staging area
+            if (fill == 0 && n_ends > stage_max) {
+                // fine level: most lanes end a run -- pass straight from the lanes that hold them (no compaction)
+                insert_pass(run_end, gidx, v);
+            } else {
+                // append: queue lane fill + r takes the r-th run end of this level (rank -> lane through LDS, then 24
+                // ds_bpermute moves); the pass runs when the queue is full, at a fine level, or after the last level
+                if (run_end)
+                    perm[__builtin_amdgcn_mbcnt_hi((uint32_t)(ends_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends_mask, 0))] = (uint32_t)lane;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const int r = lane - fill;
+                const bool take = r >= 0 && r < n_ends;
+                const int src = take ? (int)perm[r] : lane;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const uint32_t t = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)gidx[c]);
+                    q_idx[c] = take ? t : q_idx[c];
+                }
+#pragma unroll
+                for (int k2 = 0; k2 < 16; ++k2) {
+                    const float t = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v[k2])));
+                    q_v[k2] = take ? t : q_v[k2];
+                }
+                fill += n_ends;
+                __builtin_amdgcn_wave_barrier();
+            }
         }
     }
+    if (fill > 0) insert_pass(lane < fill, q_idx, q_v);
     if (WITH_DX && valid) {
         if (g.dx_accumulate) {
-            dacc0 += dx[si * 3 + 0];
-            dacc1 += dx[si * 3 + 1];
-            dacc2 += dx[si * 3 + 2];
+            dacc[0] += dx[si * 3 + 0];
+            dacc[1] += dx[si * 3 + 1];
+            dacc[2] += dx[si * 3 + 2];
         }
-        dx[si * 3 + 0] = dacc0;
-        dx[si * 3 + 1] = dacc1;
-        dx[si * 3 + 2] = dacc2;
+        dx[si * 3 + 0] = dacc[0];
+        dx[si * 3 + 1] = dacc[1];
+        dx[si * 3 + 2] = dacc[2];
     }
 }
-#endif  // LSE_DEV_KNOBS
 
 // dtable[i] += sum over replicas; the workspace reads zero again afterwards (it is handed over zeroed and returned zeroed)
 __global__ __launch_bounds__(256) void hash_bwd_reduce_replicas_kernel(float *__restrict__ ws, float *__restrict__ dtable,
@@ -1560,36 +925,11 @@ extern "C" int lse_hash_fwd(const lse_grid_desc *desc, const float *x01, const f
     if (n == 0) return LSE_OK;
     LSE_REQUIRE(x01 && table && y, "lse_hash_fwd: null pointer");
     const int64_t chunks = (n + kFwdThreads * kFwdItems - 1) / (kFwdThreads * kFwdItems);
-    const int mapping = (int)lse::option("hash_fwd_mapping");
-    int lds_levels = 0;
     hipStream_t st = lse::as_stream(stream);
-#ifdef LSE_DEV_KNOBS
-    // knob hash_fwd_lds_levels = k: the k coarsest levels whose whole table fits one CU's LDS run in hash_fwd_lds_kernel (needs
-    // the default mapping 4, whose grid simply ends k levels earlier)
-    if (mapping == 4) {
-        const int want = (int)std::min<int64_t>(lse::option("hash_fwd_lds_levels"), g.n_levels - 1);
-        while (lds_levels < want && (int64_t)(g.offsets[lds_levels + 1] - g.offsets[lds_levels]) * 8 <= 156 * 1024) ++lds_levels;
-    }
-    for (int l = 0; l < lds_levels; ++l) {
-        const int lds_bytes = (int)(g.offsets[l + 1] - g.offsets[l]) * 8;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_fwd_lds_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);     // (per device: set per call)
-        if (e != hipSuccess) {
-            lse::set_error("lse_hash_fwd: cannot raise dynamic LDS to %d bytes: %s", lds_bytes, hipGetErrorString(e));
-            return LSE_E_LAUNCH;
-        }
-        // as many workgroups as fit the chip at once with this much LDS each (16 waves per workgroup: at most 2 per CU)
-        const int per_cu = lds_bytes <= 78 * 1024 ? 2 : 1;
-        const int64_t wgs = std::max<int64_t>(1, std::min<int64_t>(256 * per_cu, (n + 2 * kFwdLdsThreads - 1) / (2 * kFwdLdsThreads)));
-        hipLaunchKernelGGL(hash_fwd_lds_kernel, dim3((unsigned)wgs), dim3(kFwdLdsThreads), lds_bytes, st, g, l, x01,
-                           reinterpret_cast<const float2 *>(table), reinterpret_cast<float2 *>(y), n, n_dev);
-    }
-#endif
-    const int64_t blocks = chunks * (g.n_levels - lds_levels);
+    const int64_t blocks = chunks * g.n_levels;
     LSE_REQUIRE(blocks < (1ll << 31), "lse_hash_fwd: grid too large");
     hipLaunchKernelGGL(hash_fwd_kernel, dim3((unsigned)blocks), dim3(kFwdThreads), 0, st, g, x01,
-                       reinterpret_cast<const float2 *>(table), reinterpret_cast<float2 *>(y), n, chunks, mapping,
-                       n_dev, lds_levels);
+                       reinterpret_cast<const float2 *>(table), reinterpret_cast<float2 *>(y), n, chunks, n_dev);
     return lse::check_launch("lse_hash_fwd");
 }
 
@@ -1616,26 +956,26 @@ extern "C" void lse_hash_bwd_default_opts(lse_hash_bwd_opts *o)
     o->impl = 2;           // lane-per-sample + LDS sector cache, run ends of several levels batched per cache pass
     o->stage_max = (int32_t)lse::option("hash_bwd_stage_max");   // impl 2: a level ending more runs than this per wave passes unstaged
                            // when the queue is empty
-    o->gran = 6;           // impl 2: 512 slots of one 32-B sector, paired by 64-B line, second-generation flush (4 = first-generation
-                           // flush, 2 = unpaired); impl 1: 2 / 3
-    o->few_runs = (int32_t)lse::option("hash_bwd_few_runs");     // 8 (round 5, profiles/r05_hash_bwd_thresholds.txt: with stage_max 48 the best pair for steps
+    o->few_runs = (int32_t)lse::option("hash_bwd_few_runs");     // 8 (profiles/r05_hash_bwd_thresholds.txt: with stage_max 48 the best pair for steps
                            // that grow with the distance -- the reference's default configuration 1.51 -> 1.43 ms -- and neutral
                            // (+0.2 %) at the metric size, whose constant step prefers fewer direct adds -- (3, 56) on the final kernel; callers that know the
                            // regime pass the pair (lsenerf_amd/ops.py: HASH_BWD_DENSE_STEPS); 10 and 16: slower everywhere)
-    o->second_probe = (int32_t)lse::option("hash_bwd_probes");   // extra probe rounds (home + k * step) before a corner goes to memory
+    o->second_probe = (int32_t)lse::option("hash_bwd_probes");   // extra probe rounds (home + 2 * k) before a corner goes to memory
                            // alone; pays wherever the kernel is bound by atomic requests, costs ~2 % per round where it is issue-bound.
-                           // 1 -> 3 rounds (round 3, once the later rounds probed NEW slots): requests 50.5 -> 48.2 M (metric size),
-                           // 28.3 -> 26.9 M (default configuration); hash_bwd 2.66 -> 2.66 / 1.40 -> 1.34 / 1.13 -> 1.05 ms (metric size /
-                           // default configuration / 3-bundle step), M-packed step 6.07 -> 5.99; 4 rounds: slower everywhere
-    o->rounds = 32;
-    o->dbg = 0;
-    o->interleave_from_scale = 1e30f;   // measured negative on MI355X (same-address lanes of one atomic instruction serialise)
-    o->coarse_levels = 0;  // levels below this one run in the cache-free high-occupancy kernel (hash_bwd_coarse_kernel) first
+                           // 1 -> 3 rounds: requests 50.5 -> 48.2 M (metric size), 28.3 -> 26.9 M (default configuration); hash_bwd
+                           // 2.66 -> 2.66 / 1.40 -> 1.34 / 1.13 -> 1.05 ms (metric size / default configuration / 3-bundle step),
+                           // M-packed step 6.07 -> 5.99; 4 rounds: slower everywhere (profiles/r03_hash_bwd_probe_rounds.txt)
     o->replicas = 16;      // direct adds of the levels < replica_levels go to this many replicas (power of two); needs `workspace`
                            // (M-packed 3.67 -> 3.21 ms with 8, 3.16 with 16, 3.18 with 32; M-march and the default configuration +-1 %)
     o->replica_levels = 4; // 16^3 .. 43^3: 125 568 entries = 1 MB per replica
     o->workspace = nullptr;
     o->workspace_bytes = 0;
+    // reserved (include/lse_hip.h): the values lse_hash_bwd_ex insists on
+    o->gran = 6;
+    o->rounds = 32;
+    o->dbg = 0;
+    o->interleave_from_scale = 1e30f;
+    o->coarse_levels = 0;
     o->prefetch = 0;
 }
 
@@ -1683,20 +1023,17 @@ extern "C" int lse_hash_bwd_ex(const lse_grid_desc *desc, const float *x01, cons
     lse_hash_bwd_opts o;
     lse_hash_bwd_default_opts(&o);
     if (opts) o = *opts;
-#ifndef LSE_DEV_KNOBS
-    // the library that ships holds the production variants only: the batched sector-cache kernel (impl 2, gran 6) and the generic
-    // 16-lanes-per-sample kernel (impl 0; also taken for grids whose levels do not start on 64-byte lines)
-    if (!((o.impl == 2 && o.gran == 6 && !o.prefetch) || o.impl == 0) || o.coarse_levels != 0 || o.dbg != 0 || o.rounds != 32 ||
+    // two kernels exist: the batched sector-cache kernel (impl 2) and the generic 16-lanes-per-sample kernel (impl 0; also taken for
+    // grids whose levels do not start on 64-byte lines).  The reserved fields once selected variants that are retired
+    // (DESIGN_HISTORY.md): anything but the value lse_hash_bwd_default_opts writes is refused before anything is launched.
+    if ((o.impl != 0 && o.impl != 2) || o.gran != 6 || o.prefetch != 0 || o.coarse_levels != 0 || o.rounds != 32 || o.dbg != 0 ||
         o.interleave_from_scale < 1e29f) {
-        lse::set_error("lse_hash_bwd: impl %d / gran %d / prefetch %d / coarse_levels %d / rounds %d / dbg %d selects a development "
-                       "variant (csrc/dev_knobs.h: build liblse_hip_dev.so)", o.impl, o.gran, o.prefetch, o.coarse_levels, o.rounds, o.dbg);
+        lse::set_error("lse_hash_bwd: impl %d / gran %d / prefetch %d / coarse_levels %d / rounds %d / dbg %d / interleave_from_scale %g "
+                       "selects a retired development variant (DESIGN_HISTORY.md)", o.impl, o.gran, o.prefetch, o.coarse_levels, o.rounds,
+                       o.dbg, (double)o.interleave_from_scale);
         return LSE_E_UNSUPPORTED;
     }
-#endif
-    LSE_REQUIRE(o.impl >= 0 && o.impl <= 2, "lse_hash_bwd: opts.impl must be 0, 1 or 2");
     LSE_REQUIRE(o.stage_max >= 0 && o.stage_max <= 64, "lse_hash_bwd: opts.stage_max must be in [0, 64]");
-    LSE_REQUIRE(o.gran >= 2 && o.gran <= 13, "lse_hash_bwd: opts.gran must be 2 .. 13");
-    LSE_REQUIRE(o.rounds == 16 || o.rounds == 32 || o.rounds == 64, "lse_hash_bwd: opts.rounds must be 16, 32 or 64");
     LSE_REQUIRE(o.few_runs >= 0 && o.few_runs <= 16, "lse_hash_bwd: opts.few_runs must be in [0, 16]");
     GridParams g;
     int rc = fill_params(desc, g, "lse_hash_bwd");
@@ -1711,18 +1048,18 @@ extern "C" int lse_hash_bwd_ex(const lse_grid_desc *desc, const float *x01, cons
     if (n == 0) return LSE_OK;
     LSE_REQUIRE(x01 && dy && dtable, "lse_hash_bwd: null pointer");
     LSE_REQUIRE(!dx || table, "lse_hash_bwd: dx requested but table is null");
-    LSE_REQUIRE(o.coarse_levels >= 0 && o.coarse_levels <= LSE_MAX_GRID_LEVELS, "lse_hash_bwd: opts.coarse_levels out of range");
-    const float il_scale = o.interleave_from_scale;
-    const int rounds = o.rounds, impl = o.impl, dbg = o.dbg;
-    (void)rounds;
-#ifndef LSE_DEV_KNOBS
-    (void)dbg;      // (timing ablations exist in the development build only: rejected above)
-#endif
-    hipStream_t st = lse::as_stream(stream);
-    const float *tb = dx ? table : nullptr;
-    // device-side sample count: honoured by the default kernel (and the development build's coarse kernel)
-    LSE_REQUIRE(!n_dev || (impl == 2), "lse_hash_bwd: a device-side count needs opts.impl == 2");
-    // replicas of the coarsest levels for the direct adds (impl 2's few-runs path and the coarse kernel)
+    // the sector cache needs every level to start on a 64-B line (tcnn pads level sizes to 8 entries)
+    bool lines_ok = true;
+    for (int l = 0; l <= g.n_levels; ++l) lines_ok = lines_ok && (g.offsets[l] % 8 == 0);
+    const bool batched = o.impl == 2 && lines_ok;
+    // device-side sample count: honoured by the batched kernel only
+    LSE_REQUIRE(!n_dev || o.impl == 2, "lse_hash_bwd: a device-side count needs opts.impl == 2");
+    LSE_REQUIRE(!n_dev || lines_ok, "lse_hash_bwd: a device-side count needs 64-byte aligned levels (the default kernel)");
+    // batched: one wave = 64 samples per workgroup, rounded up to a multiple of 8 for the XCD chunk mapping;
+    // 16 lanes per sample: four waves of 4 * kRounds samples
+    const int64_t blocks = batched ? ((n + 63) / 64 + 7) / 8 * 8 : (n + 16 * kRounds - 1) / (16 * kRounds);
+    LSE_REQUIRE(blocks < (1ll << 31), "lse_hash_bwd: grid too large");
+    // replicas of the coarsest levels for the direct adds of the batched kernel's few-runs path
     float *ws = nullptr;
     int rep_lv = 0;
     const int64_t rep_floats = replica_floats(desc, o, &rep_lv);
@@ -1737,163 +1074,23 @@ extern "C" int lse_hash_bwd_ex(const lse_grid_desc *desc, const float *x01, cons
         g.rep_mask = o.replicas - 1;
         g.rep_stride = (uint32_t)rep_floats;
     }
-    struct ReduceAtExit {     // the replicas are folded into dtable after whatever kernels this call launches
-        float *ws, *dtable; int64_t floats; int n_rep; hipStream_t st;
-        ~ReduceAtExit() {
-            if (!ws) return;
-            const uint32_t n4 = (uint32_t)(floats / 4);
-            hipLaunchKernelGGL(hash_bwd_reduce_replicas_kernel, dim3((n4 + 255) / 256), dim3(256), 0, st, ws, dtable, n4, n_rep,
-                               (uint32_t)floats);
-        }
-    } reduce_at_exit{ws, dtable, rep_floats, o.replicas, st};
-#ifdef LSE_DEV_KNOBS
-    // the coarse share of the level range first, in the cache-free kernel; the rest of the range then accumulates into dx
-    const int coarse_end = std::min<int>(o.coarse_levels, level_end);
-    if (coarse_end > level_begin) {
-        GridParams gc = g;
-        gc.l_end = coarse_end;
-        const int64_t blocks = (n + 4 * 64 - 1) / (4 * 64);
-        LSE_REQUIRE(blocks < (1ll << 31), "lse_hash_bwd: grid too large");
+    hipStream_t st = lse::as_stream(stream);
+    const float *tb = dx ? table : nullptr;
+    if (batched) {
         const float2 *dy2 = reinterpret_cast<const float2 *>(dy);
         const float2 *tb2 = reinterpret_cast<const float2 *>(tb);
-        if (dx) hipLaunchKernelGGL((hash_bwd_coarse_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, gc, x01, dy2, tb2, dtable,
-                                   dx, n, dbg, ws, n_dev);
-        else hipLaunchKernelGGL((hash_bwd_coarse_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, gc, x01, dy2, tb2, dtable,
-                                dx, n, dbg, ws, n_dev);
-        rc = lse::check_launch("lse_hash_bwd (coarse levels)");
-        if (rc) return rc;
-        if (coarse_end == level_end) return LSE_OK;
-        g.l_begin = coarse_end;
-        g.dx_accumulate = 1;
+        if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, st, g, x01, dy2, tb2, dtable, dx,
+                                   n, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
+        else hipLaunchKernelGGL((hash_bwd_batched_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, st, g, x01, dy2, tb2, dtable, dx,
+                                n, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
+    } else {
+        if (dx) hipLaunchKernelGGL((hash_bwd_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy, tb, dtable, dx, n);
+        else hipLaunchKernelGGL((hash_bwd_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy, tb, dtable, dx, n);
     }
-#endif
-    // line-cache kernel: needs every level to start on a 64-B line (tcnn pads level sizes to 8 entries)
-    bool lines_ok = true;
-    for (int l = 0; l <= g.n_levels; ++l) lines_ok = lines_ok && (g.offsets[l] % 8 == 0);
-    LSE_REQUIRE(!n_dev || lines_ok, "lse_hash_bwd: a device-side count needs 64-byte aligned levels (the default kernel)");
-    if (impl == 2 && lines_ok) {     // per-wave sector cache with run ends of several levels batched into one pass
-        const int64_t blocks = ((n + 4 * 64 - 1) / (4 * 64) + 7) / 8 * 8;      // (four-wave development variants; chunk mapping: a multiple of 8)
-        LSE_REQUIRE(blocks < (1ll << 31), "lse_hash_bwd: grid too large");
-        const float2 *dy2 = reinterpret_cast<const float2 *>(dy);
-        const float2 *tb2 = reinterpret_cast<const float2 *>(tb);
-        // (workgroups of WAVES waves with SLOTS cache slots per wave; nothing in the kernel synchronises across waves)
-#define LSE_HASH_BWD_LAUNCH(SLOTS, WAVES)                                                                                              \
-        {                                                                                                                                 \
-            const int64_t bl = ((n + (WAVES) * 64 - 1) / ((WAVES) * 64) + 7) / 8 * 8;      /* (chunk mapping: a multiple of 8) */          \
-            LSE_REQUIRE(bl < (1ll << 31), "lse_hash_bwd: grid too large");                                                                \
-            if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true, SLOTS, 2, true, true, false, false, WAVES>), dim3((unsigned)bl),    \
-                                       dim3(64 * (WAVES)), 0, st, g, x01, dy2, tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe,       \
-                                       o.stage_max, ws, n_dev);                                                                          \
-            else hipLaunchKernelGGL((hash_bwd_batched_kernel<false, SLOTS, 2, true, true, false, false, WAVES>), dim3((unsigned)bl),      \
-                                    dim3(64 * (WAVES)), 0, st, g, x01, dy2, tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe,          \
-                                    o.stage_max, ws, n_dev);                                                                             \
-            return lse::check_launch("lse_hash_bwd");                                                                                     \
-        }
-#ifdef LSE_DEV_KNOBS
-        if (o.gran == 5) {      // the same with 256 slots: half the LDS, three workgroups per CU
-            if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true, 256, 2, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                       tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            else hipLaunchKernelGGL((hash_bwd_batched_kernel<false, 256, 2, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                    tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            return lse::check_launch("lse_hash_bwd");
-        }
-        if (o.gran == 7) {      // gran 6 with pair-aligned flush lists (a line is never split between two flush instructions)
-            if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true, 512, 2, true, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                       tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            else hipLaunchKernelGGL((hash_bwd_batched_kernel<false, 512, 2, true, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                    tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            return lse::check_launch("lse_hash_bwd");
-        }
-        if (o.gran == 6 && o.prefetch) {      // ... and the next level's operands fetched ahead of the cache pass
-            if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true, 512, 2, true, true, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                       tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            else hipLaunchKernelGGL((hash_bwd_batched_kernel<false, 512, 2, true, true, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                    tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            return lse::check_launch("lse_hash_bwd");
-        }
-#endif
-#ifdef LSE_DEV_KNOBS
-        // gran 6 with 320 slots: 52 KB of LDS per workgroup -> three workgroups (12 waves) per CU.  Round 5: more waves hide more
-        // latency, fewer slots collide more, and the two cancel where it matters -- headline 2.56 -> 2.58 ms, default configuration
-        // 1.49 -> 1.54, M-packed 3.12 -> 3.23; only the inside-box workload (long runs in the contracted shell, few sectors per
-        // sample) gains, 2.60 -> 2.47 (profiles/r05_hash_bwd_slots320.txt).  The production kernel sits where its CU-side bound
-        // (2 waves per SIMD) and the memory-side request bound (more requests at 3 waves per SIMD) meet.
-        if (o.gran == 8) {
-            if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true, 320, 2, true, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                       tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            else hipLaunchKernelGGL((hash_bwd_batched_kernel<false, 320, 2, true, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                    tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            return lse::check_launch("lse_hash_bwd");
-        }
-        // between the two: smaller workgroups hand the LDS out in finer portions.  gran 9: 384 slots, two waves per workgroup (30.5 KB)
-        // -> 10 waves per CU; gran 10: 448 slots, one wave per workgroup (17.6 KB) -> 9 waves per CU; gran 11: 384 slots, one wave; gran 12 / 13: 512 slots in workgroups of four (the shape until round 5) / two waves.
-        if (o.gran == 9) LSE_HASH_BWD_LAUNCH(384, 2)
-        if (o.gran == 10) LSE_HASH_BWD_LAUNCH(448, 1)
-        if (o.gran == 11) LSE_HASH_BWD_LAUNCH(384, 1)
-        if (o.gran == 12) LSE_HASH_BWD_LAUNCH(512, 4)
-        if (o.gran == 13) LSE_HASH_BWD_LAUNCH(512, 2)
-#endif
-        // THE production kernel: paired 32-byte sectors, second-generation flush, 512 slots per wave, ONE wave per workgroup.  A
-        // workgroup's LDS is released when its last wave retires, and waves differ in how many cache passes their samples need:
-        // in workgroups of four (until round 5) a CU held 20 KB per early finisher idle.  One wave per workgroup: samples in the
-        // contracted shell 2.53 -> 2.40 ms, headline, M-packed and the default configuration within +-1 %
-        // (profiles/r05_hash_bwd_workgroup_size.txt).
-        if (o.gran == 6) LSE_HASH_BWD_LAUNCH(512, 1)
-#undef LSE_HASH_BWD_LAUNCH
-#ifdef LSE_DEV_KNOBS
-        if (o.gran == 4) {      // 32-byte slots paired by 64-byte line, flush list in slot order
-            if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true, 512, 2, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                       tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            else hipLaunchKernelGGL((hash_bwd_batched_kernel<false, 512, 2, true>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                    tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-            return lse::check_launch("lse_hash_bwd");
-        }
-        if (dx) hipLaunchKernelGGL((hash_bwd_batched_kernel<true, 512, 2>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                   tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-        else hipLaunchKernelGGL((hash_bwd_batched_kernel<false, 512, 2>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2,
-                                tb2, dtable, dx, n, dbg, o.few_runs, o.second_probe, o.stage_max, ws, n_dev);
-        return lse::check_launch("lse_hash_bwd");
-#else
-        lse::set_error("lse_hash_bwd: opts.gran %d is a development variant", o.gran);     // (rejected above already)
-        return LSE_E_UNSUPPORTED;
-#endif
+    if (ws) {      // fold the replicas into the table gradient
+        const uint32_t n4 = (uint32_t)(rep_floats / 4);
+        hipLaunchKernelGGL(hash_bwd_reduce_replicas_kernel, dim3((n4 + 255) / 256), dim3(256), 0, st, ws, dtable, n4, o.replicas,
+                           (uint32_t)rep_floats);
     }
-#ifdef LSE_DEV_KNOBS
-    if (impl >= 1 && lines_ok) {
-        const int few_runs = o.few_runs, second_probe = o.second_probe, gran = o.gran;
-        const int64_t blocks = (n + 4 * 64 - 1) / (4 * 64);
-        LSE_REQUIRE(blocks < (1ll << 31), "lse_hash_bwd: grid too large");
-        const float2 *dy2 = reinterpret_cast<const float2 *>(dy);
-        const float2 *tb2 = reinterpret_cast<const float2 *>(tb);
-#define LSE_LAUNCH_CACHED(DX, SLOTS, ENTLOG2)                                                                          \
-    hipLaunchKernelGGL((hash_bwd_cached_kernel<DX, SLOTS, ENTLOG2>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy2, \
-                       tb2, dtable, dx, n, dbg, few_runs, second_probe)
-        if (gran != 3) {   // 512 slots of one 32-B sector (gran 4 = the pairing of impl 2: plain sectors here)
-            if (dx) LSE_LAUNCH_CACHED(true, 512, 2);
-            else LSE_LAUNCH_CACHED(false, 512, 2);
-        } else {           // 256 slots of one 64-B line
-            if (dx) LSE_LAUNCH_CACHED(true, 256, 3);
-            else LSE_LAUNCH_CACHED(false, 256, 3);
-        }
-#undef LSE_LAUNCH_CACHED
-        return lse::check_launch("lse_hash_bwd");
-    }
-#endif
-#define LSE_LAUNCH_BWD(R)                                                                                             \
-    do {                                                                                                              \
-        const int64_t blocks = (n + 4 * 4 * R - 1) / (4 * 4 * R);                                                     \
-        LSE_REQUIRE(blocks < (1ll << 31), "lse_hash_bwd: grid too large");                                            \
-        if (dx) hipLaunchKernelGGL((hash_bwd_kernel<true, R>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy, tb, \
-                                   dtable, dx, n, il_scale, dbg);                                                     \
-        else hipLaunchKernelGGL((hash_bwd_kernel<false, R>), dim3((unsigned)blocks), dim3(256), 0, st, g, x01, dy, tb,   \
-                                dtable, dx, n, il_scale, dbg);                                                        \
-    } while (0)
-#ifdef LSE_DEV_KNOBS
-    if (rounds == 64) LSE_LAUNCH_BWD(64);
-    else if (rounds == 16) LSE_LAUNCH_BWD(16);
-    else
-#endif
-    LSE_LAUNCH_BWD(32);
-#undef LSE_LAUNCH_BWD
     return lse::check_launch("lse_hash_bwd");
 }

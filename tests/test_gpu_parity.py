@@ -393,9 +393,9 @@ def _hash_bwd_ex(ops, meta, x, dy, table, with_dx=True, **opt_kw):
 def test_hash_bwd_metric_regime_every_kernel_variant_vs_oracle():
     """The regime bench.py times: 64 rays x 1024 CONSECUTIVE samples each (16 waves per ray, runs of many lanes per cell on
     the coarse levels, ~2 cells per step on the finest), L = 16, T = 2^19.  The default kernel (run scan, cross-row carry,
-    LDS sector cache, few-runs path, pair-lane collision atomics), its 64-B-line and second-probe variants and the
+    LDS sector cache, few-runs path, pair-lane collision atomics) under its staging / probing / few-runs / replica settings and the
     16-lanes-per-sample kernel are selected through lse_hash_bwd_ex's CALL ARGUMENTS in one process and all compared with
-    oracle/hashgrid.py, level by level."""
+    oracle/hashgrid.py, level by level; the selections of retired variants are refused by both libraries."""
     from oracle import hashgrid as ohg
     ops = _ops()
     meta_o = ohg.tcnn_grid_meta(n_levels=16, log2_hashmap_size=19)
@@ -410,35 +410,20 @@ def test_hash_bwd_metric_regime_every_kernel_variant_vs_oracle():
     dy = w.reshape(N, 16, 2).permute(1, 0, 2).contiguous().cuda()          # level-major, as the fused MLP hands it over
     xg, tg = x.cuda(), table.cuda()
     bounds = hash_level_bounds(meta)
-    variants = {"default": {}, "unpaired_sectors": {"gran": 2}, "paired_probe2": {"gran": 4, "second_probe": 2}, "stage_all": {"stage_max": 64}, "stage_none": {"stage_max": 0}, "batched_probe0": {"second_probe": 0}, "batched_probe1": {"second_probe": 1}, "batched_probe5": {"second_probe": 5},
-                "batched_no_few_runs": {"few_runs": 0}, "per_level_pass": {"impl": 1}, "line_cache": {"impl": 1, "gran": 3},
-                "second_probe": {"impl": 1, "second_probe": 1}, "no_few_runs": {"impl": 1, "few_runs": 0},
-                "lanes16": {"impl": 0}, "lanes16_r64": {"impl": 0, "rounds": 64},
-                # round 3: the cache-free high-occupancy kernel takes the levels below `coarse_levels` (a split of the level
-                # range between two launches; all of them = that kernel alone, incl. its multi-trip staging on the fine levels)
-                "coarse6": {"coarse_levels": 6}, "coarse9": {"coarse_levels": 9}, "coarse_all": {"coarse_levels": 16},
-                "coarse8_impl1": {"coarse_levels": 8, "impl": 1}, "coarse5_lanes16": {"coarse_levels": 5, "impl": 0},
+    variants = {"default": {}, "stage_all": {"stage_max": 64}, "stage_none": {"stage_max": 0}, "batched_probe0": {"second_probe": 0}, "batched_probe1": {"second_probe": 1}, "batched_probe5": {"second_probe": 5},
+                "batched_no_few_runs": {"few_runs": 0},
+                "lanes16": {"impl": 0},
                 # second-generation flush of the paired sector cache (transposed list, read-and-zero exchange, bulk key reset)
-                "flush2": {"gran": 6}, "flush2_coarse7": {"gran": 6, "coarse_levels": 7}, "flush2_stage_all": {"gran": 6, "stage_max": 64},
+                "flush2": {"gran": 6}, "flush2_stage_all": {"gran": 6, "stage_max": 64},
                 "flush2_no_few_runs": {"gran": 6, "few_runs": 0, "second_probe": 0},
-                # coarse-level replicas (default: 8 replicas of levels 0-3): off, more of them, every dense level, with the coarse kernel
+                # coarse-level replicas (default: 16 replicas of levels 0-3): off, more of them, every dense level
                 "no_replicas": {"replicas": 0}, "replicas8": {"replicas": 8}, "replicas32_levels6": {"replicas": 32, "replica_levels": 6},
-                "replicas_coarse_kernel": {"coarse_levels": 7, "replicas": 16, "replica_levels": 5},
                 "replicas_few_runs16": {"few_runs": 16, "replica_levels": 16, "replicas": 4},
-                # next level's dy / table operands fetched before the current level's cache pass
-                "prefetch": {"prefetch": 1}, "prefetch_no_few_runs": {"prefetch": 1, "few_runs": 0}, "prefetch_stage_all": {"prefetch": 1, "stage_max": 64},
-                "prefetch_coarse5": {"prefetch": 1, "coarse_levels": 5},
-                # pair-aligned flush lists
-                "few_runs8": {"few_runs": 8}, "dense_steps_thresholds": {"few_runs": 3, "stage_max": 56}, "round5_first_thresholds": {"few_runs": 6, "stage_max": 32}, "few_runs2_stage_all": {"few_runs": 2, "stage_max": 64}, "round4_thresholds": {"few_runs": 6, "stage_max": 16},
-                # 320 slots (52 KB of LDS per workgroup: three workgroups = 12 waves per CU; non-power-of-two slot arithmetic)
-                # the compute half of two levels issued together (development build)
-                "slots320": {"gran": 8}, "slots320_dense_steps": {"gran": 8, "few_runs": 6, "stage_max": 32}, "slots320_probe0": {"gran": 8, "second_probe": 0},
-                "slots320_stage_all_no_few_runs": {"gran": 8, "stage_max": 64, "few_runs": 0}, "slots320_no_replicas": {"gran": 8, "replicas": 0},
-                # the workgroup size sets the portions LDS is handed out in (production: 512 slots, ONE wave per workgroup):
-                # 384 slots x 2 waves (10 waves per CU), 448 x 1 (9), 384 x 1, 512 x 4 (the shape until round 5), 512 x 2
-                "slots384_wg2": {"gran": 9}, "slots384_wg2_dense_steps": {"gran": 9, "few_runs": 6, "stage_max": 32}, "slots384_wg2_stage_all_no_few_runs": {"gran": 9, "stage_max": 64, "few_runs": 0},
-                "slots448_wg1": {"gran": 10}, "slots448_wg1_probe0_stage_all": {"gran": 10, "second_probe": 0, "stage_max": 64}, "slots384_wg1": {"gran": 11}, "slots512_wg4": {"gran": 12}, "slots512_wg4_dense_steps": {"gran": 12, "few_runs": 6, "stage_max": 32}, "slots512_wg2": {"gran": 13},
-                "aligned_pairs": {"gran": 7}, "aligned_pairs_stage_all": {"gran": 7, "stage_max": 64}, "aligned_pairs_probe0": {"gran": 7, "second_probe": 0}}
+                "few_runs8": {"few_runs": 8}, "dense_steps_thresholds": {"few_runs": 3, "stage_max": 56}, "round5_first_thresholds": {"few_runs": 6, "stage_max": 32}, "few_runs2_stage_all": {"few_runs": 2, "stage_max": 64}, "round4_thresholds": {"few_runs": 6, "stage_max": 16}}
+    # selections of retired development variants (DESIGN_HISTORY.md): one cache pass per level, first-generation flush, 320 slots, the
+    # cache-free coarse-level kernel, operand prefetch, 64 rounds in the 16-lanes kernel
+    retired = {"per_level_pass": {"impl": 1}, "paired_flush1": {"gran": 4}, "slots320": {"gran": 8}, "coarse6": {"coarse_levels": 6},
+               "prefetch": {"prefetch": 1}, "lanes16_r64": {"impl": 0, "rounds": 64}}
     # floor() decisions of samples that sit within rounding of a cell face may differ between the two position formulas
     on_face = torch.zeros(N, dtype=torch.bool)
     for sc in meta.scales:
@@ -454,25 +439,20 @@ def test_hash_bwd_metric_regime_every_kernel_variant_vs_oracle():
         assert rel_l2(dt, tc.grad) < TOL_GRAD, name
         assert nmax_err(dx.cpu()[~on_face], xc.grad[~on_face]) < TOL_GRAD, name
 
-    # The library that ships holds the production kernels only (ABI 5): the batched sector-cache kernel with the second-generation
-    # flush (impl 2, gran 6) under any staging / probing / few-runs / replica setting, and the generic 16-lanes-per-sample kernel.
-    # Every other selection is a development variant: rejected there, held against the oracle in liblse_hip_dev.so.
-    shipped = lambda kw: (kw.get("impl", 2) == 0 or (kw.get("impl", 2) == 2 and kw.get("gran", 6) == 6 and not kw.get("prefetch"))) \
-        and not kw.get("coarse_levels") and kw.get("rounds", 32) == 32
-    n_shipped = 0
-    for name, kw in variants.items():
-        if shipped(kw):
-            check(name, kw)
-            n_shipped += 1
-        else:
+    # Both libraries hold the same two kernels: the batched sector-cache kernel (impl 2) under any staging / probing / few-runs /
+    # replica setting, and the generic 16-lanes-per-sample kernel.  Every other selection is a retired development variant.
+    def check_all(prefix):
+        for name, kw in variants.items():
+            check(prefix + name, kw)
+        for name, kw in retired.items():
             with pytest.raises(_lib.LseHipError, match="development variant"):
                 _hash_bwd_ex(ops, meta, xg, dy, tg, **kw)
-    assert n_shipped >= 16
+
+    assert len(variants) == 20 and len(retired) == 6
+    check_all("")
     assert _lib.dev_available(), "liblse_hip_dev.so is built by __graft_entry__.build() (make -C lsenerf_amd/csrc dev)"
     with _lib.dev_library():
-        for name, kw in variants.items():
-            check("dev:" + name, kw)
-
+        check_all("dev:")
 
 def test_hash_bwd_chunk_mapping_covers_every_sample_count():
     """The default hash backward hands workgroup b the chunk (b % 8) * ceil(B / 8) + b / 8 of the B chunks the samples fill (every
@@ -1189,33 +1169,24 @@ def test_mlp_fused_density_head_and_compact_output():
     assert nmax_err(xhg.grad, xhc.grad) < TOL_GRAD
 
 
-def test_hash_fwd_lds_resident_variant_is_bit_identical():
-    """Development knob hash_fwd_lds_levels (the "LDS-staged trilinear interpolation" BASELINE.json's north_star names, kept as the A/B partner
-    of the L2-resident level-major schedule, profiles/r04_hash_fwd_lds_ab.txt): the k coarsest levels are gathered from an LDS copy of
-    their table.  Same multiply-adds in the same order -> bit-identical features, for ragged counts, a device-side count below the
-    capacity, and a grid whose level 1 does not fit the LDS (the variant then stops at level 0)."""
+def test_hash_fwd_shipped_and_development_builds_are_bit_identical():
+    """The library that ships and the development build's default schedule compute the same bits in the hash forward, for ragged
+    counts, a device-side count below the capacity, a small grid and a non-default geometry."""
     from lsenerf_amd import _lib, ops
     g = torch.Generator().manual_seed(5)
-    with _lib.dev_library() as dev:        # a knob of the development build (csrc/dev_knobs.h); restored when the block ends
-        for meta, n in ((ops.make_grid_meta(), 200003), (ops.make_grid_meta(n_levels=4, log2_hashmap_size=12), 777),
-                        (ops.make_grid_meta(base_resolution=24, max_res=1024), 65537)):
-            table = ((torch.rand(meta.n_params, generator=g) * 2 - 1) * 1e-2).cuda()
-            x = torch.rand(n, 3, generator=g).cuda()
-            x[: n // 2] = (x[:1] + 1e-3 * torch.arange(n // 2, device="cuda")[:, None]).clamp(0, 1)      # ray-like: neighbours share cells
-            dev.set_option("hash_fwd_lds_levels", 0)
-            ref = ops.hash_encode(x, table, meta)
-            n_dev = torch.tensor([n - 1234 if n > 2000 else n - 7], dtype=torch.int64, device="cuda")
-            ref_dev = ops.hash_encode(x, table, meta, n_dev=n_dev)
-            for k in (1, 2, 5):
-                dev.set_option("hash_fwd_lds_levels", k)
-                assert torch.equal(ops.hash_encode(x, table, meta), ref), (meta.n_levels, n, k)
-                got = ops.hash_encode(x, table, meta, n_dev=n_dev)
-                m = int(n_dev)
-                assert torch.equal(got[:, :m], ref_dev[:, :m]) and torch.equal(got[:, :m], ref[:, :m]), (meta.n_levels, n, k)
-            dev.set_option("hash_fwd_lds_levels", 0)
-    # ... and the library that ships computes the same bits as the development build's default schedule
-    assert torch.equal(ops.hash_encode(x, table, meta), ref)
-
+    for meta, n in ((ops.make_grid_meta(), 200003), (ops.make_grid_meta(n_levels=4, log2_hashmap_size=12), 777),
+                    (ops.make_grid_meta(base_resolution=24, max_res=1024), 65537)):
+        table = ((torch.rand(meta.n_params, generator=g) * 2 - 1) * 1e-2).cuda()
+        x = torch.rand(n, 3, generator=g).cuda()
+        x[: n // 2] = (x[:1] + 1e-3 * torch.arange(n // 2, device="cuda")[:, None]).clamp(0, 1)      # ray-like: neighbours share cells
+        n_dev = torch.tensor([n - 1234 if n > 2000 else n - 7], dtype=torch.int64, device="cuda")
+        m = int(n_dev)
+        ref = ops.hash_encode(x, table, meta)
+        ref_dev = ops.hash_encode(x, table, meta, n_dev=n_dev)
+        assert torch.equal(ref_dev[:, :m], ref[:, :m]), (meta.n_levels, n)
+        with _lib.dev_library():
+            assert torch.equal(ops.hash_encode(x, table, meta), ref), (meta.n_levels, n)
+            assert torch.equal(ops.hash_encode(x, table, meta, n_dev=n_dev)[:, :m], ref_dev[:, :m]), (meta.n_levels, n)
 
 @pytest.mark.parametrize("shape", ["head", "base"])
 def test_mlp_full_size_properties(shape):

@@ -67,7 +67,7 @@ def test_dev_knobs_and_hash_bwd_opts_without_gpu():
     assert (o.impl, o.gran, o.few_runs, o.second_probe, o.rounds, o.dbg, o.stage_max, o.coarse_levels) == (2, 6, 8, 3, 32, 0, 48, 0)
     assert (o.replicas, o.replica_levels, o.prefetch, o.workspace) == (16, 4, 0, None)
     with _lib.dev_library() as dev:
-        assert _lib.get_option("hash_fwd_mapping") == 4 and _lib.get_option("mlp_bwd_cfg") == 28 and _lib.get_option("traverse_vec") == 1
+        assert _lib.get_option("compact_features_groups") == 4 and _lib.get_option("mlp_bwd_cfg") == 28 and _lib.get_option("traverse_vec") == 1
         dev.set_option("mlp_fwd_cfg", 44)
         assert _lib.get_option("mlp_fwd_cfg") == 44
         dev.set_option("hash_bwd_few_runs", 9)
@@ -77,7 +77,7 @@ def test_dev_knobs_and_hash_bwd_opts_without_gpu():
     with _lib.dev_library():
         assert _lib.get_option("mlp_fwd_cfg") == 28 and _lib.get_option("hash_bwd_few_runs") == 8      # restored on exit
     assert _lib.hash_bwd_default_opts().few_runs == 8
-    # invalid kernel selections are rejected before anything is launched; development variants are not in the shipped library
+    # invalid kernel selections are rejected before anything is launched; the retired development variants are in neither library
     d = _lib.GridDesc()
     d.n_levels, d.n_features = 1, 2
     d.offsets[0], d.offsets[1], d.scales[0], d.resolutions[0] = 0, 8, 1.0, 2
@@ -87,6 +87,19 @@ def test_dev_knobs_and_hash_bwd_opts_without_gpu():
     o.impl = 1
     with pytest.raises(_lib.LseHipError, match="development variant"):
         _lib.call("lse_hash_bwd_ex", ctypes.byref(d), None, None, None, None, None, 0, 0, 1, 0, None, ctypes.byref(o), None)
+    # every reserved field: a value other than the default's is a retired variant, in the shipped library and in the development build
+    retired = [("impl", 1), ("gran", 2), ("gran", 4), ("gran", 8), ("prefetch", 1), ("coarse_levels", 6), ("rounds", 16), ("rounds", 64),
+               ("interleave_from_scale", 64.0), ("dbg", 1)]
+
+    def rejects_all():
+        for field, value in retired:
+            r = _lib.hash_bwd_default_opts()
+            setattr(r, field, value)
+            with pytest.raises(_lib.LseHipError, match="development variant"):
+                _lib.call("lse_hash_bwd_ex", ctypes.byref(d), None, None, None, None, None, 0, 0, 1, 0, None, ctypes.byref(r), None)
+    rejects_all()
+    with _lib.dev_library():
+        rejects_all()
 
 
 def test_argument_counts_match_header():
