@@ -80,11 +80,20 @@ typedef struct lse_mlp_desc {
      * bf16-piece kernels (f32 operands cut into three bf16 pieces, six piece products per multiply on the bf16 matrix cores, f32
      * accumulate: the f32 error bound, csrc/mlp_x6.h); LSE_MLP_ARITH_F32_MFMA = v_mfma_f32_16x16x4_f32 (what every other shape
      * runs on).  The two routes differ in the last bits, both within f32 rounding of the exact result.  The backward's route
-     * follows act_tiled (3 = bf16 pieces). */
+     * follows act_tiled (3 = bf16 pieces).
+     * LSE_MLP_ARITH_BF16X3 / LSE_MLP_ARITH_BF16X1: reduced-piece INFERENCE forward of the same two shapes (lse_mlp_fwd with
+     * nothing saved -- act == NULL, or act_tiled == 3 whose act is ignored -- and lse_mlp_fwd_pair with the same route in both
+     * descriptors; anything else, every backward included, is LSE_E_UNSUPPORTED).  With NP = 2 (BF16X3) or 1 (BF16X1) pieces per
+     * operand, cut by round-to-nearest-even (p0 = bf16_rn(x), p1 = bf16_rn(x - p0), weights and activations alike), a layer's
+     * pre-activation is the row bias (f32, uncut) plus exactly the piece products a_i * b_j with i + j < NP -- hi*hi + hi*mid +
+     * mid*hi, or hi*hi alone -- each exact in f32 and accumulated in f32 on the matrix core.  Activations, density head, stores,
+     * n_dev and tails are those of LSE_MLP_ARITH_AUTO.  Relative error of a multiply: 2^-16 (BF16X3), 2^-8 (BF16X1). */
     int32_t arith;
 } lse_mlp_desc;
 #define LSE_MLP_ARITH_AUTO 0
 #define LSE_MLP_ARITH_F32_MFMA 1
+#define LSE_MLP_ARITH_BF16X3 2
+#define LSE_MLP_ARITH_BF16X1 3
 
 /* ---- misc -------------------------------------------------------------------------------------------- */
 int lse_abi_version(void);
@@ -286,8 +295,9 @@ int lse_mlp_fwd(const lse_mlp_desc *desc, const float *params, const float *in, 
  *     lse_mlp_fwd(head_desc, head_params, h, row_bias, row_bias_idx, out, out_cols, NULL, 3, NULL, NULL, 0, n, n_dev, stream);
  * Shapes: the recompute-all production pair only -- base 32 -> 64 -> 16 (one hidden layer, level-major or row-major input, no
  * output activation), head 16 -> 64 -> 64 -> 16 (row-major, first-layer view w0_ld / w0_col / w0_mask_col0 as in lse_mlp_fwd),
- * both LSE_MLP_ARITH_AUTO; anything else is LSE_E_UNSUPPORTED (call lse_mlp_fwd twice).  Nothing is saved for the backward
- * (lse_mlp_bwd with act_tiled = 3 recomputes).  selector, row_bias, row_bias_idx nullable as in lse_mlp_fwd. */
+ * both LSE_MLP_ARITH_AUTO, or both the same reduced-piece route (the bitwise equality to two lse_mlp_fwd calls holds per
+ * route); anything else is LSE_E_UNSUPPORTED (call lse_mlp_fwd twice).  Nothing is saved for the backward
+ * (lse_mlp_bwd with act_tiled = 3 recomputes; LSE_MLP_ARITH_AUTO only).  selector, row_bias, row_bias_idx nullable as in lse_mlp_fwd. */
 int lse_mlp_fwd_pair(const lse_mlp_desc *base_desc, const float *base_params, const float *y, const uint8_t *selector,
                      float density_scale, const lse_mlp_desc *head_desc, const float *head_params, const float *row_bias,
                      const int32_t *row_bias_idx, float *h, float *sigma, float *out, int32_t out_cols, int64_t n,

@@ -21,6 +21,7 @@ LSE_IN_ROWMAJOR, LSE_IN_LEVELMAJOR = 0, 1
 LSE_ACT_NONE, LSE_ACT_SIGMOID = 0, 1
 LSE_ABI_VERSION = 6
 LSE_MLP_ARITH_AUTO, LSE_MLP_ARITH_F32_MFMA = 0, 1
+LSE_MLP_ARITH_BF16X3, LSE_MLP_ARITH_BF16X1 = 2, 3      # reduced-piece inference forward (include/lse_hip.h: lse_mlp_desc.arith)
 LSE_TRAVERSE_FMA_SETUP = 1
 LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
 LSE_PREP_EVENT_STATS = 1

@@ -1390,8 +1390,20 @@ int check_desc(const lse_mlp_desc *d, const char *who)
     LSE_REQUIRE(d->w0_ld == 0 || d->w0_ld >= d->w0_col + d->n_in, "%s: first-layer view [%d, %d) exceeds its leading dimension %d",
                 who, d->w0_col, d->w0_col + d->n_in, d->w0_ld);
     LSE_REQUIRE(d->w0_col >= 0 && (d->w0_ld != 0 || d->w0_col == 0), "%s: w0_col needs w0_ld", who);
-    LSE_REQUIRE(d->arith == LSE_MLP_ARITH_AUTO || d->arith == LSE_MLP_ARITH_F32_MFMA, "%s: bad arith", who);
+    LSE_REQUIRE(d->arith == LSE_MLP_ARITH_AUTO || d->arith == LSE_MLP_ARITH_F32_MFMA || d->arith == LSE_MLP_ARITH_BF16X3 ||
+                    d->arith == LSE_MLP_ARITH_BF16X1,
+                "%s: bad arith", who);
     return LSE_OK;
+}
+
+// the reduced-piece routes (bf16x3 / bf16x1, mlp_x6.h): inference forward only
+bool reduced_arith(int arith) { return arith == LSE_MLP_ARITH_BF16X3 || arith == LSE_MLP_ARITH_BF16X1; }
+int refuse_reduced(const lse_mlp_desc *d, const char *who)
+{
+    if (!reduced_arith(d->arith)) return LSE_OK;
+    lse::set_error("%s: the reduced-piece routes (LSE_MLP_ARITH_BF16X3 / _BF16X1) are built for lse_mlp_fwd / lse_mlp_fwd_pair with "
+                   "nothing saved only: a backward runs in bf16x6 (LSE_MLP_ARITH_AUTO)", who);
+    return LSE_E_UNSUPPORTED;
 }
 
 void fill_view(MlpArgs &a, const lse_mlp_desc *d)
@@ -1414,9 +1426,38 @@ int launch_fwd_cfg(const MlpArgs &a, hipStream_t st)
     return lse::check_launch("lse_mlp_fwd");
 }
 
+// grid of the reduced routes' forwards, as for bf16x6: 8 tiles of 32 samples per workgroup, at most the resident workgroups of 256 CUs
+int x6_fwd_blocks(int64_t n)
+{
+    const int64_t tiles = (n + 31) / 32;
+    return (int)std::min<int64_t>((tiles + 7) / 8, 256 * kX6FwdWorkgroupsPerCu);
+}
+
+template <int KIN, int NHL, int INL, int NP>
+int launch_fwd3_reduced(MlpArgs a, hipStream_t st)
+{
+    a.act = nullptr;      // nothing is saved (act_tiled = 3: `act` is ignored)
+    hipLaunchKernelGGL((mlp_fwd3_kernel<KIN, NHL, INL, NP>), dim3(x6_fwd_blocks(a.n)), dim3(512),
+                       (X6Fwd<KIN, NHL, INL, NP>::lds_bytes), st, a, false);
+    return lse::check_launch("lse_mlp_fwd");
+}
+
 template <int KIN, int WIDTH, int NHL, int INL>
 int launch_fwd(const MlpArgs &a, hipStream_t st)
 {
+    if (reduced_arith(a.arith)) {
+        if constexpr (x6_recompute_shape(KIN, WIDTH, NHL, INL)) {
+            if (a.act == nullptr || a.act_tiled == 3) {
+                if (a.arith == LSE_MLP_ARITH_BF16X3) return launch_fwd3_reduced<KIN, NHL, INL, 2>(a, st);
+                return launch_fwd3_reduced<KIN, NHL, INL, 1>(a, st);
+            }
+        }
+        lse::set_error("lse_mlp_fwd: the reduced-piece routes (LSE_MLP_ARITH_BF16X3 / _BF16X1) serve the 16->64->64->16 row-major "
+                       "and 32->64->16 shapes with nothing saved (act == NULL or act_tiled == 3); got n_in=%d width=%d "
+                       "n_hidden_layers=%d in_layout=%d act=%s act_tiled=%d",
+                       KIN, WIDTH, NHL, INL, a.act ? "set" : "NULL", a.act_tiled);
+        return LSE_E_UNSUPPORTED;
+    }
     const int cfg = (int)lse::option("mlp_fwd_cfg");   // CT*10 + NW
     if constexpr (WIDTH == 64 && ((KIN == 16 && INL == LSE_IN_ROWMAJOR) || KIN == 32)) {
         // third generation: f32-equivalent arithmetic on the bf16 matrix cores (mlp_x6.h)
@@ -1674,16 +1715,19 @@ extern "C" int lse_mlp_fwd_pair(const lse_mlp_desc *base_desc, const float *base
     if (rc) return rc;
     LSE_REQUIRE(n >= 0, "lse_mlp_fwd_pair: n < 0");
     LSE_REQUIRE(out_cols == 16 || out_cols == 4, "lse_mlp_fwd_pair: out_cols must be 16 or 4");
+    const int arith = base_desc->arith;      // one route for both networks: bf16x6 or one of the reduced-piece routes
+    const bool arith_ok = (arith == LSE_MLP_ARITH_AUTO || reduced_arith(arith)) && head_desc->arith == arith;
     const bool base_ok = base_desc->n_in == 32 && base_desc->width == 64 && base_desc->n_hidden_layers == 1 &&
-                         base_desc->out_activation == LSE_ACT_NONE && base_desc->arith == LSE_MLP_ARITH_AUTO;
+                         base_desc->out_activation == LSE_ACT_NONE;
     const bool head_ok = head_desc->n_in == 16 && head_desc->width == 64 && head_desc->n_hidden_layers == 2 &&
-                         head_desc->in_layout == LSE_IN_ROWMAJOR && head_desc->arith == LSE_MLP_ARITH_AUTO;
-    if (!base_ok || !head_ok) {
+                         head_desc->in_layout == LSE_IN_ROWMAJOR;
+    if (!base_ok || !head_ok || !arith_ok) {
         lse::set_error("lse_mlp_fwd_pair: built for the 32->64->16 base (no output activation) and the 16->64->64->16 row-major head "
-                       "in bf16x6 arithmetic only (got base n_in=%d width=%d n_hidden_layers=%d, head n_in=%d width=%d "
-                       "n_hidden_layers=%d in_layout=%d): call lse_mlp_fwd twice",
-                       base_desc->n_in, base_desc->width, base_desc->n_hidden_layers, head_desc->n_in, head_desc->width,
-                       head_desc->n_hidden_layers, head_desc->in_layout);
+                       "in bf16x6 arithmetic or in the same reduced-piece route for both (got base n_in=%d width=%d "
+                       "n_hidden_layers=%d arith=%d, head n_in=%d width=%d n_hidden_layers=%d in_layout=%d arith=%d): call "
+                       "lse_mlp_fwd twice",
+                       base_desc->n_in, base_desc->width, base_desc->n_hidden_layers, base_desc->arith, head_desc->n_in,
+                       head_desc->width, head_desc->n_hidden_layers, head_desc->in_layout, head_desc->arith);
         return LSE_E_UNSUPPORTED;
     }
     if (n == 0) return LSE_OK;
@@ -1699,6 +1743,20 @@ extern "C" int lse_mlp_fwd_pair(const lse_mlp_desc *base_desc, const float *base
     hipStream_t st = lse::as_stream(stream);
     const int64_t tiles = (n + 31) / 32;
     const int blocks = (int)std::min<int64_t>((tiles + 7) / 8, 512);      // the grid of mlp_fwd3_kernel: two resident workgroups per CU
+    if (reduced_arith(arith)) {
+#define LSE_PAIR_REDUCED(INL, NP)                                                                                              \
+    hipLaunchKernelGGL((mlp_fwd_pair_kernel<INL, NP>), dim3(x6_fwd_blocks(n)), dim3(512), (X6FwdPair<INL, NP>::lds_bytes), st, a, b)
+        const bool lm = base_desc->in_layout == LSE_IN_LEVELMAJOR;
+        if (arith == LSE_MLP_ARITH_BF16X3) {
+            if (lm) LSE_PAIR_REDUCED(LSE_IN_LEVELMAJOR, 2);
+            else LSE_PAIR_REDUCED(LSE_IN_ROWMAJOR, 2);
+        } else {
+            if (lm) LSE_PAIR_REDUCED(LSE_IN_LEVELMAJOR, 1);
+            else LSE_PAIR_REDUCED(LSE_IN_ROWMAJOR, 1);
+        }
+#undef LSE_PAIR_REDUCED
+        return lse::check_launch("lse_mlp_fwd_pair");
+    }
     if (base_desc->in_layout == LSE_IN_LEVELMAJOR)
         hipLaunchKernelGGL((mlp_fwd_pair_kernel<LSE_IN_LEVELMAJOR>), dim3(blocks), dim3(512),
                            X6FwdPair<LSE_IN_LEVELMAJOR>::lds_bytes, st, a, b);
@@ -1715,6 +1773,8 @@ extern "C" int lse_mlp_bwd(const lse_mlp_desc *desc, const float *params, const 
                            float *d_row_bias, int64_t n, const int64_t *n_dev, lse_stream_t stream)
 {
     int rc = check_desc(desc, "lse_mlp_bwd");
+    if (rc) return rc;
+    rc = refuse_reduced(desc, "lse_mlp_bwd");
     if (rc) return rc;
     LSE_REQUIRE(n >= 0, "lse_mlp_bwd: n < 0");
     if (n == 0) return LSE_OK;
@@ -1794,6 +1854,8 @@ extern "C" int lse_mlp_wgrad(const lse_mlp_desc *desc, const float *in, const fl
                              const float *d_out_pre, float *d_params, int64_t n, lse_stream_t stream)
 {
     int rc = check_desc(desc, "lse_mlp_wgrad");
+    if (rc) return rc;
+    rc = refuse_reduced(desc, "lse_mlp_wgrad");
     if (rc) return rc;
     LSE_REQUIRE(n >= 0, "lse_mlp_wgrad: n < 0");
     if (n == 0) return LSE_OK;

@@ -44,6 +44,22 @@ __device__ __forceinline__ uint32_t piece_of(float x, int p)
     return b >> 16;
 }
 
+// Reduced-piece routes (NP = 2 "bf16x3", NP = 1 "bf16x1": the inference forward only) keep the products a_i b_j with i + j < NP.
+// Their pieces are cut by round-to-nearest-even, weights as well as activations: p0 = bf16_rn(x), p1 = bf16_rn(x - p0) (the
+// subtraction is exact in f32).  Truncation is harmless only while all three pieces are kept -- the NP = 3 images keep piece_of.
+__device__ __forceinline__ uint32_t cvt_pk(float a, float b);
+__device__ __forceinline__ uint32_t piece_rn(float x, int p)
+{
+    uint32_t b = cvt_pk(x, 0.f) & 0xffffu;
+    for (int i = 0; i < p; ++i) {
+        x = x - __uint_as_float(b << 16);
+        b = cvt_pk(x, 0.f) & 0xffffu;
+    }
+    return b;
+}
+template <int NP>
+__device__ __forceinline__ uint32_t piece_np(float x, int p) { return NP == 3 ? piece_of(x, p) : piece_rn(x, p); }
+
 // ---- cutting on the matrix core.  Cutting on the vector ALU (and / subtract / permute) costs 5.5 instructions per value and
 // made the kernels bound by exactly those instructions.  Instead:  hi = bf16(x) (v_cvt_pk_bf16_f32, two values per instruction, round to nearest), then
 // the REMAINDER x - hi is produced by one MFMA with the negated identity as the A operand and the packed hi pieces as B
@@ -86,23 +102,31 @@ struct NegI {
     __device__ __forceinline__ u32x4 operator[](int b) const { return p[64 * b]; }
 };
 
-// c0, c1 -> pieces o[hi, mid, lo]; c0 / c1 are consumed (they end as the third remainders)
-template <typename NI>
+// c0, c1 -> pieces o[hi, mid, lo]; c0 / c1 are consumed (they end as the third remainders).  NP < 3: the first NP pieces only, one
+// remainder stage (NP = 2) or none (NP = 1: nI is never read)
+template <int NP = 3, typename NI>
 __device__ __forceinline__ void split_pair(f32x4 c0, f32x4 c1, const NI &nI, u32x4 (&o)[3])
 {
     o[0] = (u32x4){cvt_pk(c0[0], c0[1]), cvt_pk(c0[2], c0[3]), cvt_pk(c1[0], c1[1]), cvt_pk(c1[2], c1[3])};
+    if constexpr (NP == 1) return;
     c0 = LSE_MFMA_BF(nI[0], o[0], c0);
     c1 = LSE_MFMA_BF(nI[1], o[0], c1);
     o[1] = (u32x4){cvt_pk(c0[0], c0[1]), cvt_pk(c0[2], c0[3]), cvt_pk(c1[0], c1[1]), cvt_pk(c1[2], c1[3])};
+    if constexpr (NP == 2) return;
     c0 = LSE_MFMA_BF(nI[0], o[1], c0);
     c1 = LSE_MFMA_BF(nI[1], o[1], c1);
     o[2] = (u32x4){cvt_pk(c0[0], c0[1]), cvt_pk(c0[2], c0[3]), cvt_pk(c1[0], c1[1]), cvt_pk(c1[2], c1[3])};
 }
 
 // four values per lane (k = 16 operands): pieces as 2-register halves
-template <typename NI>
+template <int NP = 3, typename NI>
 __device__ __forceinline__ void split_half(f32x4 c0, const NI &nI, uint32_t (&hi)[2], uint32_t (&mid)[2], uint32_t (&lo)[2])
 {
+    if constexpr (NP == 1) {          // no remainder: nI is never read
+        hi[0] = cvt_pk(c0[0], c0[1]);
+        hi[1] = cvt_pk(c0[2], c0[3]);
+        return;
+    }
     // the remainder products have k = 16: the two-register v_mfma_f32_16x16x16_bf16 takes the same 16 cycles as the k = 32 form
     // (tools/micro/mfma_rate.hip) and needs no zero upper half (two v_mov per product in the k = 32 form).  Its A operand is the
     // first half of "minus identity" variant 0: lane (row i, group q) holds k = 4q .. 4q+3 -> -1 at k = i.
@@ -113,6 +137,7 @@ __device__ __forceinline__ void split_half(f32x4 c0, const NI &nI, uint32_t (&hi
     c0 = LSE_MFMA_BF16K(n2, ((u32x2){hi[0], hi[1]}), c0);
     mid[0] = cvt_pk(c0[0], c0[1]);
     mid[1] = cvt_pk(c0[2], c0[3]);
+    if constexpr (NP == 2) return;
     c0 = LSE_MFMA_BF16K(n2, ((u32x2){mid[0], mid[1]}), c0);
     lo[0] = cvt_pk(c0[0], c0[1]);
     lo[1] = cvt_pk(c0[2], c0[3]);
@@ -128,8 +153,8 @@ struct PiecesB {
 };
 
 // acc[rb][ct] += W[rows 16rb.., :] * X for CT column tiles at once (the A pieces are read once); img = LDS image
-// [piece][rb][slab][64 lanes] of u32x4
-template <int RB, int S, int CT>
+// [piece][rb][slab][64 lanes] of u32x4 with NP pieces.  NP = 2: the three products hi*hi, hi*mid, mid*hi; NP = 1: hi*hi.
+template <int RB, int S, int CT, int NP = 3>
 __device__ __forceinline__ void layer_x6_ct(f32x4 (&acc)[RB][CT], const u32x4 *img, const PiecesB<2 * S> (&x)[CT], int lane)
 {
 #pragma unroll
@@ -137,6 +162,19 @@ __device__ __forceinline__ void layer_x6_ct(f32x4 (&acc)[RB][CT], const u32x4 *i
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
             const u32x4 ah = img[((0 * RB + rb) * S + s) * 64 + lane];
+            if constexpr (NP < 3) {       // smallest products first, as in the six-product order below
+                if constexpr (NP == 2) {
+                    const u32x4 am2 = img[((1 * RB + rb) * S + s) * 64 + lane];
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) acc[rb][ct] = LSE_MFMA_BF(am2, x[ct].p[s][0], acc[rb][ct]);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) acc[rb][ct] = LSE_MFMA_BF(ah, x[ct].p[s][1], acc[rb][ct]);
+                }
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) acc[rb][ct] = LSE_MFMA_BF(ah, x[ct].p[s][0], acc[rb][ct]);
+                __builtin_amdgcn_sched_barrier(0);
+                continue;
+            }
             const u32x4 am = img[((1 * RB + rb) * S + s) * 64 + lane];
             const u32x4 al = img[((2 * RB + rb) * S + s) * 64 + lane];
 #pragma unroll
@@ -165,11 +203,25 @@ struct PiecesB16 {
     u32x4 c[3];
 };
 
-template <typename NI>
+// Reduced routes (the products with i + j < NP):
+//   NP = 2, two MFMAs per row block:  k = 32  A = (hi | hi)  B = (hi | mid)   W_hi x_hi + W_hi x_mid   share one instruction,
+//                                     k = 16  A = mid        B = hi           W_mid x_hi               has its own;
+//           image [rb][lane] of u32x4 (hi | hi), then [rb][lane] of u32x2 (mid).  B: c[0] = (hi | mid), c[1] words 0..1 = hi.
+//   NP = 1, one k = 16 MFMA per row block: image [rb][lane] of u32x2 (hi), B = c[0] words 0..1.
+template <int NP = 3, typename NI>
 __device__ __forceinline__ void split_in16(const f32x4 v, const NI &nI, PiecesB16 &o)
 {
     uint32_t h[2], m[2], l[2];
-    split_half(v, nI, h, m, l);
+    split_half<NP>(v, nI, h, m, l);
+    if constexpr (NP == 1) {
+        o.c[0] = (u32x4){h[0], h[1], 0u, 0u};
+        return;
+    }
+    if constexpr (NP == 2) {
+        o.c[0] = (u32x4){h[0], h[1], m[0], m[1]};
+        o.c[1] = (u32x4){h[0], h[1], 0u, 0u};
+        return;
+    }
     o.c[0] = (u32x4){h[0], h[1], m[0], m[1]};
     o.c[1] = (u32x4){h[0], h[1], h[0], h[1]};
     o.c[2] = (u32x4){l[0], l[1], m[0], m[1]};
@@ -180,11 +232,29 @@ __device__ __forceinline__ constexpr int combo_piece(int combo, int half)
     return combo == 0 ? 0 : combo == 1 ? (half ? 2 : 1) : (half ? 1 : 0);
 }
 
-template <int RB, int CT>
+template <int RB, int CT, int NP = 3>
 __device__ __forceinline__ void layer16_x6_ct(f32x4 (&acc)[RB][CT], const u32x4 *img, const PiecesB16 (&x)[CT], int lane)
 {
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
+        if constexpr (NP < 3) {
+            const u32x2 *img2 = reinterpret_cast<const u32x2 *>(img + (NP == 2 ? RB * 64 : 0));       // the k = 16 operands
+            const u32x2 ak = img2[rb * 64 + lane];
+            if constexpr (NP == 2) {
+                const u32x4 ahh = img[rb * 64 + lane];
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+                    acc[rb][ct] = LSE_MFMA_BF16K(ak, ((u32x2){x[ct].c[1][0], x[ct].c[1][1]}), acc[rb][ct]);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) acc[rb][ct] = LSE_MFMA_BF(ahh, x[ct].c[0], acc[rb][ct]);
+            } else {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+                    acc[rb][ct] = LSE_MFMA_BF16K(ak, ((u32x2){x[ct].c[0][0], x[ct].c[0][1]}), acc[rb][ct]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            continue;
+        }
         const u32x4 a0 = img[(0 * RB + rb) * 64 + lane];
         const u32x4 a1 = img[(1 * RB + rb) * 64 + lane];
         const u32x4 a2 = img[(2 * RB + rb) * 64 + lane];
@@ -200,33 +270,33 @@ __device__ __forceinline__ void layer16_x6_ct(f32x4 (&acc)[RB][CT], const u32x4 
 
 // ---- weight images -------------------------------------------------------------------------------------------------
 // chained layer: W [rows x 64] row-major with leading dimension ld; image [piece][rb][slab][lane] (u32x4 = 8 bf16 slots)
-template <int RB, int S>
+template <int RB, int S, int NP = 3>
 __device__ __forceinline__ void stage_chain_image(u32x4 *img, const float *W, int ld, int rows_real, int nthreads)
 {
     uint32_t *w32 = reinterpret_cast<uint32_t *>(img);
-    for (int e = threadIdx.x; e < 3 * RB * S * 64 * 4; e += nthreads) {
+    for (int e = threadIdx.x; e < NP * RB * S * 64 * 4; e += nthreads) {
         const int word = e & 3, ln = (e >> 2) & 63, rest = e >> 8;
         const int s = rest % S, rb = (rest / S) % RB, p = rest / (S * RB);
         const int i = ln & 15, q = ln >> 4, row = 16 * rb + i;
         const float v0 = row < rows_real ? W[row * ld + kslot_chain(s, q, 2 * word)] : 0.f;
         const float v1 = row < rows_real ? W[row * ld + kslot_chain(s, q, 2 * word + 1)] : 0.f;
-        w32[e] = piece_of(v0, p) | (piece_of(v1, p) << 16);
+        w32[e] = piece_np<NP>(v0, p) | (piece_np<NP>(v1, p) << 16);
     }
 }
 
 // level-major / row-major 32-input first layer: slot t of lane q is input column 8q + t; image [piece][rb][lane]
-template <int RB>
+template <int RB, int NP = 3>
 __device__ __forceinline__ void stage_in32_image(u32x4 *img, const float *W, int ld, int mask0, int nthreads)
 {
     uint32_t *w32 = reinterpret_cast<uint32_t *>(img);
-    for (int e = threadIdx.x; e < 3 * RB * 64 * 4; e += nthreads) {
+    for (int e = threadIdx.x; e < NP * RB * 64 * 4; e += nthreads) {
         const int word = e & 3, ln = (e >> 2) & 63, rest = e >> 8;
         const int rb = rest % RB, p = rest / RB;
         const int i = ln & 15, q = ln >> 4, row = 16 * rb + i;
         const int c0 = 8 * q + 2 * word, c1 = c0 + 1;
         const float v0 = (mask0 && c0 == 0) ? 0.f : W[row * ld + c0];
         const float v1 = W[row * ld + c1];
-        w32[e] = piece_of(v0, p) | (piece_of(v1, p) << 16);
+        w32[e] = piece_np<NP>(v0, p) | (piece_np<NP>(v1, p) << 16);
     }
 }
 
@@ -244,6 +314,27 @@ __device__ __forceinline__ void stage_in16_image(u32x4 *img, const float *W, int
         const float v0 = (mask0 && c0 == 0) ? 0.f : W[row * ld + c0];
         const float v1 = W[row * ld + c1];
         w32[e] = piece_of(v0, p) | (piece_of(v1, p) << 16);
+    }
+}
+
+// 16-input first layer of the reduced routes (layouts: see split_in16): NP = 2 [rb][lane] u32x4 (hi | hi) then [rb][lane] u32x2
+// (mid); NP = 1 [rb][lane] u32x2 (hi).  k-slot t of lane q of a k = 16 operand is input column 4q + t.
+template <int RB, int NP>
+__device__ __forceinline__ void stage_in16_image_rn(u32x4 *img, const float *W, int ld, int mask0, int nthreads)
+{
+    static_assert(NP == 1 || NP == 2, "the three-piece image is stage_in16_image");
+    uint32_t *w32 = reinterpret_cast<uint32_t *>(img);
+    constexpr int N4 = NP == 2 ? RB * 64 * 4 : 0, N2 = RB * 64 * 2;      // words of the k = 32 image, of the k = 16 image
+    for (int e = threadIdx.x; e < N4 + N2; e += nthreads) {
+        const bool k32 = e < N4;
+        const int f = k32 ? e : e - N4;
+        const int word = k32 ? (f & 3) : (f & 1), ln = (k32 ? (f >> 2) : (f >> 1)) & 63, rb = k32 ? (f >> 8) : (f >> 7);
+        const int i = ln & 15, q = ln >> 4, row = 16 * rb + i;
+        const int c0 = 4 * q + 2 * (word & 1), c1 = c0 + 1;
+        const int p = (k32 || NP == 1) ? 0 : 1;
+        const float v0 = (mask0 && c0 == 0) ? 0.f : W[row * ld + c0];
+        const float v1 = W[row * ld + c1];
+        w32[e] = piece_rn(v0, p) | (piece_rn(v1, p) << 16);
     }
 }
 
@@ -317,14 +408,21 @@ __device__ __forceinline__ void init_h_from_row_bias(const MlpArgs &a, int64_t n
 // forward (third generation).  Same tile walk, prefetch, activation layout and stores as mlp_fwd2_kernel; WIDTH = 64.
 //   KIN = 16 row-major (head) or 32 level-major / row-major (base).
 // ------------------------------------------------------------------------------------------------------
-template <int KIN, int NHL, int INL>
+template <int KIN, int NHL, int INL, int NP = 3>
 struct X6Fwd {
     static constexpr int WIDTH = 64, HB = 4, S = 2;
-    static constexpr int IMG0 = 3 * HB * 64;                       // u32x4 entries
-    static constexpr int IMGH = (NHL == 2) ? 3 * HB * S * 64 : 0;
-    static constexpr int IMGO = 3 * 1 * S * 64;
-    static constexpr int lds_bytes = (IMG0 + IMGH + IMGO + 128) * 16;      // + the two "minus identity" operands
+    // u32x4 entries.  16 inputs: three combos (NP = 3), (hi | hi) + a half-size mid image (NP = 2), a half-size hi image (NP = 1)
+    static constexpr int IMG0 = KIN == 16 ? (NP == 3 ? 3 * HB * 64 : NP == 2 ? HB * 64 + HB * 32 : HB * 32) : NP * HB * 64;
+    static constexpr int IMGH = (NHL == 2) ? NP * HB * S * 64 : 0;
+    static constexpr int IMGO = NP * 1 * S * 64;
+    static constexpr int NEGI = NP > 1 ? 128 : 0;                          // the two "minus identity" operands (no remainders: none)
+    static constexpr int lds_bytes = (IMG0 + IMGH + IMGO + NEGI) * 16;
 };
+
+// The reduced routes keep the tile shape of bf16x6 -- 2 column tiles per wave, 8 waves per workgroup, a grid of two workgroups per
+// CU: their registers (82 .. 116 VGPRs) allow 4 to 5 waves per SIMD, i.e. still two 8-wave workgroups, and 4-wave workgroups (3 to 5
+// per CU) measured 0.38 / 0.23 ms against 0.30 / 0.215 ms for the pair at 4.19 M samples.
+constexpr int kX6FwdWorkgroupsPerCu = 2;
 
 template <int KIN, int INL, int CT>
 __device__ __forceinline__ void load_in_x6(const MlpArgs &a, int64_t tile, int j, int q, f32x4 (&raw)[CT][KIN / 16])
@@ -355,27 +453,36 @@ __device__ __forceinline__ void load_in_x6(const MlpArgs &a, int64_t tile, int j
 
 // first hidden layer of one tile: h = relu(W0 * in + bias), shared by the forward and the recomputing backward so that both
 // produce the same bits
-template <int KIN, int CT, typename NI>
+template <int KIN, int CT, int NP = 3, typename NI>
 __device__ __forceinline__ void first_layer_x6(f32x4 (&h)[4][CT], const u32x4 *img0, const f32x4 (&raw)[CT][KIN / 16],
                                                const NI &nI, int lane)
 {
     if constexpr (KIN == 16) {
         PiecesB16 x[CT];
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) split_in16(raw[ct][0], nI, x[ct]);
-        layer16_x6_ct<4, CT>(h, img0, x, lane);
+        for (int ct = 0; ct < CT; ++ct) split_in16<NP>(raw[ct][0], nI, x[ct]);
+        layer16_x6_ct<4, CT, NP>(h, img0, x, lane);
     } else {
         PiecesB<2> x[CT];
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) split_pair(raw[ct][0], raw[ct][1], nI, x[ct].p[0]);
-        layer_x6_ct<4, 1, CT>(h, img0, x, lane);
+        for (int ct = 0; ct < CT; ++ct) split_pair<NP>(raw[ct][0], raw[ct][1], nI, x[ct].p[0]);
+        layer_x6_ct<4, 1, CT, NP>(h, img0, x, lane);
     }
 }
 
-template <int KIN, int NHL, int INL>
+// staging of a forward's images, one call per matrix (NP = 3: today's images)
+template <int KIN, int NP>
+__device__ __forceinline__ void stage_first_image(u32x4 *img0, const float *W0, int ld, int mask0, int nthreads)
+{
+    if constexpr (KIN == 32) stage_in32_image<4, NP>(img0, W0, ld, mask0, nthreads);
+    else if constexpr (NP == 3) stage_in16_image<4>(img0, W0, ld, mask0, nthreads);
+    else stage_in16_image_rn<4, NP>(img0, W0, ld, mask0, nthreads);
+}
+
+template <int KIN, int NHL, int INL, int NP = 3>
 __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 {
-    using C = X6Fwd<KIN, NHL, INL>;
+    using C = X6Fwd<KIN, NHL, INL, NP>;
     constexpr int CT = 2, NW = 8, TS = 16 * CT, HB = 4, WIDTH = 64;
     static_assert(KIN == 16 || KIN == 32, "first layer: 16 or 32 inputs");
     extern __shared__ float lds[];
@@ -384,11 +491,10 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
     const float *W0 = a.params + a.w0_col;
     const float *W1 = a.params + a.rest_off;
     const float *Wo = W1 + (NHL - 1) * WIDTH * WIDTH;
-    if constexpr (KIN == 16) stage_in16_image<HB>(img0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
-    else stage_in32_image<HB>(img0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
-    if constexpr (NHL == 2) stage_chain_image<HB, 2>(imgH, W1, WIDTH, WIDTH, 64 * NW);
-    stage_chain_image<1, 2>(imgO, Wo, WIDTH, 16, 64 * NW);
-    stage_neg_identity(imgO + C::IMGO);
+    stage_first_image<KIN, NP>(img0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
+    if constexpr (NHL == 2) stage_chain_image<HB, 2, NP>(imgH, W1, WIDTH, WIDTH, 64 * NW);
+    stage_chain_image<1, 2, NP>(imgO, Wo, WIDTH, 16, 64 * NW);
+    if constexpr (NP > 1) stage_neg_identity(imgO + C::IMGO);
     __syncthreads();
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -422,7 +528,7 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
         init_h_from_row_bias<HB, WIDTH, CT>(a, n, tile, t_end, j, q, sl, idx_nx, h);
         if (tile + 1 < t_end) load_in_x6<KIN, INL, CT>(a, tile + 1, j, q, raw_nx);
         // ---- layer 0
-        first_layer_x6<KIN, CT>(h, img0, raw, nI, lane);
+        first_layer_x6<KIN, CT, NP>(h, img0, raw, nI, lane);
         float *act0_t = a.act ? a.act + tile * (CT * HB * 256) : nullptr;
         const bool st1 = 16 < n_rem;
         const bool skip0 = NHL == 2 && a.act_tiled == 2;      // the backward recomputes the first hidden layer
@@ -438,7 +544,7 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) split_pair(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+            for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
         __builtin_amdgcn_sched_barrier(0);
         // ---- hidden layer
         if constexpr (NHL == 2) {
@@ -447,7 +553,7 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
             for (int rb = 0; rb < HB; ++rb)
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) h2[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<HB, 2, CT>(h2, imgH, x, lane);
+            layer_x6_ct<HB, 2, CT, NP>(h2, imgH, x, lane);
             float *act1_t = act0_t ? act0_t + (skip0 ? 0 : a.act_layer_stride) : nullptr;
 #pragma unroll
             for (int rb = 0; rb < HB; ++rb)
@@ -460,14 +566,14 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair(h2[2 * s2][ct], h2[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h2[2 * s2][ct], h2[2 * s2 + 1][ct], nI, x[ct].p[s2]);
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- output layer
         f32x4 o[1][CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) o[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        layer_x6_ct<1, 2, CT>(o, imgO, x, lane);
+        layer_x6_ct<1, 2, CT, NP>(o, imgO, x, lane);
         float *out_t = a.out + tile_base * oc;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -493,32 +599,32 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 // (same pieces, same MFMA order per layer, same epilogues), so h, sigma and the head output carry the same bits as two launches
 // and the recomputing backward reproduces them.  Nothing is saved (act_tiled = 3 only).
 // ------------------------------------------------------------------------------------------------------
-template <int INL>
+template <int INL, int NP = 3>
 struct X6FwdPair {
-    using B = X6Fwd<32, 1, INL>;
-    using H = X6Fwd<16, 2, LSE_IN_ROWMAJOR>;
+    using B = X6Fwd<32, 1, INL, NP>;
+    using H = X6Fwd<16, 2, LSE_IN_ROWMAJOR, NP>;
     // [base img0 | base imgO | head img0 | head imgH | head imgO | the two "minus identity" operands (shared)]
     static constexpr int B_IMG0 = 0, B_IMGO = B_IMG0 + B::IMG0, H_IMG0 = B_IMGO + B::IMGO, H_IMGH = H_IMG0 + H::IMG0,
                          H_IMGO = H_IMGH + H::IMGH, NEGI = H_IMGO + H::IMGO;
-    static constexpr int lds_bytes = (NEGI + 128) * 16;
+    static constexpr int lds_bytes = (NEGI + B::NEGI) * 16;
 };
 
-template <int INL>
+template <int INL, int NP = 3>
 __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */, MlpArgs b /* head: b.in is unused */)
 {
-    using C = X6FwdPair<INL>;
+    using C = X6FwdPair<INL, NP>;
     constexpr int CT = 2, NW = 8, TS = 16 * CT, HB = 4, WIDTH = 64;
     extern __shared__ float lds[];
     u32x4 *img = reinterpret_cast<u32x4 *>(lds);
     u32x4 *b_img0 = img + C::B_IMG0, *b_imgO = img + C::B_IMGO;
     u32x4 *h_img0 = img + C::H_IMG0, *h_imgH = img + C::H_IMGH, *h_imgO = img + C::H_IMGO;
 
-    stage_in32_image<HB>(b_img0, a.params + a.w0_col, a.w0_ld, a.w0_mask0, 64 * NW);
-    stage_chain_image<1, 2>(b_imgO, a.params + a.rest_off, WIDTH, 16, 64 * NW);
-    stage_in16_image<HB>(h_img0, b.params + b.w0_col, b.w0_ld, b.w0_mask0, 64 * NW);
-    stage_chain_image<HB, 2>(h_imgH, b.params + b.rest_off, WIDTH, WIDTH, 64 * NW);
-    stage_chain_image<1, 2>(h_imgO, b.params + b.rest_off + WIDTH * WIDTH, WIDTH, 16, 64 * NW);
-    stage_neg_identity(img + C::NEGI);
+    stage_first_image<32, NP>(b_img0, a.params + a.w0_col, a.w0_ld, a.w0_mask0, 64 * NW);
+    stage_chain_image<1, 2, NP>(b_imgO, a.params + a.rest_off, WIDTH, 16, 64 * NW);
+    stage_first_image<16, NP>(h_img0, b.params + b.w0_col, b.w0_ld, b.w0_mask0, 64 * NW);
+    stage_chain_image<HB, 2, NP>(h_imgH, b.params + b.rest_off, WIDTH, WIDTH, 64 * NW);
+    stage_chain_image<1, 2, NP>(h_imgO, b.params + b.rest_off + WIDTH * WIDTH, WIDTH, 16, 64 * NW);
+    if constexpr (NP > 1) stage_neg_identity(img + C::NEGI);
     __syncthreads();
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -556,7 +662,7 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (tile + 1 < t_end) load_in_x6<32, INL, CT>(a, tile + 1, j, q, raw_nx);
-            first_layer_x6<32, CT>(h, b_img0, raw, nI, lane);
+            first_layer_x6<32, CT, NP>(h, b_img0, raw, nI, lane);
 #pragma unroll
             for (int rb = 0; rb < HB; ++rb)
 #pragma unroll
@@ -567,11 +673,11 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) o[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<1, 2, CT>(o, b_imgO, x, lane);
+            layer_x6_ct<1, 2, CT, NP>(o, b_imgO, x, lane);
             float *h_t = a.out + tile_base * 16;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
@@ -588,7 +694,7 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
             f32x4 rawh[CT][1];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) rawh[ct][0] = o[0][ct];
-            first_layer_x6<16, CT>(h, h_img0, rawh, nI, lane);
+            first_layer_x6<16, CT, NP>(h, h_img0, rawh, nI, lane);
 #pragma unroll
             for (int rb = 0; rb < HB; ++rb)
 #pragma unroll
@@ -599,14 +705,14 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
             __builtin_amdgcn_sched_barrier(0);
             f32x4 h2[HB][CT];
 #pragma unroll
             for (int rb = 0; rb < HB; ++rb)
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) h2[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<HB, 2, CT>(h2, h_imgH, x, lane);
+            layer_x6_ct<HB, 2, CT, NP>(h2, h_imgH, x, lane);
 #pragma unroll
             for (int rb = 0; rb < HB; ++rb)
 #pragma unroll
@@ -616,12 +722,12 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair(h2[2 * s2][ct], h2[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h2[2 * s2][ct], h2[2 * s2 + 1][ct], nI, x[ct].p[s2]);
             __builtin_amdgcn_sched_barrier(0);
             f32x4 r[1][CT];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) r[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<1, 2, CT>(r, h_imgO, x, lane);
+            layer_x6_ct<1, 2, CT, NP>(r, h_imgO, x, lane);
             float *out_t = b.out + tile_base * oc;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {

@@ -11,6 +11,7 @@ allocated.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import weakref
 from dataclasses import dataclass
@@ -432,6 +433,10 @@ class LSEField(nn.Module):
         self.reuse_prepass = True  # the main pass re-uses the visibility pre-pass's positions / hash features of the survivors
         self._prepass = None
         self._h_ref = None        # weak reference to the last base-MLP output (get_density -> get_outputs hand-over)
+        # arithmetic of the two fused MLPs where nothing can need a backward (eval mode under torch.no_grad()): "bf16x6" (what
+        # trains), "bf16x3" or "bf16x1" (ops.MLP_ARITH_ROUTES).  Ignored in training mode -- occupancy refresh, visibility pre-pass
+        # and frozen-field refinement see bf16x6 -- and by a field whose MLPs are not the production shapes.
+        self.inference_arith = "bf16x6"
 
     # -- helpers ---------------------------------------------------------------------------------------
     def _aabb_list(self):
@@ -478,12 +483,34 @@ class LSEField(nn.Module):
         sigma_fn.on_cull = on_cull
         return sigma_fn
 
+    @property
+    def inference_arith(self) -> str:
+        return self._inference_arith
+
+    @inference_arith.setter
+    def inference_arith(self, name: str) -> None:
+        if name not in ops.MLP_ARITH_ROUTES:
+            raise ValueError(f"inference_arith {name!r}: one of {sorted(ops.MLP_ARITH_ROUTES)}")
+        self._inference_arith = name
+
+    def _routed(self, meta: ops.MlpMeta) -> ops.MlpMeta:
+        """``meta`` in the route ``inference_arith`` names, where that route applies: eval mode, no gradients recorded, and both MLPs
+        of the production shapes (the base on the unpadded 32 hash features); everywhere else ``meta`` itself (bf16x6)."""
+        if self._inference_arith == "bf16x6" or self.training or torch.is_grad_enabled():
+            return meta
+        base, head = self.mlp_base_mlp, self.mlp_head
+        if not (base.in_pad == base.in_dim and ops.mlp_reduced_shape(base.meta())
+                and ops.mlp_reduced_shape(ops.MlpMeta(16, head.layer_width, head.n_hidden_layers))):
+            return meta
+        return dataclasses.replace(meta, arith=ops.MLP_ARITH_ROUTES[self._inference_arith])
+
     def _base_mlp(self, y: Tensor, sel: Tensor, n: int, n_dev: Optional[Tensor] = None):
         """(h[N,16], sigma[N]) = base MLP on level-major hash features with the fused trunc_exp density head."""
         mlp = self.mlp_base_mlp
         dens = (sel, self.average_init_density)    # trunc_exp density head fused into the MLP epilogue / backward
         if mlp.in_pad == mlp.in_dim:
-            return ops.fused_mlp(mlp.params, y, mlp.meta(), n, density=dens, n_dev=n_dev, input_only=mlp.input_only_bwd)
+            return ops.fused_mlp(mlp.params, y, self._routed(mlp.meta()), n, density=dens, n_dev=n_dev,
+                                 input_only=mlp.input_only_bwd)
         if n_dev is not None:
             raise _lib.LseHipError("a device-side sample count needs the 32-input base MLP (L * F == 32)")
         # small grids (L*F < 16): tcnn's ones-padding columns act as a bias shared by every sample
@@ -533,9 +560,10 @@ class LSEField(nn.Module):
         n = x01.shape[0]
         base, head = self.mlp_base_mlp, self.mlp_head
         row_bias, head_meta = self._head_row_bias(rays_d, emb_idx, emb_table)
-        if base.in_pad == base.in_dim and ops.mlp_pair_usable(base.params, y, base.meta(), head.params, head_meta, row_bias,
+        base_meta, head_meta = self._routed(base.meta()), self._routed(head_meta)
+        if base.in_pad == base.in_dim and ops.mlp_pair_usable(base.params, y, base_meta, head.params, head_meta, row_bias,
                                                               ray_idx, packed_info):
-            h, sigma, out = ops.fused_mlp_pair(base.params, y, sel, self.average_init_density, base.meta(), head.params, head_meta,
+            h, sigma, out = ops.fused_mlp_pair(base.params, y, sel, self.average_init_density, base_meta, head.params, head_meta,
                                                n, row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev,
                                                input_only=base.input_only_bwd and head.input_only_bwd)
             return sigma, h, sel, out
@@ -568,6 +596,7 @@ class LSEField(nn.Module):
         W_in IN PLACE (first-layer view: leading dimension in_pad, column offset 15, column 0 masked) -- the parameter
         vector is never split or copied, and both kernels accumulate their weight gradients straight into its .grad."""
         row_bias, meta = self._head_row_bias(rays_d, emb_idx, emb_table)
+        meta = self._routed(meta)
         return ops.fused_mlp(self.mlp_head.params, h, meta, h.shape[0], row_bias, ray_idx, packed_info, out_cols=4, n_dev=n_dev,
                              input_only=self.mlp_head.input_only_bwd)
 

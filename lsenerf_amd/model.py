@@ -82,6 +82,19 @@ class LSENeRFModelConfig:
     # dictionaries of ``get_image_metrics_and_images`` and ``evaluate_set``'s ``on_image``, after "err_map".  Computed on the
     # device (``ops.canny_edges``; OpenCV's published algorithm restated, parity unpinned).  Off: the dictionaries are as before.
     eval_overlay: bool = False
+    # --- arithmetic of the two fused MLPs in the eval render: "bf16x6" (what trains: six bf16 piece products per multiply, f32's
+    # error bound), "bf16x3" (two pieces per operand, three products, relative error 2^-16 per multiply) or "bf16x1" (plain bf16
+    # operands, 2^-8) -- include/lse_hip.h: lse_mlp_desc.arith.  Sets ``LSEField.inference_arith``: honoured where the field runs in
+    # eval mode under torch.no_grad() (get_outputs_for_camera_ray_bundle, the early-stop route, evaluate_set, render_camera, the
+    # eager eval ``forward``) and both MLPs are the production shapes; training mode -- occupancy refresh, visibility pre-pass,
+    # frozen-field refinement -- always runs bf16x6, and so does a small-grid base MLP or a ``hidden_dim`` other than 64.  An
+    # unknown name is a ValueError in ``populate_modules``.  Measured on one MI355X (tools/bench_eval_precision.py, 640 x 480, the
+    # bench workload): 38.7 / 34.5 / 31.9 ms per image at chunks of 32768 rays and 43.2 / 39.0 / 37.5 ms at 3512 for
+    # bf16x6 / bf16x3 / bf16x1 (the pair kernel alone: 0.506 / 0.320 / 0.226 ms per 4.19 M samples).  Against the bf16x6 image
+    # bf16x3 keeps rgb at 128.8 dB (largest difference 2.4e-6) and, with opaque surfaces, at 103.2 dB (1.5e-4); bf16x1 at 72.4 dB
+    # (1.6e-3) and 48.9 dB (single pixels move by 0.09, depth by 0.34: the density logit is off by ~0.03).  Prefer "bf16x3";
+    # "bf16x1" is the fast one and its images are for a trained scene to judge.
+    eval_mlp_arith: str = "bf16x6"
 
     def __post_init__(self):   # R:lse_nerf/lsenerf.py:86-99
         if self.evs_mapping_method is None or str(self.evs_mapping_method).lower() == "none":
@@ -402,12 +415,15 @@ class LSENeRFModel(nn.Module):
     # -- R:lse_nerf/lsenerf.py:158-228 ----------------------------------------------------------------
     def populate_modules(self):
         cfg = self.config
+        if cfg.eval_mlp_arith not in ops.MLP_ARITH_ROUTES:
+            raise ValueError(f"eval_mlp_arith {cfg.eval_mlp_arith!r}: one of {sorted(ops.MLP_ARITH_ROUTES)}")
         scene_contraction = None if cfg.disable_scene_contraction else SceneContraction(order=float("inf"))
         self.field = LSEField(aabb=self.scene_aabb_2x3, num_images=self.num_train_data,
                               log2_hashmap_size=cfg.log2_hashmap_size, max_res=cfg.max_res,
                               spatial_distortion=scene_contraction, embd_config=cfg.embed_config, implementation="tcnn",
                               num_levels=cfg.num_levels, hidden_dim=cfg.hidden_dim,      # (field-size knobs: BASELINE config 1)
                               hidden_dim_color=cfg.hidden_dim_color)
+        self.field.inference_arith = cfg.eval_mlp_arith
         self.scene_aabb = nn.Parameter(self.scene_aabb_2x3.flatten(), requires_grad=False)
         if cfg.render_step_size is None:   # auto step size: ~1000 samples in the base level grid
             cfg.render_step_size = ((self.scene_aabb[3:] - self.scene_aabb[:3]) ** 2).sum().sqrt().item() / 1000

@@ -676,6 +676,33 @@ def mlp_input_only_shape(meta: MlpMeta) -> bool:
     return _x6_shape(meta) and meta.arith == _lib.LSE_MLP_ARITH_AUTO
 
 
+# The forward's arithmetic routes by name (include/lse_hip.h: lse_mlp_desc.arith).  "bf16x6" is what trains; the two reduced-piece
+# routes are inference forwards of the head / base shapes (LSEField.inference_arith, LSENeRFModelConfig.eval_mlp_arith).
+MLP_ARITH_ROUTES = {"bf16x6": _lib.LSE_MLP_ARITH_AUTO, "bf16x3": _lib.LSE_MLP_ARITH_BF16X3, "bf16x1": _lib.LSE_MLP_ARITH_BF16X1}
+
+
+def mlp_reduced_arith(meta: MlpMeta) -> bool:
+    return meta.arith in (_lib.LSE_MLP_ARITH_BF16X3, _lib.LSE_MLP_ARITH_BF16X1)
+
+
+def mlp_reduced_shape(meta: MlpMeta) -> bool:
+    """The shapes the reduced-piece forwards are built for: the head's and the base's (whatever ``meta.arith`` says)."""
+    return _x6_shape(meta)
+
+
+def _check_reduced_call(who: str, metas, tensors) -> None:
+    """A reduced-piece route is a forward and nothing else: refuse, before any launch, a call that would need a backward or a shape
+    the kernels do not serve."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise ValueError(f"{who}: the reduced-piece routes (bf16x3 / bf16x1) run the forward only -- call under torch.no_grad(), or "
+                         "with tensors that need no gradient (a backward runs in bf16x6)")
+    for meta in metas:
+        if not mlp_reduced_shape(meta):
+            raise ValueError(f"{who}: the reduced-piece routes serve the 16->64->64->16 row-major head and the 32->64->16 base only "
+                             f"(got n_in={meta.n_in} width={meta.width} n_hidden_layers={meta.n_hidden_layers} "
+                             f"in_layout={meta.in_layout})")
+
+
 def _bias_grad_in_kernel(bias_grad: bool, bias_sorted: bool) -> bool:      # a needed row-bias gradient can be reduced in-kernel
     return not bias_grad or bool(FUSED_BIAS_GRAD and bias_sorted)
 
@@ -823,6 +850,20 @@ class _MlpFn(torch.autograd.Function):
         return (None if direct is not None else d_params), d_in, d_bias, None, None, None, None, None, None, None, None, None
 
 
+def _mlp_fwd_reduced(params, x, row_bias, row_bias_idx, selector, meta: MlpMeta, n: int, out_cols: int, density_scale, n_dev):
+    """``lse_mlp_fwd`` in a reduced-piece route: nothing saved, nothing recorded for autograd."""
+    with torch.no_grad():
+        dev = params.device
+        out = torch.empty((n, out_cols), dtype=torch.float32, device=dev)
+        sigma = torch.empty(n, dtype=torch.float32, device=dev) if density_scale is not None else None
+        desc = meta.desc()
+        _call_n("lse_mlp_fwd", n_dev, ctypes.byref(desc), _f32(params, "params"), _f32(x, "mlp input"),
+                _f32(row_bias, "row_bias", True), _chk(row_bias_idx, torch.int32, "row_bias_idx", True),
+                ctypes.c_void_p(out.data_ptr()), out_cols, None, 3, _f32(sigma, "sigma", True),
+                _chk(selector, torch.uint8, "selector", True), float(density_scale or 0.0), n, _stream())
+    return out if sigma is None else (out, sigma)
+
+
 def _mlp_pair_shapes(base_meta: MlpMeta, head_meta: MlpMeta) -> bool:
     """The shapes lse_mlp_fwd_pair is built for: the recompute-all production pair (base 32 -> 64 -> 16, head 16 -> 64 -> 64 -> 16)."""
     return (mlp_input_only_shape(base_meta) and base_meta.n_in == 32 and base_meta.out_activation == _lib.LSE_ACT_NONE
@@ -887,17 +928,26 @@ class _MlpPairFn(torch.autograd.Function):
         return d_bp, d_y, None, d_hp, d_bias, None, None, None, None, None, None, None, None, None
 
 
+def _mlp_pair_reduced(base_meta: MlpMeta, head_meta: MlpMeta) -> bool:
+    """The production pair with the same reduced-piece route in both networks."""
+    return (mlp_reduced_arith(base_meta) and head_meta.arith == base_meta.arith and _x6_shape(base_meta) and base_meta.n_in == 32
+            and base_meta.out_activation == _lib.LSE_ACT_NONE and _x6_shape(head_meta) and head_meta.n_in == 16)
+
+
 def mlp_pair_usable(base_params, y, base_meta: MlpMeta, head_params, head_meta: MlpMeta, row_bias, row_bias_idx,
                     bias_packed_info) -> bool:
     """Whether ``fused_mlp_pair`` may replace ``fused_mlp`` (base, density head) followed by ``fused_mlp`` (head) on the same
     samples: the switch is on, the shapes are the pair's, and either nothing needs a gradient or both backward launches can take
     the recompute-all path (nothing saved, act_tiled = 3) -- with trainable parameters what ``_MlpFn.forward`` would choose, with
     frozen ones (``requires_grad == False``) the same kernels writing their weight-gradient products to ``frozen_wgrad_scratch``."""
-    if not (MLP_FWD_PAIR and _mlp_pair_shapes(base_meta, head_meta)):
+    reduced = _mlp_pair_reduced(base_meta, head_meta)      # (a reduced-piece pair: forward only, the same route in both)
+    if not (MLP_FWD_PAIR and (reduced or _mlp_pair_shapes(base_meta, head_meta))):
         return False
     need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (base_params, y, head_params, row_bias))
     if not need_grad:
         return True
+    if reduced:
+        return False
     # the pair saves nothing, so frozen parameters recompute too, as they do under a device-side count: has_count=True
     route = functools.partial(mlp_bwd_route, need_grad=True, has_count=True, input_only=False)
     base = route(base_meta, params_grad=base_params.requires_grad, bias_grad=False, bias_sorted=False)
@@ -911,7 +961,24 @@ def fused_mlp_pair(base_params, y, selector, density_scale, base_meta: MlpMeta, 
                    input_only: bool = False):
     """``fused_mlp(base_params, y, base_meta, n, density=(selector, density_scale))`` followed by ``fused_mlp(head_params, h,
     head_meta, n, row_bias, row_bias_idx, bias_packed_info, out_cols)`` with one forward launch; returns ``(h[n,16], sigma[n],
-    out[n,out_cols])`` with the same bits.  Callers check ``mlp_pair_usable`` first.  ``input_only``: as in ``fused_mlp``."""
+    out[n,out_cols])`` with the same bits.  Callers check ``mlp_pair_usable`` first.  ``input_only``: as in ``fused_mlp``.  Both metas
+    in the same reduced route: the forward only, as in ``fused_mlp`` (same bits as its two calls in that route)."""
+    if mlp_reduced_arith(base_meta) or mlp_reduced_arith(head_meta):
+        _check_reduced_call("fused_mlp_pair", (base_meta, head_meta), (base_params, y, head_params, row_bias))
+        if not _mlp_pair_reduced(base_meta, head_meta):
+            raise ValueError("fused_mlp_pair: a reduced-piece pair needs the production shapes and the same route in both networks")
+        with torch.no_grad():      # nothing saved, nothing recorded for autograd
+            dev = base_params.device
+            h = torch.empty((n, 16), dtype=torch.float32, device=dev)
+            sigma = torch.empty(n, dtype=torch.float32, device=dev)
+            out = torch.empty((n, out_cols), dtype=torch.float32, device=dev)
+            bdesc, hdesc = base_meta.desc(), head_meta.desc()
+            _call_n("lse_mlp_fwd_pair", n_dev, ctypes.byref(bdesc), _f32(base_params, "base params"), _f32(y, "mlp input"),
+                    _chk(selector, torch.uint8, "selector", True), float(density_scale), ctypes.byref(hdesc),
+                    _f32(head_params, "head params"), _f32(row_bias, "row_bias", True),
+                    _chk(row_bias_idx, torch.int32, "row_bias_idx", True), ctypes.c_void_p(h.data_ptr()),
+                    ctypes.c_void_p(sigma.data_ptr()), ctypes.c_void_p(out.data_ptr()), out_cols, n, _stream())
+        return h, sigma, out
     return _MlpPairFn.apply(base_params, y, selector, head_params, row_bias, row_bias_idx, bias_packed_info, base_meta, head_meta,
                             n, out_cols, density_scale, n_dev, input_only)
 
@@ -976,8 +1043,13 @@ def fused_mlp(params, x, meta: MlpMeta, n: int, row_bias=None, row_bias_idx=None
     ``density=(selector_or_None, scale)`` fuses the trunc_exp density head on output 0 and returns ``(out, sigma[n])``.
     ``input_only`` (this call's, not the process's): where ``params`` is frozen (``requires_grad == False``) and the shape is the
     head's or the base's, the backward is ``lse_mlp_bwd_input`` -- d(input) and d(row_bias) alone, no weight-gradient products and
-    no ``frozen_wgrad_scratch``; everywhere else it changes nothing."""
+    no ``frozen_wgrad_scratch``; everywhere else it changes nothing.
+    A reduced ``meta.arith`` (``MLP_ARITH_ROUTES``: bf16x3 / bf16x1) runs the forward only, on the head / base shapes: ``ValueError``
+    before any launch where gradients are enabled and params / input / row bias require one, or for another shape."""
     selector, scale = (None, None) if density is None else density
+    if mlp_reduced_arith(meta):
+        _check_reduced_call("fused_mlp", (meta,), (params, x, row_bias))
+        return _mlp_fwd_reduced(params, x, row_bias, row_bias_idx, selector, meta, n, out_cols, scale, n_dev)
     return _MlpFn.apply(params, x, row_bias, row_bias_idx, bias_packed_info, selector, meta, n, out_cols, scale, n_dev, input_only)
 
 

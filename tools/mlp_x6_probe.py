@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Fused-MLP forward on the bf16 matrix cores with three-piece operands (mlp_x6.h, lse_mlp_desc.arith = AUTO) next to the f32-MFMA
-forward (impl 1): time at the metric size, and error of both against a float64 evaluation of the same network on a subset."""
+forward (impl 1): time at the metric size, and error of both against a float64 evaluation of the same network on a subset.  The
+reduced-piece inference routes (arith = BF16X3 / BF16X1: two pieces and three products, one piece and one product) are reported
+next to them: time with nothing saved, and output error against the same float64 network."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -88,3 +90,17 @@ for N in (4096 * 1024, 1000):
             line += f"  impl {impl}: {t:.3f} ms, out err {eo:.2e}, hidden err {eh:.2e};"
         d = float((res[1][0] - res[2][0]).abs().max())
         print(line + f"  max|impl1 - impl2| = {d:.2e}", flush=True)
+        line = f"N={N} {name}, nothing saved:"
+        for route in ("bf16x6", "bf16x3", "bf16x1"):
+            desc = dataclasses.replace(meta, arith=ops.MLP_ARITH_ROUTES[route]).desc()
+            out = torch.zeros(N, oc, device=dev)
+
+            def run():
+                _lib.call("lse_mlp_fwd", ctypes.byref(desc), P(params), P(x), P(rb), P(ridx), P(out), oc, None, 3,
+                          None, None, 0.0, N, None, ops._stream())
+            run()
+            torch.cuda.synchronize()
+            t = timeit(run)[0] if N > 100000 else float("nan")
+            eo = float((out[rows].double() - o64).abs().max() / o64.abs().max())
+            line += f"  {route}: {t:.3f} ms, out err {eo:.2e};"
+        print(line, flush=True)
