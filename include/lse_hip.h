@@ -329,6 +329,15 @@ int lse_mlp_bwd_input(const lse_mlp_desc *desc, const float *params, const float
                       const float *d_out, const float *d_sigma, const uint8_t *selector, float density_scale, float *d_in,
                       const float *row_bias, const int32_t *row_bias_idx, float *d_row_bias, int64_t n, const int64_t *n_dev,
                       lse_stream_t stream);
+/* d_in = d(out[0]) / d(in) of the base network (32 inputs in either layout, width 64, one hidden layer, no output activation,
+ * LSE_MLP_ARITH_AUTO): the gradient of the density logit with respect to the hash features, for analytic normals.  This is
+ * lse_mlp_bwd_input for a d_out of (1, 0, .., 0) without the seed: the hidden layer is recomputed on the bf16 matrix cores, the
+ * output layer's backward is row 0 of the output matrix through the ReLU mask (no product), and neither `out` nor a d_out is read.
+ * d_in is overwritten in the layout of desc->in_layout (level-major is what lse_hash_bwd_input reads); rows at or beyond the
+ * count are not written; two calls give the same bits.  Any other shape or arithmetic route is LSE_E_UNSUPPORTED before any
+ * launch.  Keeps no state. */
+int lse_density_logit_grad(const lse_mlp_desc *desc, const float *params, const float *in, float *d_in, int64_t n,
+                           const int64_t *n_dev, lse_stream_t stream);
 /* unfused weight gradients from materialised d_act / d_out_pre, accumulate into d_params (same layout as params). */
 int lse_mlp_wgrad(const lse_mlp_desc *desc, const float *in, const float *act, const float *d_act,
                   const float *d_out_pre, float *d_params, int64_t n, lse_stream_t stream);
@@ -411,6 +420,21 @@ int lse_render_weight_bwd(const float *t_starts, const float *t_ends, const floa
 int lse_eval_composite(const float *t_starts, const float *t_ends, const float *sigmas, const float *rgb, int32_t rgb_stride,
                        const int64_t *packed_info, int32_t n_rays, int32_t flags, float background, float *workspace, float *out_rgb,
                        float *out_acc, float *out_depth, int64_t *out_nsamples, lse_stream_t stream);
+
+/* Rendered normals of an evaluation render, one launch: the per-ray walk and the render weights w_i of lse_eval_composite over
+ * the same t_starts / t_ends / sigmas / packed_info (capacity-extent sample arrays, packed_info authoritative), applied to
+ *   n_i = -g_i / max(|g_i|, 1e-12),   g_i = d_x01[i]  (the gradient of the density logit with respect to the unit-cube position),
+ *   N = sum_i w_i n_i,   and with LSE_NORMALS_RENORMALIZE   N / (|N| + 1e-10)        (nerfstudio's NormalsRenderer).
+ * LSE_NORMALS_WORLD multiplies g_i by the transposed Jacobian of the position map at the sample (what lse_positions_bwd applies:
+ * contraction or aabb normalisation, selector-masked) before it is normalised; it needs rays_o, rays_d [n_rays,3] and, without
+ * contraction, h_aabb[6] -- all three are unused and nullable otherwise.  A zero gradient gives a zero normal, a ray without
+ * samples or with zero weights gives (0, 0, 0); a NaN sigma propagates as in lse_eval_composite.  out_normals [n_rays,3] may be a
+ * row offset into a larger image.  No atomics, no workspace, no state. */
+#define LSE_NORMALS_WORLD 1
+#define LSE_NORMALS_RENORMALIZE 2
+int lse_eval_composite_normals(const float *t_starts, const float *t_ends, const float *sigmas, const float *d_x01,
+                               const int64_t *packed_info, int32_t n_rays, const float *rays_o, const float *rays_d,
+                               int32_t contraction, const float *h_aabb, int32_t flags, float *out_normals, lse_stream_t stream);
 
 /* The same compositing walked in SEGMENTS of the ray, for early ray termination: between two segments the caller evaluates the field
  * only on the rays that are still alive.  Ray sample k meets lane k mod 64 in lse_eval_composite; every segment but the last ends

@@ -24,6 +24,7 @@ LSE_MLP_ARITH_AUTO, LSE_MLP_ARITH_F32_MFMA = 0, 1
 LSE_MLP_ARITH_BF16X3, LSE_MLP_ARITH_BF16X1 = 2, 3      # reduced-piece inference forward (include/lse_hip.h: lse_mlp_desc.arith)
 LSE_TRAVERSE_FMA_SETUP = 1
 LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
+LSE_NORMALS_WORLD, LSE_NORMALS_RENORMALIZE = 1, 2
 LSE_PREP_EVENT_STATS = 1
 LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
 LSE_PANEL_IMG, LSE_PANEL_DEPTH, LSE_PANEL_ERR_MAP, LSE_PANEL_OVERLAY, LSE_PANEL_EV_OUT = 1, 2, 4, 8, 16
@@ -145,6 +146,7 @@ SIGNATURES = {
     "lse_mlp_fwd_pair": [POINTER(MlpDesc), P, P, P, F32, POINTER(MlpDesc), P, P, P, P, P, P, I32, I64, P, P],
     "lse_mlp_bwd": [POINTER(MlpDesc), P, P, P, I32, P, I32, P, P, P, F32, P, P, P, P, P, P, P, P, I64, P, P],
     "lse_mlp_bwd_input": [POINTER(MlpDesc), P, P, P, I32, P, P, P, F32, P, P, P, P, I64, P, P],
+    "lse_density_logit_grad": [POINTER(MlpDesc), P, P, P, I64, P, P],
     "lse_mlp_wgrad": [POINTER(MlpDesc), P, P, P, P, P, I64, P],
     "lse_segment_sum_rows": [P, I32, P, I32, P, P],
     "lse_ray_features_fwd": [P, P, P, I32, I32, P, P],
@@ -160,6 +162,7 @@ SIGNATURES = {
     "lse_volrend_bwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P],
     "lse_volrend_depth_fwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P, P],
     "lse_eval_composite": [P, P, P, P, I32, P, I32, I32, F32, P, P, P, P, P, P],
+    "lse_eval_composite_normals": [P, P, P, P, P, I32, P, P, I32, P, I32, P, P],
     "lse_eval_segment_state_bytes": [I32, POINTER(c_int64)],
     "lse_eval_segment_begin": [P, I32, I64, P, P, P],
     "lse_eval_composite_segment": [P, P, P, P, I32, P, P, I32, I32, I64, I64, F32, P, P, P],

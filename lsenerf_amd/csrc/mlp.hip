@@ -1575,6 +1575,17 @@ int launch_bwd_input(const MlpArgs &a, hipStream_t st)
     return lse::check_launch("lse_mlp_bwd_input");
 }
 
+// d(out[0]) / d(input) of the base shape: the same grid, the one-hot-seeded instance of the kernel
+template <int INL>
+int launch_logit_grad(const MlpArgs &a, hipStream_t st)
+{
+    using C = X6BwdIn<32, 1>;
+    const int64_t tiles = (a.n + 16 * C::CT - 1) / (16 * C::CT);
+    const int blocks = (int)std::min<int64_t>((tiles + C::NW - 1) / C::NW, 256 * C::WAVES_PER_SIMD);
+    hipLaunchKernelGGL((mlp_bwd_input_kernel<32, 1, INL, false, true>), dim3(blocks), dim3(64 * C::NW), C::lds_bytes, st, a);
+    return lse::check_launch("lse_density_logit_grad");
+}
+
 template <int KIN, int WIDTH, int NHL, int INL>
 int launch_bwd(const MlpArgs &a, hipStream_t st)
 {
@@ -1839,6 +1850,33 @@ extern "C" int lse_mlp_bwd_input(const lse_mlp_desc *desc, const float *params, 
     if (desc->n_in == 16) return launch_bwd_input<16, 2, LSE_IN_ROWMAJOR>(a, st);
     if (desc->in_layout == LSE_IN_LEVELMAJOR) return launch_bwd_input<32, 1, LSE_IN_LEVELMAJOR>(a, st);
     return launch_bwd_input<32, 1, LSE_IN_ROWMAJOR>(a, st);
+}
+
+extern "C" int lse_density_logit_grad(const lse_mlp_desc *desc, const float *params, const float *in, float *d_in, int64_t n,
+                                      const int64_t *n_dev, lse_stream_t stream)
+{
+    int rc = check_desc(desc, "lse_density_logit_grad");
+    if (rc) return rc;
+    LSE_REQUIRE(n >= 0, "lse_density_logit_grad: n < 0");
+    if (desc->n_in != 32 || desc->width != 64 || desc->n_hidden_layers != 1 || desc->out_activation != LSE_ACT_NONE) {
+        lse::set_error("lse_density_logit_grad: built for the 32->64->16 base without an output activation only (got n_in=%d "
+                       "width=%d n_hidden_layers=%d out_activation=%d)",
+                       desc->n_in, desc->width, desc->n_hidden_layers, desc->out_activation);
+        return LSE_E_UNSUPPORTED;
+    }
+    if (desc->arith != LSE_MLP_ARITH_AUTO) {
+        lse::set_error("lse_density_logit_grad: bf16x6 arithmetic only (desc->arith must be LSE_MLP_ARITH_AUTO)");
+        return LSE_E_UNSUPPORTED;
+    }
+    if (n == 0) return LSE_OK;
+    LSE_REQUIRE(params && in && d_in, "lse_density_logit_grad: null pointer");
+    MlpArgs a{};
+    a.params = params; a.in = in; a.d_in = d_in; a.n = n; a.n_stride = n; a.n_dev = n_dev;
+    a.out_activation = LSE_ACT_NONE; a.out_cols = 16; a.act_tiled = 3;
+    fill_view(a, desc);
+    hipStream_t st = lse::as_stream(stream);
+    if (desc->in_layout == LSE_IN_LEVELMAJOR) return launch_logit_grad<LSE_IN_LEVELMAJOR>(a, st);
+    return launch_logit_grad<LSE_IN_ROWMAJOR>(a, st);
 }
 
 extern "C" int lse_gemm_tn_acc(const float *g, int32_t m, const float *a, int32_t k, int32_t a_layout, int64_t n,

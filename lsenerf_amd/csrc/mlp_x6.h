@@ -908,8 +908,9 @@ struct X6BwdW {
     int sm_j, sm_t;          // 32-byte rows (small tile, 16-column W0)
     int w0b_j, w0b_t[2];     // 64-byte rows (32-column W0): 16-byte row read / transposed
 
-    // cut the three matrices into LDS (all NW waves), write the "minus identity" operands, barrier
-    template <int NW>
+    // cut the three matrices into LDS (all NW waves), write the "minus identity" operands, barrier.  WITH_WO = false leaves the
+    // output matrix's image unwritten (the one-hot-seeded kernel reads row 0 of Wo as plain floats)
+    template <int NW, bool WITH_WO = true>
     __device__ __forceinline__ void stage(float *lds, const MlpArgs &a)
     {
         imgW0 = reinterpret_cast<uint8_t *>(lds);
@@ -920,7 +921,7 @@ struct X6BwdW {
         const float *Wo = W1 + (NHL - 1) * 64 * 64;
         stage_plain<64, KIN>(imgW0, W0, a.w0_ld, a.w0_mask0, 64 * NW);
         if constexpr (NHL == 2) stage_plain<64, 64>(imgW1, W1, 64, 0, 64 * NW);
-        stage_plain<16, 64>(imgWo, Wo, 64, 0, 64 * NW);
+        if constexpr (WITH_WO) stage_plain<16, 64>(imgWo, Wo, 64, 0, 64 * NW);
         stage_neg_identity(reinterpret_cast<u32x4 *>(imgWo + 3 * C::WO_PIECE));
         __syncthreads();
     }
@@ -1691,9 +1692,15 @@ struct X6BwdIn : X6BwdImg<KIN, NHL> {
     static constexpr int NW = kBwdInNW, CT = 2, WAVES_PER_SIMD = kBwdInWavesPerSimd;
 };
 
-template <int KIN, int NHL, int INL, bool BIAS>
+//
+// SEED0 (lse_density_logit_grad, the base shape): d_in = d(out[0]) / d(in).  The seed is one-hot, so the output layer's backward
+// is no product: dH = row 0 of Wo through the ReLU mask, each lane holding the four weights of its accumulator rows.  No d_out,
+// out or d_sigma is read and Wo has no LDS image; everything else is the code below, so d_in carries the bits that the same kernel
+// gives for a d_out of (1, 0, .., 0): Wo[0][k] * 1 over the six piece products is Wo[0][k] exactly.
+template <int KIN, int NHL, int INL, bool BIAS, bool SEED0 = false>
 __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_input_kernel(MlpArgs a)
 {
+    static_assert(!SEED0 || (NHL == 1 && !BIAS), "the one-hot seed serves the base shape without a row bias");
     using C = X6BwdIn<KIN, NHL>;
     constexpr int CT = C::CT, NW = C::NW;
     constexpr int TS = 16 * CT, HB = 4, WIDTH = 64, KB0 = KIN / 16;
@@ -1701,7 +1708,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
     static_assert(x6_recompute_shape(KIN, WIDTH, NHL, INL), "head or base shape");
     extern __shared__ float lds[];
     X6BwdW<KIN, NHL> w;
-    w.template stage<NW>(lds, a);       // the only barrier: the images are read-only from here on
+    w.template stage<NW, !SEED0>(lds, a);       // the only barrier: the images are read-only from here on
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
@@ -1715,6 +1722,14 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
     const bool need_out = a.out_activation == LSE_ACT_SIGMOID;
     const int oc = a.out_cols;
     const bool want_bias = BIAS && a.d_row_bias != nullptr;
+    // (SEED0) row 0 of Wo at this lane's accumulator rows 16rb + 4q ..
+    f32x4 wo0[HB];
+    if constexpr (SEED0) {
+#pragma unroll
+        for (int rb = 0; rb < HB; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wo0[rb][r] = a.params[a.rest_off + 16 * rb + 4 * q + r];
+    }
 
     // running row-bias sum: this lane's samples of the column tiles that belong wholly to row cur_row (wave-uniform)
     int cur_row = -1;
@@ -1751,7 +1766,7 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
         int brow[CT] = {};
         const float *rbase = bias_rows_of_tile<BIAS, CT>(a, n, tile, t_end, j, sl, brow_nx, brow);
         f32x4 g[CT];
-        out_grad_tile<CT>(a, tile_base, oc, need_out, q, sl, valid, g);
+        if constexpr (!SEED0) out_grad_tile<CT>(a, tile_base, oc, need_out, q, sl, valid, g);
         // ---- which column tiles feed the running row sum (wave-uniform): one row per tile, as in mlp_bwd3_kernel
         bool whole[CT] = {};
         if (want_bias) {
@@ -1853,8 +1868,10 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
         // ---- dH_last = Wo^T G_out (16 rows of Wo: k = 16), gated by the last mask; pieces stay in registers
         {
             PiecesB16 gx[CT];
+            if constexpr (!SEED0) {
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) split_in16(g[ct], nI, gx[ct]);
+                for (int ct = 0; ct < CT; ++ct) split_in16(g[ct], nI, gx[ct]);
+            }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 f32x4 dh[2][CT];
@@ -1862,13 +1879,17 @@ __global__ __launch_bounds__(64 * kBwdInNW, kBwdInWavesPerSimd) void mlp_bwd_inp
                 for (int b = 0; b < 2; ++b) {
                     const int rb = 2 * s2 + b;
                     u32x4 wc[3];
-                    combos16_lds([&](int p) { return lds_tr_read(w.imgWo + (p * C::WO_PIECE + w.so_t[rb])); }, wc);
+                    if constexpr (!SEED0) combos16_lds([&](int p) { return lds_tr_read(w.imgWo + (p * C::WO_PIECE + w.so_t[rb])); }, wc);
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct) {
-                        f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
-                        c = LSE_MFMA_BF(wc[2], gx[ct].c[2], c);
-                        c = LSE_MFMA_BF(wc[1], gx[ct].c[1], c);
-                        dh[b][ct] = LSE_MFMA_BF(wc[0], gx[ct].c[0], c);
+                        if constexpr (SEED0) {
+                            dh[b][ct] = wo0[rb];
+                        } else {
+                            f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
+                            c = LSE_MFMA_BF(wc[2], gx[ct].c[2], c);
+                            c = LSE_MFMA_BF(wc[1], gx[ct].c[1], c);
+                            dh[b][ct] = LSE_MFMA_BF(wc[0], gx[ct].c[0], c);
+                        }
                         const uint32_t m = (NHL == 2) ? m1[ct] : m0[ct];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) dh[b][ct][r] = relu_gate(dh[b][ct][r], m, 4 * rb + r);

@@ -219,6 +219,82 @@ __global__ __launch_bounds__(256) void eval_composite_kernel(const float *__rest
     }
 }
 
+#include "positions.h"      // Box, positions_bwd_sample: the world-space Jacobian of the normals
+
+// Rendered normals of an evaluation render (lse_eval_composite_normals): the sample-to-lane walk and the weight arithmetic of
+// eval_composite_kernel (the same prefix scan with the same fused step, the same carry, w = T * alpha), with a vector in place of
+// the colour.  Per sample: g = d_x01 (the gradient of the density logit), optionally through the transposed Jacobian of the position
+// map at the sample's position (LSE_NORMALS_WORLD), n = -g / max(|g|, 1e-12) (F.normalize: a zero gradient gives a zero normal);
+// per ray N = sum w n, then N / (|N| + 1e-10) with LSE_NORMALS_RENORMALIZE (NormalsRenderer).  A ray without samples writes zeros.
+__global__ __launch_bounds__(256) void eval_composite_normals_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                                     const float *__restrict__ sigma, const float *__restrict__ dx01,
+                                                                     const int64_t *__restrict__ packed, int n_rays,
+                                                                     const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                                     int contraction, Box box, int flags, float *__restrict__ out)
+{
+#pragma clang fp contract(off)   // the weight arithmetic is eval_composite_kernel's, operation by operation
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
+    const bool world = (flags & LSE_NORMALS_WORLD) != 0;
+    float ro[3] = {0.f, 0.f, 0.f}, rd[3] = {0.f, 0.f, 0.f};
+    if (world) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { ro[k] = rays_o[(int64_t)ray * 3 + k]; rd[k] = rays_d[(int64_t)ray * 3 + k]; }
+    }
+    float carry = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+    for (int64_t base = 0; base < cnt; base += 64) {
+        const int64_t i = s0 + base + lane;
+        const bool valid = base + lane < cnt;
+        float a = 0.f, b = 0.f, sg = 0.f;
+        if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
+        const float dt = b - a;
+        const float sd = sg * dt;
+        float incl = sd;
+        {
+            const float nb = __shfl_up(incl, 1, 64);
+            if (lane >= 1) incl = fmaf(sg, dt, nb);
+        }
+#pragma unroll
+        for (int off = 2; off < 64; off <<= 1) {
+            const float nb = __shfl_up(incl, off, 64);
+            if (lane >= off) incl = incl + nb;
+        }
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 0.f;
+        const float T = expf(-(excl + carry));
+        const float alpha = 1.f - expf(-sd);
+        const float w = valid ? T * alpha : 0.f;
+        if (valid) {
+            float g[3] = {dx01[i * 3 + 0], dx01[i * 3 + 1], dx01[i * 3 + 2]};
+            if (world) {
+                const float s = a + b;
+                float p[3], gw[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) p[k] = ro[k] + rd[k] * s / 2.f;      // the sample position of lse_positions_fwd
+                positions_bwd_sample(p, g, contraction, box, gw);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) g[k] = gw[k];
+            }
+            const float len = sqrtf(fmaf(g[2], g[2], fmaf(g[1], g[1], g[0] * g[0])));
+            const float inv = -1.f / fmaxf(len, 1e-12f);
+            nx = fmaf(w, g[0] * inv, nx);
+            ny = fmaf(w, g[1] * inv, ny);
+            nz = fmaf(w, g[2] * inv, nz);
+        }
+        carry = carry + __shfl(incl, 63, 64);
+    }
+    nx = lse::wave_sum(nx); ny = lse::wave_sum(ny); nz = lse::wave_sum(nz);
+    if (lane == 0) {
+        if (flags & LSE_NORMALS_RENORMALIZE) {
+            const float len = sqrtf(fmaf(nz, nz, fmaf(ny, ny, nx * nx))) + 1e-10f;
+            nx = nx / len; ny = ny / len; nz = nz / len;
+        }
+        out[(int64_t)ray * 3 + 0] = nx; out[(int64_t)ray * 3 + 1] = ny; out[(int64_t)ray * 3 + 2] = nz;
+    }
+}
+
 // Early ray termination of the eval render (lse_eval_segment_begin / lse_eval_composite_segment / lse_eval_composite_finish): the
 // walk of eval_composite_kernel cut into segments of the ray, with the field evaluated between two segments only for the rays that
 // are still alive.  Sample k of a ray goes to lane k mod 64 there; every segment starts at a multiple of 64, so here the same lane
@@ -609,6 +685,26 @@ extern "C" int lse_eval_composite(const float *t_starts, const float *t_ends, co
     hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(1024), 0, st, (const float *)num, (const float *)out_acc,
                        (const float *)mid_range, n_rays, out_depth, (float *)nullptr);
     return lse::check_launch("lse_eval_composite");
+}
+
+extern "C" int lse_eval_composite_normals(const float *t_starts, const float *t_ends, const float *sigmas, const float *d_x01,
+                                          const int64_t *packed_info, int32_t n_rays, const float *rays_o, const float *rays_d,
+                                          int32_t contraction, const float *h_aabb, int32_t flags, float *out_normals,
+                                          lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_eval_composite_normals: n_rays < 0");
+    LSE_REQUIRE((flags & ~(LSE_NORMALS_WORLD | LSE_NORMALS_RENORMALIZE)) == 0, "lse_eval_composite_normals: unknown flags %d", flags);
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(t_starts && t_ends && sigmas && d_x01 && packed_info && out_normals, "lse_eval_composite_normals: null pointer");
+    Box box;
+    for (int k = 0; k < 3; ++k) { box.lo[k] = h_aabb ? h_aabb[k] : -1.f; box.hi[k] = h_aabb ? h_aabb[3 + k] : 1.f; }
+    if (flags & LSE_NORMALS_WORLD) {
+        LSE_REQUIRE(rays_o && rays_d, "lse_eval_composite_normals: world space needs rays_o and rays_d");
+        LSE_REQUIRE(contraction || h_aabb, "lse_eval_composite_normals: aabb normalisation needs h_aabb");
+    }
+    hipLaunchKernelGGL(eval_composite_normals_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), t_starts, t_ends,
+                       sigmas, d_x01, packed_info, n_rays, rays_o, rays_d, contraction, box, flags, out_normals);
+    return lse::check_launch("lse_eval_composite_normals");
 }
 
 extern "C" int lse_eval_segment_state_bytes(int32_t n_rays, int64_t *h_bytes)

@@ -162,6 +162,8 @@ def _image_dict(outputs: Dict[str, Tensor], gt_planes: Tensor, pred_planes: Tens
         images["overlay"] = overlay
     if outputs.get("ev_out") is not None:
         images["ev_out"] = outputs["ev_out"]
+    if outputs.get("normals") is not None:
+        images["normals"] = evaluation.normals_colormap(outputs["normals"], outputs["accumulation"])
     return images
 
 

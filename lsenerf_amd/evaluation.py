@@ -82,6 +82,8 @@ def _render_count_free(model, rb: RayBundle, chunk: int, check_overflow: bool = 
     depth = torch.empty(R, dtype=torch.float32, device=dev)
     nsamples = torch.empty(R, dtype=torch.int64, device=dev)
     ws = torch.empty(3 * min(chunk, R), dtype=torch.float32, device=dev)
+    normals = torch.empty((R, 3), dtype=torch.float32, device=dev) if model.eval_normals_on() else None
+    feats = {} if normals is not None else None
     linear = isinstance(model.renderer_rgb, LinearRenderer)
     bg = cfg.background_color
     background = None if bg in ("random", "last_sample") else {"black": 0.0, "white": 1.0}[bg]
@@ -94,12 +96,16 @@ def _render_count_free(model, rb: RayBundle, chunk: int, check_overflow: bool = 
             alpha_thre=cfg.alpha_thre, cone_angle=cfg.cone_angle)
         rays_o, rays_d = part.origins.contiguous(), part.directions.contiguous()
         table, eidx = fld._eval_emb(hi - lo, dev) if fld.embedding_appearance is not None else (None, None)
-        sigma, _, _, head = fld.density_rgb_packed(rays_o, rays_d, ri, ts, te, packed, eidx, table, n_dev)
+        sigma, _, _, head = fld.density_rgb_packed(rays_o, rays_d, ri, ts, te, packed, eidx, table, n_dev, features_out=feats)
         ops.eval_composite(ts, te, sigma, head, packed, rgb[lo:hi], acc[lo:hi], depth[lo:hi], nsamples[lo:hi],
                            nan_to_num=not linear, background=background, clamp=not linear, workspace=ws)
+        if normals is not None:
+            model.composite_normals(feats["x01"], feats["y"], ts, te, sigma, packed, rays_o, rays_d, normals[lo:hi], n_dev)
     if check_overflow:
         model.occupancy_grid.check_deferred_overflow()      # the one read-back: a truncated ray raises here
     raw = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": nsamples}
+    if normals is not None:
+        raw["normals"] = normals
     return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
 
 
@@ -211,6 +217,8 @@ def render_flat(model, rb: RayBundle, check_overflow: bool = True) -> Dict[str, 
         raise ValueError("empty ray bundle")
     if uses_count_free_route(model, len(rb)):
         if eps > 0.0:
+            if model.eval_normals_on():
+                raise ValueError("eval_normals is not built for the early-stop segment route: set eval_early_stop_eps = 0")
             return _render_early_stop(model, rb, chunk, check_overflow)
         return _render_count_free(model, rb, chunk, check_overflow)
     return _render_loop(model, rb, chunk)
@@ -295,6 +303,11 @@ def gray_colormap(image: Tensor, invert: bool = False) -> Tensor:
     return out.repeat(*([1] * (out.dim() - 1)), 3)
 
 
+def normals_colormap(normals: Tensor, accumulation: Tensor) -> Tensor:
+    """The picture of rendered normals as nerfstudio's viewer shows it: ``(n + 1) / 2`` blended with the accumulation onto white."""
+    return (normals + 1) / 2 * accumulation + (1 - accumulation)
+
+
 def depth_gray_map(depth: Tensor, accumulation: Tensor) -> Tensor:
     """nerfstudio 0.3.2 ``apply_depth_colormap(depth, accumulation, ColormapOptions(colormap="gray", invert=True))``: depth
     normalised by its own min / max, grey map inverted (near = white), blended with the accumulation onto white.  Restated, parity
@@ -336,6 +349,8 @@ def image_metrics_and_images(model, outputs: Dict[str, Tensor], batch: Dict[str,
         images["overlay"] = make_overlay(img_b, rgb_b)
     if outputs.get("ev_out") is not None:
         images["ev_out"] = outputs["ev_out"]
+    if outputs.get("normals") is not None:
+        images["normals"] = normals_colormap(outputs["normals"], outputs["accumulation"])
     ssim, mse = ops.image_metrics(img_b, rgb_b)
     psnr = 10.0 * torch.log10(1.0 / mse)
     values = torch.stack([psnr, ssim]).tolist()

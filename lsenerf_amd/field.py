@@ -30,6 +30,7 @@ class FieldHeadNames(Enum):
     RGB = "rgb"
     DENSITY = "density"
     PRED_NORMALS = "pred_normals"
+    NORMALS = "normals"
     UNCERTAINTY = "uncertainty"
     TRANSIENT_RGB = "transient_rgb"
     TRANSIENT_DENSITY = "transient_density"
@@ -551,12 +552,15 @@ class LSEField(nn.Module):
         return x01, sel, y
 
     def density_rgb_packed(self, rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, emb_idx: Optional[Tensor],
-                           emb_table: Optional[Tensor], n_dev: Optional[Tensor] = None
+                           emb_table: Optional[Tensor], n_dev: Optional[Tensor] = None, features_out: Optional[dict] = None
                            ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         """``density_packed`` followed by ``rgb_packed`` on the same samples: returns (sigma[N], h[N,16], selector[N], compact head
         output [N,4]).  With ``ops.MLP_FWD_PAIR`` and the production shapes the two MLP forwards are ONE launch (``ops.fused_mlp_pair``:
-        h stays in registers between them); otherwise the two calls, with the same bits."""
+        h stays in registers between them); otherwise the two calls, with the same bits.  ``features_out``: a dict that receives the
+        samples' ``x01`` and level-major hash features ``y`` (what ``normals_packed`` takes)."""
         x01, sel, y = self._encode_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, n_dev)
+        if features_out is not None:
+            features_out.update(x01=x01, y=y)
         n = x01.shape[0]
         base, head = self.mlp_base_mlp, self.mlp_head
         row_bias, head_meta = self._head_row_bias(rays_d, emb_idx, emb_table)
@@ -725,15 +729,54 @@ class LSEField(nn.Module):
             outputs[FieldHeadNames.PRED_NORMALS] = self.field_head_pred_normals(x)
         return outputs
 
+    # -- analytic normals (nerfstudio Field.get_normals: the negated, normalised gradient of the density logit) ------------
+    @torch.no_grad()
+    def normals_packed(self, x01: Tensor, y: Tensor, n_dev: Optional[Tensor] = None) -> Tensor:
+        """``d_x01[N,3]``: the gradient of the density logit ``h[:, 0]`` with respect to the unit-cube position, from the samples'
+        ``x01`` and level-major hash features ``y`` (``_encode_packed``).  Two forward-only launches: ``lse_density_logit_grad`` (the
+        base MLP's input gradient for the one-hot seed; always bf16x6, whatever ``inference_arith`` says) and ``lse_hash_bwd_input``
+        (a gather).  No autograd history; rows at or beyond ``n_dev[0]`` are unspecified.  The normal is
+        ``-d_x01 / max(|d_x01|, 1e-12)``."""
+        base = self.mlp_base_mlp
+        if base.in_pad != base.in_dim:
+            raise _lib.LseHipError("analytic normals need the 32-input base MLP (L * F == 32): the small-grid base MLP, whose input is "
+                                   "padded, has no density-logit gradient kernel")
+        d_y = ops.density_logit_grad(base.params.detach(), y.detach(), base.meta(), x01.shape[0], n_dev=n_dev)
+        return ops.hash_bwd_input(x01.detach(), d_y, self.mlp_base_grid.params.detach(), self.mlp_base_grid.meta, n_dev=n_dev)
+
+    @torch.no_grad()
+    def density_normals(self, positions: Tensor) -> Tuple[Tensor, Tensor]:
+        """positions [..,3] -> (density [..,1], analytic normals [..,3] in field space: unit vectors, zero where the gradient is)."""
+        p = positions.reshape(-1, 3).contiguous()
+        x01, sel, y = self._encode_packed(p, None, None, None, None, None)
+        sigma = self._base_mlp(y, sel, x01.shape[0])[1]
+        normals = -torch.nn.functional.normalize(self.normals_packed(x01, y), dim=-1)
+        return sigma.view(*positions.shape[:-1], 1), normals.view(*positions.shape[:-1], 3)
+
+    def _sample_normals(self, ray_samples: RaySamples) -> Tensor:
+        fr = ray_samples.frustums
+        rb, ridx, pinfo = self._packed_view(ray_samples)
+        with torch.no_grad():
+            if rb is not None:
+                x01, _, y = self._encode_packed(rb.origins.contiguous(), rb.directions.contiguous(), ridx, fr.starts.reshape(-1),
+                                                fr.ends.reshape(-1), pinfo)
+            else:
+                x01, _, y = self._encode_packed(fr.get_positions().reshape(-1, 3).contiguous(), None, None, None, None, None)
+            normals = -torch.nn.functional.normalize(self.normals_packed(x01, y), dim=-1)
+        return normals.view(*fr.shape, 3)
+
     def density_fn(self, positions: Tensor) -> Tensor:
         """nerfstudio ``Field.density_fn`` (wired at R:lse_nerf/lsenerf.py:193): positions [..,3] -> density [..,1]."""
         p = positions.reshape(-1, 3).contiguous()
         sigma, _, _ = self.density_packed(p, None, None, None, None, None)
         return sigma.view(*positions.shape[:-1], 1)
 
-    def forward(self, ray_samples: RaySamples) -> Dict[FieldHeadNames, Tensor]:
-        """nerfstudio ``Field.forward``: get_density -> get_outputs -> add DENSITY."""
+    def forward(self, ray_samples: RaySamples, compute_normals: bool = False) -> Dict[FieldHeadNames, Tensor]:
+        """nerfstudio ``Field.forward``: get_density -> get_outputs -> add DENSITY; ``compute_normals`` adds NORMALS, the analytic
+        normals of the samples (field space, no autograd history), on packed and on stock ``RaySamples``."""
         density, geo = self.get_density(ray_samples)
         out = self.get_outputs(ray_samples, density_embedding=geo)
         out[FieldHeadNames.DENSITY] = density
+        if compute_normals:
+            out[FieldHeadNames.NORMALS] = self._sample_normals(ray_samples)
         return out

@@ -95,6 +95,15 @@ class LSENeRFModelConfig:
     # (1.6e-3) and 48.9 dB (single pixels move by 0.09, depth by 0.34: the density logit is off by ~0.03).  Prefer "bf16x3";
     # "bf16x1" is the fast one and its images are for a trained scene to judge.
     eval_mlp_arith: str = "bf16x6"
+    # --- rendered analytic normals in the eval render: "off", "field" (the gradient of the density logit with respect to the
+    # normalised position, as nerfstudio's Field.get_normals has it) or "world" (that gradient through the transposed Jacobian of
+    # the contraction / aabb normalisation first).  With it on, eval-mode renders carry outputs["normals"] [.., 3]: per sample
+    # n = -g / max(|g|, 1e-12), per ray N = sum w n over the render weights, then N / (|N| + 1e-10) -- unit vectors, (0, 0, 0) for
+    # a ray without weight.  Per chunk this adds three forward-only launches (lse_density_logit_grad, lse_hash_bwd_input,
+    # lse_eval_composite_normals); the gradient always runs bf16x6, whatever ``eval_mlp_arith`` says.  Training mode never computes
+    # normals.  Not built for the early-stop segment route: together with ``eval_early_stop_eps > 0`` it is a ValueError in
+    # ``populate_modules``, and so is an unknown name.
+    eval_normals: str = "off"
 
     def __post_init__(self):   # R:lse_nerf/lsenerf.py:86-99
         if self.evs_mapping_method is None or str(self.evs_mapping_method).lower() == "none":
@@ -417,6 +426,11 @@ class LSENeRFModel(nn.Module):
         cfg = self.config
         if cfg.eval_mlp_arith not in ops.MLP_ARITH_ROUTES:
             raise ValueError(f"eval_mlp_arith {cfg.eval_mlp_arith!r}: one of {sorted(ops.MLP_ARITH_ROUTES)}")
+        if cfg.eval_normals not in ("off", "field", "world"):
+            raise ValueError(f"eval_normals {cfg.eval_normals!r}: one of 'off', 'field', 'world'")
+        if cfg.eval_normals != "off" and cfg.eval_early_stop_eps > 0:
+            raise ValueError("eval_normals is not built for the early-stop segment route: set eval_early_stop_eps = 0 "
+                             f"(got eval_normals={cfg.eval_normals!r}, eval_early_stop_eps={cfg.eval_early_stop_eps})")
         scene_contraction = None if cfg.disable_scene_contraction else SceneContraction(order=float("inf"))
         self.field = LSEField(aabb=self.scene_aabb_2x3, num_images=self.num_train_data,
                               log2_hashmap_size=cfg.log2_hashmap_size, max_res=cfg.max_res,
@@ -680,7 +694,9 @@ class LSENeRFModel(nn.Module):
             grid.dense_steps = not (self.config.cone_angle and self.config.cone_angle > 0)
         table, eidx = fld._ray_emb(ray_bundle.metadata, ray_bundle.camera_indices, num_rays, rays_o.device)
         # density_packed -> rgb_packed on the same samples (the two MLP forwards are one launch where the shapes allow)
-        sigma, _, _, rgb16 = fld.density_rgb_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, eidx, table, n_dev)
+        feats = {} if self.eval_normals_on() else None
+        sigma, _, _, rgb16 = fld.density_rgb_packed(rays_o, rays_d, ray_idx, t_starts, t_ends, packed_info, eidx, table, n_dev,
+                                                    features_out=feats)
         linear = isinstance(self.renderer_rgb, LinearRenderer)
         if not (self.training or linear):
             rgb16 = torch.nan_to_num(rgb16)
@@ -690,8 +706,27 @@ class LSENeRFModel(nn.Module):
             rgb = rgb + {"black": 0.0, "white": 1.0}[bg] * (1.0 - acc[:, None])
         if not (self.training or linear):
             rgb = torch.clamp(rgb, 0.0, 1.0)
-        return {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None],
-                "num_samples_per_ray": packed_info[:, 1]}
+        out = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": packed_info[:, 1]}
+        if feats is not None:
+            out["normals"] = torch.empty((num_rays, 3), dtype=torch.float32, device=rays_o.device)
+            self.composite_normals(feats["x01"], feats["y"], t_starts, t_ends, sigma, packed_info, rays_o, rays_d, out["normals"], n_dev)
+        return out
+
+    def eval_normals_on(self) -> bool:
+        """Whether this render carries "normals": ``config.eval_normals`` is on and the model is in eval mode."""
+        return self.config.eval_normals != "off" and not self.training
+
+    @torch.no_grad()
+    def composite_normals(self, x01: Tensor, y: Tensor, t_starts: Tensor, t_ends: Tensor, sigma: Tensor, packed_info: Tensor,
+                          rays_o: Tensor, rays_d: Tensor, out: Tensor, n_dev: Optional[Tensor] = None) -> None:
+        """The normals pass of one chunk, shared by ``render_packed`` and the count-free eval route: ``LSEField.normals_packed`` on
+        the chunk's samples, then ``lse_eval_composite_normals`` with the rendered ``sigma`` into ``out [n,3]``."""
+        fld = self.field
+        d_x01 = fld.normals_packed(x01, y, n_dev)
+        contraction = fld._contraction == "inf"
+        ops.eval_composite_normals(t_starts, t_ends, sigma.detach(), d_x01, packed_info, out,
+                                   world=self.config.eval_normals == "world", renormalize=True, rays_o=rays_o, rays_d=rays_d,
+                                   contraction=contraction, aabb6=None if contraction else fld._aabb_list())
 
     # -- output routing and losses (what R:lse_nerf/lsenerf.py:329-439 computes) ---------------------------------
     # One description of the routing (``_plan``) drives both implementations: ``route_outputs`` / ``get_loss_dict`` build

@@ -742,6 +742,40 @@ def mlp_bwd_input(params, x, meta: MlpMeta, n: int, out, out_cols: int, d_out, d
             _chk(row_bias_idx, torch.int32, "row_bias_idx", True), _f32(d_row_bias, "d_row_bias", True), n, _stream())
 
 
+def density_logit_shape(meta: MlpMeta) -> bool:
+    """The call ``lse_density_logit_grad`` serves: the 32 -> 64 -> 16 base without an output activation, in bf16x6 arithmetic."""
+    return meta.n_in == 32 and meta.width == 64 and meta.n_hidden_layers == 1 and meta.out_activation == _lib.LSE_ACT_NONE \
+        and meta.arith == _lib.LSE_MLP_ARITH_AUTO
+
+
+@torch.no_grad()
+def density_logit_grad(params, x, meta: MlpMeta, n: int, d_in=None, n_dev=None) -> torch.Tensor:
+    """``lse_density_logit_grad``: ``d_in = d(out[:, 0]) / d(x)`` of the base MLP (32 -> 64 -> 16, either input layout, bf16x6) --
+    what ``mlp_bwd_input`` gives for a ``d_out`` of (1, 0, .., 0), without the seed and without the output layer's product.  ``d_in``
+    (like ``x``; allocated when absent) is overwritten, rows at or beyond ``n_dev[0]`` are left alone; returned.  Any other shape or
+    arithmetic route raises before a launch."""
+    if d_in is None:
+        d_in = torch.empty_like(x)
+    elif d_in.shape != x.shape:
+        raise ValueError(f"density_logit_grad: d_in {tuple(d_in.shape)} must have the shape of the input {tuple(x.shape)}")
+    desc = meta.desc()
+    _call_n("lse_density_logit_grad", n_dev, ctypes.byref(desc), _f32(params, "params"), _f32(x, "mlp input"), _f32(d_in, "d_in"),
+            n, _stream())
+    return d_in
+
+
+@torch.no_grad()
+def hash_bwd_input(x01, dy, table, meta: GridMeta, dx=None, n_dev=None) -> torch.Tensor:
+    """``lse_hash_bwd_input``: ``dx[N,3]`` (allocated when absent; overwritten) from the level-major feature gradient ``dy`` -- a
+    gather over the table, no atomics, nothing table-sized written."""
+    if dx is None:
+        dx = torch.empty_like(x01)
+    desc = meta.desc()
+    _call_n("lse_hash_bwd_input", n_dev, ctypes.byref(desc), _f32(x01, "x01"), _f32(dy, "dy"), _f32(table, "table"),
+            _f32(dx, "dx"), x01.shape[0], _stream())
+    return dx
+
+
 def _mlp_bwd_recompute(params, x, meta: MlpMeta, n: int, out, out_cols: int, d_out, d_sigma, selector, density_scale, row_bias,
                        row_bias_idx, n_dev, *, input_only: bool, want_params: bool, want_in: bool, want_bias: bool, scratch=None):
     """The backward of one network on the route that saved nothing (act_tiled = 3): ``lse_mlp_bwd_input`` for frozen parameters
@@ -1351,6 +1385,36 @@ def eval_composite(t_starts, t_ends, sigmas, rgb, packed_info, out_rgb, out_acc,
               rgb.stride(0), _chk(packed_info, torch.int64, "packed_info"), n, flags,
               float(background) if background is not None else 0.0, _f32(workspace, "workspace"), _f32(out_rgb, "out_rgb"),
               _f32(out_acc, "out_acc"), _f32(out_depth, "out_depth"), _chk(out_nsamples, torch.int64, "out_nsamples"), _stream())
+
+
+@torch.no_grad()
+def eval_composite_normals(t_starts, t_ends, sigmas, d_x01, packed_info, out_normals, world: bool = False, renormalize: bool = True,
+                           rays_o=None, rays_d=None, contraction: bool = True, aabb6=None):
+    """Rendered normals of an evaluation render (lse_eval_composite_normals) into ``out_normals [n,3]`` -- a contiguous row block
+    (view) of the caller's image buffer: the render weights of ``eval_composite`` over the same samples applied to
+    ``-d_x01 / max(|d_x01|, 1e-12)``, then ``N / (|N| + 1e-10)`` with ``renormalize``.  ``d_x01 [N,3]`` is the gradient of the
+    density logit with respect to the unit-cube position (``LSEField.normals_packed``).  ``world``: the gradient goes through the
+    transposed Jacobian of the position map first, which needs ``rays_o`` / ``rays_d [n,3]`` and ``contraction`` or ``aabb6`` as
+    ``positions`` takes them.  Sample arrays may have capacity extent (``packed_info`` rows are authoritative)."""
+    n = packed_info.shape[0]
+    if n == 0:
+        return
+    if out_normals.shape != (n, 3):
+        raise ValueError("eval_composite_normals: out_normals [n,3] expected")
+    if d_x01.dim() != 2 or d_x01.shape[1] != 3:
+        raise ValueError("eval_composite_normals: d_x01 [N,3] expected")
+    flags = (_lib.LSE_NORMALS_WORLD if world else 0) | (_lib.LSE_NORMALS_RENORMALIZE if renormalize else 0)
+    aabb_arr = None
+    if world:
+        if rays_o is None or rays_d is None or rays_o.shape != (n, 3) or rays_d.shape != (n, 3):
+            raise ValueError("eval_composite_normals: world space needs rays_o and rays_d [n,3]")
+        if not contraction:
+            if aabb6 is None:
+                raise ValueError("eval_composite_normals: world space without contraction needs aabb6")
+            aabb_arr = (ctypes.c_float * 6)(*aabb6)
+    _lib.call("lse_eval_composite_normals", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(sigmas, "sigmas"),
+              _f32(d_x01, "d_x01"), _chk(packed_info, torch.int64, "packed_info"), n, _f32(rays_o, "rays_o", not world),
+              _f32(rays_d, "rays_d", not world), 1 if contraction else 0, aabb_arr, flags, _f32(out_normals, "out_normals"), _stream())
 
 
 def _eval_flags(nan_to_num: bool, background: Optional[float], clamp: bool) -> int:
