@@ -594,6 +594,49 @@ int lse_occ_update_cells_dev(float *occs, const int64_t *cell_ids, const float *
 int lse_occ_mean_threshold(const float *occs, int64_t n, float occ_thre, double *workspace, float *mean_all, float *threshold,
                            lse_stream_t stream);
 
+/* ---- mesh export (csrc/mesh.hip; ABI 6, additive): naive surface nets of a density lattice ------------------------------------
+ * Lattice.  res = (nx, ny, nz) cells, every count >= 1.  Points (ix, iy, iz), 0 <= i_k <= n_k, index
+ *   p = (ix * (ny + 1) + iy) * (nz + 1) + iz (fewer than 2^31 points), position_k = lo_k + ((float)i_k / (float)n_k) * (hi_k - lo_k)
+ *   in float32, every operation rounded on its own (the form of lse_occ_draw_cells).  Cells (cx, cy, cz), 0 <= c_k < n_k, index
+ *   c = (cx * ny + cy) * nz + cz; a cell's lowest corner is the point with its coordinates.  sigma: f32, one value per point.
+ * inside(p) = sigma[p] > level: NaN is outside.
+ * Vertices.  A cell is active when its 8 corners are neither all inside nor all outside; the vertices are the active cells in
+ *   ascending cell index.  The position is the mean of the crossings on the cell's 12 edges, visited as: axis a = 0, 1, 2 with
+ *   b = (a + 1) % 3, c = (a + 2) % 3; offset ob in (0, 1) along b (outer), oc in (0, 1) along c (inner); the edge runs from
+ *   P = cell + ob e_b + oc e_c to Q = P + e_a.  An edge with inside(P) != inside(Q) contributes the lattice-unit point P + t e_a,
+ *   t = (level - sigma[P]) / (sigma[Q] - sigma[P]), NaN replaced by 0.5, then clamped to [0, 1].  The three coordinates are summed
+ *   in float32 in that order, divided by (float)count and mapped to world as lo_k + (u_k / (float)n_k) * (hi_k - lo_k).
+ * Faces.  A lattice edge (p, a) from p to q = p + e_a (both in the lattice) with inside(p) != inside(q) that is interior in the
+ *   other two axes (1 <= p_b <= n_b - 1, 1 <= p_c <= n_c - 1) gives one quad over the cells C0 = p - e_b - e_c, C1 = p - e_c,
+ *   C2 = p, C3 = p - e_b (all active by construction): corners (C0, C1, C2, C3) if inside(p), else (C3, C2, C1, C0), so that the
+ *   geometric normal points from high to low density; triangles (w0, w1, w2), (w0, w2, w3) of int32 vertex ids; quads in ascending
+ *   (p, a).  Edges on the box surface give nothing: the mesh is open exactly where the surface leaves the box, and an active
+ *   boundary cell keeps its (possibly unreferenced) vertex.
+ *
+ * lse_lattice_positions: positions [n, 3] of the points first .. first + n (0 <= first, first + n <= points).
+ * lse_surface_nets_workspace: *h_bytes = size of the workspace the two passes share: per cell an int32 rank inside its segment
+ *   of LSE_MESH_SEGMENT consecutive cells, per segment of cells and of points an int64 offset.
+ * lse_surface_nets_count: fills the workspace and totals (device int64[2] = {vertices, quads}).  One wave per segment, ballot /
+ *   popcount ranks, one block per row scans the segment counts: fixed grids, no atomics, no host read.
+ * lse_surface_nets_emit: vertices f32 [cap_vertices, 3], triangles int32 [2 * cap_quads, 3] from the SAME sigma, resolution and
+ *   level as the count that filled the workspace (which it only reads).  Rows at or beyond a capacity are not written; totals keeps
+ *   the true counts, so a caller sizes exactly after one read or runs with fixed capacities.  Workspace and totals are 8-byte aligned. */
+#define LSE_MESH_SEGMENT 1024
+int lse_lattice_positions(const float *h_lo, const float *h_hi, int32_t nx, int32_t ny, int32_t nz, int64_t first, int64_t n,
+                          float *positions, lse_stream_t stream);
+int lse_surface_nets_workspace(int32_t nx, int32_t ny, int32_t nz, int64_t *h_bytes);
+int lse_surface_nets_count(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
+                           int64_t workspace_bytes, int64_t *totals, lse_stream_t stream);
+int lse_surface_nets_emit(const float *sigma, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi, float level,
+                          const void *workspace, int64_t workspace_bytes, int64_t cap_vertices, int64_t cap_quads, float *vertices,
+                          int32_t *triangles, lse_stream_t stream);
+/* World-space normals at n points: out[i] = -g / max(|g|, 1e-12) with g = J^T d_x01[i], J the Jacobian of the position map at
+ * positions[i] (what lse_positions_bwd applies: contraction or aabb normalisation by h_aabb[6], selector-masked) -- the per-sample
+ * arithmetic of lse_eval_composite_normals with LSE_NORMALS_WORLD.  d_x01, positions, out: f32 [n, 3]; n_dev: nullable device
+ * count as in the per-sample entry points; h_aabb is unused and nullable with contraction. */
+int lse_point_normals_world(const float *d_x01, const float *positions, int32_t contraction, const float *h_aabb, int64_t n,
+                            const int64_t *n_dev, float *out, lse_stream_t stream);
+
 /* ---- training epilogue: output routing + intensity mappers + both losses, O(rays), one launch each way
  *      (R:lse_nerf/lsenerf.py:329-377 routing, :392-439 losses; R:lse_nerf/intensity_mappers.py:64-94 mappers).
  * Colour bundle:  v = rgb_mapped ? m_rgb(max(rgb, 1e-5)) : rgb;  mean over deblur_group consecutive rays (the 4 virtual

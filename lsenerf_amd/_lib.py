@@ -27,6 +27,7 @@ LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
 LSE_NORMALS_WORLD, LSE_NORMALS_RENORMALIZE = 1, 2
 LSE_PREP_EVENT_STATS = 1
 LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
+LSE_MESH_SEGMENT = 1024
 LSE_PANEL_IMG, LSE_PANEL_DEPTH, LSE_PANEL_ERR_MAP, LSE_PANEL_OVERLAY, LSE_PANEL_EV_OUT = 1, 2, 4, 8, 16
 
 
@@ -190,6 +191,11 @@ SIGNATURES = {
     "lse_occ_draw_cells": [P, P, P, P, I32, I64, I32, I32, I32, I32, P, c_uint64, I64, P, P, P, P],
     "lse_occ_update_cells_dev": [P, P, P, F32, P, I64, F32, P, P],
     "lse_occ_mean_threshold": [P, I64, F32, P, P, P, P],
+    "lse_lattice_positions": [P, P, I32, I32, I32, I64, I64, P, P],
+    "lse_surface_nets_workspace": [I32, I32, I32, POINTER(c_int64)],
+    "lse_surface_nets_count": [P, I32, I32, I32, F32, P, I64, P, P],
+    "lse_surface_nets_emit": [P, I32, I32, I32, P, P, F32, P, I64, I64, I64, P, P, P],
+    "lse_point_normals_world": [P, P, I32, P, I64, P, P, P],
     "lse_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, I32, F32, P],
     "lse_adam_step_f64": [P, P, P, P, I64, c_double, c_double, c_double, c_double, I32, F32, P],
     "lse_adam_step_dev": [P, P, P, P, I64, P, F32, P],

@@ -633,6 +633,12 @@ class LSENeRFModel(nn.Module):
         from . import eval_set as _eval_set
         return _eval_set.evaluate_set(self, eval_set, events_only=events_only, on_image=on_image, panels=panels)
 
+    def extract_mesh(self, **kwargs):
+        """Triangle mesh of the field's density isosurface with analytic normals (``lsenerf_amd.mesh.extract_mesh``: resolution,
+        level, bounds, normals, colors, chunk).  Runs without gradients in eval mode and restores the model's mode."""
+        from . import mesh as _mesh
+        return _mesh.extract_mesh(self, **kwargs)
+
     def _ngp_metrics_dict(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]) -> Dict[str, Tensor]:
         image = batch["image"].to(outputs["rgb"].device)
         return {"psnr": self.psnr(outputs["rgb"], image), "num_samples_per_batch": outputs["num_samples_per_ray"].sum()}

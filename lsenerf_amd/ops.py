@@ -47,7 +47,7 @@ def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-_N_DEV_AT = {"lse_positions_fwd": 6, "lse_positions_bwd": 6, "lse_hash_bwd_ex": 10}     # elsewhere: right before the stream
+_N_DEV_AT = {"lse_positions_fwd": 6, "lse_positions_bwd": 6, "lse_hash_bwd_ex": 10, "lse_point_normals_world": 5}    # elsewhere: right before the stream
 
 
 def _call_n(name: str, n_dev: Optional[torch.Tensor], *args):
@@ -2133,3 +2133,118 @@ def occ_mean_threshold(occs, occ_thre: float, workspace, mean_all, threshold):
         raise ValueError("occ_mean_threshold: workspace needs 3 * LSE_OCC_MEAN_BLOCKS doubles")
     _lib.call("lse_occ_mean_threshold", _f32(occs, "occs"), occs.numel(), float(occ_thre), _chk(workspace, torch.float64, "workspace"),
               _f32(mean_all, "mean_all"), _f32(threshold, "threshold"), _stream())
+
+
+# ---- mesh export (csrc/mesh.hip; driven by lsenerf_amd.mesh.extract_mesh) ----
+def _res3(res) -> Tuple[int, int, int]:
+    r = tuple(int(v) for v in res) if hasattr(res, "__len__") else (int(res),) * 3
+    if len(r) != 3:
+        raise ValueError(f"resolution {res!r}: an int or three ints expected")
+    return r
+
+
+def _box3(lo, hi):
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("lo and hi: three floats each expected")
+    return (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
+
+
+def lattice_points(res) -> int:
+    nx, ny, nz = _res3(res)
+    return (nx + 1) * (ny + 1) * (nz + 1)
+
+
+@torch.no_grad()
+def lattice_positions(res, lo, hi, first: int = 0, n: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                      device="cuda") -> torch.Tensor:
+    """World positions [n, 3] of the lattice points ``first .. first + n`` of a ``res = (nx, ny, nz)``-cell lattice over the box
+    ``lo .. hi`` (lse_lattice_positions; point order and arithmetic: include/lse_hip.h, "mesh export").  ``n`` defaults to the rest
+    of the lattice; ``out``: a float32 [n, 3] buffer to write into."""
+    nx, ny, nz = _res3(res)
+    first = int(first)
+    n = lattice_points(res) - first if n is None else int(n)
+    if out is None:
+        out = torch.empty((max(n, 0), 3), dtype=torch.float32, device=device)
+    elif out.shape != (n, 3):
+        raise ValueError("lattice_positions: out [n, 3] expected")
+    c_lo, c_hi = _box3(lo, hi)
+    _lib.call("lse_lattice_positions", c_lo, c_hi, nx, ny, nz, first, n, _f32(out, "out") if n > 0 else None, _stream())
+    return out
+
+
+def surface_nets_workspace_bytes(res) -> int:
+    v = ctypes.c_int64(0)
+    _lib.call("lse_surface_nets_workspace", *_res3(res), ctypes.byref(v))
+    return int(v.value)
+
+
+@torch.no_grad()
+def surface_nets_count(sigma: torch.Tensor, res, level: float, workspace: torch.Tensor, totals: torch.Tensor) -> None:
+    """First pass of ``surface_nets``: fills ``workspace`` (uint8, ``surface_nets_workspace_bytes(res)``) and ``totals`` (int64 [2] on
+    the device: vertices, quads).  No host read."""
+    if sigma.numel() != lattice_points(res):
+        raise ValueError(f"surface_nets: sigma has {sigma.numel()} values, the lattice {lattice_points(res)} points")
+    _lib.call("lse_surface_nets_count", _f32(sigma, "sigma"), *_res3(res), float(level), _chk(workspace, torch.uint8, "workspace"),
+              workspace.numel(), _chk(totals, torch.int64, "totals"), _stream())
+
+
+@torch.no_grad()
+def surface_nets_emit(sigma: torch.Tensor, res, lo, hi, level: float, workspace: torch.Tensor, vertices: torch.Tensor,
+                      triangles: torch.Tensor) -> None:
+    """Second pass of ``surface_nets`` with the workspace ``surface_nets_count`` filled for the same ``sigma``, ``res`` and ``level``:
+    writes ``vertices`` (float32 [cap_vertices, 3]) and ``triangles`` (int32 [2 * cap_quads, 3]); rows beyond a buffer are dropped."""
+    if sigma.numel() != lattice_points(res):
+        raise ValueError(f"surface_nets: sigma has {sigma.numel()} values, the lattice {lattice_points(res)} points")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.shape[0] % 2:
+        raise ValueError("surface_nets: vertices [cap_vertices, 3] and triangles [2 * cap_quads, 3] expected")
+    c_lo, c_hi = _box3(lo, hi)
+    cap_v, cap_q = vertices.shape[0], triangles.shape[0] // 2
+    _lib.call("lse_surface_nets_emit", _f32(sigma, "sigma"), *_res3(res), c_lo, c_hi, float(level),
+              _chk(workspace, torch.uint8, "workspace"), workspace.numel(), cap_v, cap_q,
+              _f32(vertices, "vertices") if cap_v else None, _chk(triangles, torch.int32, "triangles") if cap_q else None, _stream())
+
+
+@torch.no_grad()
+def surface_nets(sigma: torch.Tensor, res, lo, hi, level: float, caps: Optional[Tuple[int, int]] = None):
+    """Naive surface nets of the density lattice ``sigma`` (float32, one value per point of the ``res``-cell lattice over the box
+    ``lo .. hi``, iz fastest) at the iso value ``level``: ``(vertices [V, 3] float32, triangles [2 Q, 3] int32, totals int64 [2])``.
+    The definition -- one vertex per active cell, one quad per sign-changing interior lattice edge, ordered, deterministic -- is in
+    include/lse_hip.h ("mesh export").  Without ``caps`` the buffers are sized from ONE host read of ``totals`` between the two
+    passes; with ``caps = (cap_vertices, cap_quads)`` nothing is read, the buffers have the capacities' extent, rows beyond the true
+    counts are left unwritten and ``totals`` (on the device) says how many there are."""
+    sigma = _c(sigma.detach()).reshape(-1)
+    dev = sigma.device
+    ws = torch.empty(surface_nets_workspace_bytes(res), dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    surface_nets_count(sigma, res, level, ws, totals)
+    if caps is None:
+        n_v, n_q = (int(v) for v in totals.tolist())
+    else:
+        n_v, n_q = int(caps[0]), int(caps[1])
+    vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+    triangles = torch.empty((2 * n_q, 3), dtype=torch.int32, device=dev)
+    surface_nets_emit(sigma, res, lo, hi, level, ws, vertices, triangles)
+    return vertices, triangles, totals
+
+
+@torch.no_grad()
+def point_normals_world(d_x01: torch.Tensor, positions: torch.Tensor, contraction: bool = True, aabb6=None,
+                        out: Optional[torch.Tensor] = None, n_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """World-space normals [n, 3] at ``positions`` from ``d_x01`` (``LSEField.normals_packed``): the gradient through the transposed
+    Jacobian of the position map (``contraction`` or ``aabb6`` as ``positions`` takes them), then ``-g / max(|g|, 1e-12)`` -- unit
+    vectors, zero where the gradient is or the point lies outside the field's domain (lse_point_normals_world)."""
+    n = d_x01.shape[0]
+    if d_x01.shape != (n, 3) or positions.shape != (n, 3):
+        raise ValueError("point_normals_world: d_x01 and positions [n, 3] expected")
+    if not contraction and aabb6 is None:
+        raise ValueError("point_normals_world: aabb normalisation needs aabb6")
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=d_x01.device)
+    elif out.shape != (n, 3):
+        raise ValueError("point_normals_world: out [n, 3] expected")
+    aabb_arr = None if aabb6 is None else (ctypes.c_float * 6)(*[float(v) for v in aabb6])
+    if n > 0:
+        _call_n("lse_point_normals_world", n_dev, _f32(d_x01, "d_x01"), _f32(positions, "positions"), 1 if contraction else 0, aabb_arr,
+                n, _f32(out, "out"), _stream())
+    return out
