@@ -479,6 +479,45 @@ __device__ __forceinline__ void stage_first_image(u32x4 *img0, const float *W0, 
     else stage_in16_image_rn<4, NP>(img0, W0, ld, mask0, nthreads);
 }
 
+// One tile through one network <KIN, NHL>: the first layer on top of what h holds (zero or the per-row bias), the second hidden
+// layer for NHL == 2, the output layer into o.  The SINGLE definition of the layer sequence of the bf16 forwards: mlp_fwd3_kernel
+// runs it once per tile and mlp_fwd_pair_kernel twice (base, then head on the base's o), so one launch and two carry the same bits
+// on every route NP.  store(layer, rb, ct, block) sees every hidden block after its ReLU (the saved activations of mlp_fwd3_kernel).
+template <int KIN, int NHL, int CT, int NP, typename NI, typename Store>
+__device__ __forceinline__ void network_tile_x6(f32x4 (&h)[4][CT], const f32x4 (&raw)[CT][KIN / 16], const u32x4 *img0,
+                                                const u32x4 *imgH, const u32x4 *imgO, const NI &nI, int lane, f32x4 (&o)[1][CT],
+                                                Store store)
+{
+    first_layer_x6<KIN, CT, NP>(h, img0, raw, nI, lane);
+    PiecesB<4> x[CT];
+#pragma unroll
+    for (int layer = 0; layer < NHL; ++layer) {
+        if (layer > 0) {      // x holds the previous layer's output, so h is free to take this one's
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            layer_x6_ct<4, 2, CT, NP>(h, imgH, x, lane);
+        }
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) h[rb][ct][r] = relu_bits(h[rb][ct][r]);
+                store(layer, rb, ct, h[rb][ct]);
+            }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) o[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    layer_x6_ct<1, 2, CT, NP>(o, imgO, x, lane);
+}
+
 template <int KIN, int NHL, int INL, int NP = 3>
 __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 {
@@ -527,53 +566,18 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
         f32x4 h[HB][CT];
         init_h_from_row_bias<HB, WIDTH, CT>(a, n, tile, t_end, j, q, sl, idx_nx, h);
         if (tile + 1 < t_end) load_in_x6<KIN, INL, CT>(a, tile + 1, j, q, raw_nx);
-        // ---- layer 0
-        first_layer_x6<KIN, CT, NP>(h, img0, raw, nI, lane);
+        // saved activations [layer][ct][rb][lane][4] of the tile; act_tiled = 2: the backward recomputes the first hidden layer
         float *act0_t = a.act ? a.act + tile * (CT * HB * 256) : nullptr;
         const bool st1 = 16 < n_rem;
-        const bool skip0 = NHL == 2 && a.act_tiled == 2;      // the backward recomputes the first hidden layer
-#pragma unroll
-        for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h[rb][ct][r] = relu_bits(h[rb][ct][r]);
-                if (act0_t && !skip0 && (ct == 0 || st1)) store_act(act0_t + (unsigned)(((ct * HB + rb) * 64 + lane) * 4), h[rb][ct], nt);
-            }
-        PiecesB<HB> x[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- hidden layer
-        if constexpr (NHL == 2) {
-            f32x4 h2[HB][CT];
-#pragma unroll
-            for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) h2[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<HB, 2, CT, NP>(h2, imgH, x, lane);
-            float *act1_t = act0_t ? act0_t + (skip0 ? 0 : a.act_layer_stride) : nullptr;
-#pragma unroll
-            for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h2[rb][ct][r] = relu_bits(h2[rb][ct][r]);
-                    if (act1_t && (ct == 0 || st1)) store_act(act1_t + (unsigned)(((ct * HB + rb) * 64 + lane) * 4), h2[rb][ct], nt);
-                }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h2[2 * s2][ct], h2[2 * s2 + 1][ct], nI, x[ct].p[s2]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- output layer
+        const bool skip0 = NHL == 2 && a.act_tiled == 2;
         f32x4 o[1][CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) o[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        layer_x6_ct<1, 2, CT, NP>(o, imgO, x, lane);
+        network_tile_x6<KIN, NHL, CT, NP>(h, raw, img0, imgH, imgO, nI, lane, o,
+                                          [&](int layer, int rb, int ct, const f32x4 &v) __attribute__((always_inline)) {
+            if (act0_t && !(layer == 0 && skip0) && (ct == 0 || st1)) {
+                float *act_t = act0_t + ((layer == 0 || skip0) ? 0 : a.act_layer_stride);      // act_tiled = 2: layer 1 in layer 0's place
+                store_act(act_t + (unsigned)(((ct * HB + rb) * 64 + lane) * 4), v, nt);
+            }
+        });
         float *out_t = a.out + tile_base * oc;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -595,9 +599,9 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(MlpArgs a, bool nt)
 // The base's output accumulator o[0][ct] (C/D layout: lane (j, q) holds columns 4q .. 4q+3 of sample j) IS the head's k = 16
 // input raw[ct][0] of load_in_x6 / split_in16: per tile the base runs, stores h and sigma, and the head continues on the same
 // registers -- h is written once and never read back, one launch / weight-staging prologue / tail instead of two, and the head's
-// MFMA chains run in the waves that would otherwise wait for the next tile's y.  Both phases are the code of mlp_fwd3_kernel
-// (same pieces, same MFMA order per layer, same epilogues), so h, sigma and the head output carry the same bits as two launches
-// and the recomputing backward reproduces them.  Nothing is saved (act_tiled = 3 only).
+// MFMA chains run in the waves that would otherwise wait for the next tile's y.  Both phases run network_tile_x6, the layer
+// sequence of mlp_fwd3_kernel, and keep that kernel's epilogues, so h, sigma and the head output carry the same bits as two
+// launches and the recomputing backward reproduces them.  Nothing is saved (act_tiled = 3 only).
 // ------------------------------------------------------------------------------------------------------
 template <int INL, int NP = 3>
 struct X6FwdPair {
@@ -635,6 +639,7 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
     wave_tile_range<CT, NW>(n, wave, t_begin, t_end);
     const int oc = b.out_cols;
     const NegI nI{img + C::NEGI + lane};
+    const auto no_store = [](int, int, int, const f32x4 &) __attribute__((always_inline)) {};      // nothing is saved
 
     f32x4 raw_nx[CT][2];
     if (t_begin < t_end) load_in_x6<32, INL, CT>(a, t_begin, j, q, raw_nx);
@@ -662,22 +667,7 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) h[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (tile + 1 < t_end) load_in_x6<32, INL, CT>(a, tile + 1, j, q, raw_nx);
-            first_layer_x6<32, CT, NP>(h, b_img0, raw, nI, lane);
-#pragma unroll
-            for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h[rb][ct][r] = relu_bits(h[rb][ct][r]);
-            PiecesB<HB> x[CT];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) o[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<1, 2, CT, NP>(o, b_imgO, x, lane);
+            network_tile_x6<32, 1, CT, NP>(h, raw, b_img0, nullptr, b_imgO, nI, lane, o, no_store);
             float *h_t = a.out + tile_base * 16;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
@@ -694,40 +684,8 @@ __global__ __launch_bounds__(512) void mlp_fwd_pair_kernel(MlpArgs a /* base */,
             f32x4 rawh[CT][1];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) rawh[ct][0] = o[0][ct];
-            first_layer_x6<16, CT, NP>(h, h_img0, rawh, nI, lane);
-#pragma unroll
-            for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h[rb][ct][r] = relu_bits(h[rb][ct][r]);
-            PiecesB<HB> x[CT];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h[2 * s2][ct], h[2 * s2 + 1][ct], nI, x[ct].p[s2]);
-            __builtin_amdgcn_sched_barrier(0);
-            f32x4 h2[HB][CT];
-#pragma unroll
-            for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) h2[rb][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<HB, 2, CT, NP>(h2, h_imgH, x, lane);
-#pragma unroll
-            for (int rb = 0; rb < HB; ++rb)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h2[rb][ct][r] = relu_bits(h2[rb][ct][r]);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) split_pair<NP>(h2[2 * s2][ct], h2[2 * s2 + 1][ct], nI, x[ct].p[s2]);
-            __builtin_amdgcn_sched_barrier(0);
             f32x4 r[1][CT];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) r[0][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            layer_x6_ct<1, 2, CT, NP>(r, h_imgO, x, lane);
+            network_tile_x6<16, 2, CT, NP>(h, rawh, h_img0, h_imgH, h_imgO, nI, lane, r, no_store);
             float *out_t = b.out + tile_base * oc;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {

@@ -23,6 +23,51 @@ __device__ __forceinline__ float wave_inclusive_sum_rev(float v)
     return v;
 }
 
+// Weights of one 64-sample group of a ray (sample k of the ray on lane k mod 64): T, alpha and w = T * alpha of this lane's sample
+// [a, b) with density sg; `carry` is the optical depth in front of the group and is advanced past it.  The SINGLE definition of the
+// scan: the training forward and the three eval compositors call it and so agree bit for bit (tests/test_gpu_eval.py,
+// tests/test_gpu_compositing.py).  Contraction is off and the one fused step is written out: the first step of the sigma * dt prefix
+// scan is fmaf(sg, dt, neighbour); the other five steps, excl + carry and the carry update are plain adds, T * alpha a plain product.
+// The exclusive prefix is the inclusive one shifted by a lane (as in visibility_kernel), not `incl - sd`: a surface sample of a
+// trained scene has sd = 1e2 .. 1e5 and beyond, and the subtraction would return the optical depth in front of it -- which decides
+// that sample's weight, the largest of the ray -- to half an ulp of sd; at sd = +inf it is inf - inf = NaN.
+struct GroupWeights { float w, T, alpha; };
+
+__device__ __forceinline__ GroupWeights group_weights(float a, float b, float sg, bool valid, int lane, float &carry)
+{
+#pragma clang fp contract(off)
+    const float dt = b - a;
+    const float sd = sg * dt;
+    float incl = sd;
+    {
+        const float nb = __shfl_up(incl, 1, 64);
+        if (lane >= 1) incl = fmaf(sg, dt, nb);
+    }
+#pragma unroll
+    for (int off = 2; off < 64; off <<= 1) {
+        const float nb = __shfl_up(incl, off, 64);
+        if (lane >= off) incl = incl + nb;
+    }
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.f;
+    GroupWeights g;
+    g.T = expf(-(excl + carry));
+    g.alpha = 1.f - expf(-sd);
+    g.w = valid ? g.T * g.alpha : 0.f;
+    carry = carry + __shfl(incl, 63, 64);
+    return g;
+}
+
+// smallest / largest interval mid-point over the wave (DepthRenderer's clip range of the ray); min / max are exact in any order
+__device__ __forceinline__ void wave_mid_range(float &mlo, float &mhi)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mlo = fminf(mlo, __shfl_xor(mlo, off, 64));
+        mhi = fmaxf(mhi, __shfl_xor(mhi, off, 64));
+    }
+}
+
 __global__ __launch_bounds__(256) void volrend_fwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                           const float *__restrict__ sigma, const float *__restrict__ rgb,
                                                           int rgb_stride, const int64_t *__restrict__ packed, int n_rays,
@@ -42,20 +87,12 @@ __global__ __launch_bounds__(256) void volrend_fwd_kernel(const float *__restric
         const bool valid = base + lane < cnt;
         float a = 0.f, b = 0.f, sg = 0.f;
         if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
-        const float sd = sg * (b - a);
-        const float incl = lse::wave_inclusive_sum(sd);
-        // exclusive prefix = the inclusive one shifted by a lane (as in visibility_kernel), not `incl - sd`: a surface sample of a
-        // trained scene has sd = 1e2 .. 1e5 and beyond, and the subtraction would return the optical depth in front of it -- which
-        // decides that sample's weight, the largest of the ray -- to half an ulp of sd; at sd = +inf it is inf - inf = NaN
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 0.f;
-        const float T = expf(-(excl + carry));
-        const float alpha = 1.f - expf(-sd);
-        const float w = valid ? T * alpha : 0.f;
+        const GroupWeights g = group_weights(a, b, sg, valid, lane, carry);
+        const float w = g.w;
         if (valid) {
             weights[i] = w;
-            if (trans) trans[i] = T;
-            if (alphas) alphas[i] = alpha;
+            if (trans) trans[i] = g.T;
+            if (alphas) alphas[i] = g.alpha;
             mlo = fminf(mlo, (a + b) * 0.5f);
             mhi = fmaxf(mhi, (a + b) * 0.5f);
             if (rgb) {
@@ -67,17 +104,10 @@ __global__ __launch_bounds__(256) void volrend_fwd_kernel(const float *__restric
             aw += w;
             ad = fmaf(w, (a + b) * 0.5f, ad);
         }
-        carry += __shfl(incl, 63, 64);
     }
     ar = lse::wave_sum(ar); ag = lse::wave_sum(ag); ab = lse::wave_sum(ab);
     aw = lse::wave_sum(aw); ad = lse::wave_sum(ad);
-    if (mid_range) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mlo = fminf(mlo, __shfl_xor(mlo, off, 64));
-            mhi = fmaxf(mhi, __shfl_xor(mhi, off, 64));
-        }
-    }
+    if (mid_range) wave_mid_range(mlo, mhi);
     if (lane == 0) {
         if (out_rgb) { out_rgb[ray * 3 + 0] = ar; out_rgb[ray * 3 + 1] = ag; out_rgb[ray * 3 + 2] = ab; }
         if (out_acc) out_acc[ray] = aw;
@@ -135,76 +165,38 @@ __device__ __forceinline__ float clamp01(float v)
     return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
 }
 
-// Forward-only compositing of an evaluation render (lse_eval_composite): the per-ray walk of volrend_fwd_kernel with the SAME
-// arithmetic -- contraction is off in this body and every fused step is an explicit fmaf, so that the contraction choices the
-// compiler made in volrend_fwd_kernel are reproduced, not re-decided (HIP's __fadd_rn / __fmul_rn are plain operators whose fusing
-// follows the flags of their own definition, so they cannot pin this): the first step of the sigma*dt prefix scan is a fused multiply-add there (sd + neighbour, sd = sigma * dt), the
-// accumulation sum is a plain add, the colour / depth sums are fmaf; the exclusive prefix (inclusive scan shifted one lane, + carry)
-// and w = T * alpha have nothing to fuse.  These sites are read off the gfx950 ISA of volrend_fwd_kernel (hipcc -S: one v_fmac_f32
-// after the first ds_bpermute of the scan, v_add_f32 for the other five steps, for excl + carry and for aw, v_pk_fma_f32 / v_fmac_f32
-// for rgb and depth) and were re-derived when the prefix changed from `incl - sd` to the shift; tests/test_gpu_eval.py and
-// tests/test_gpu_compositing.py hold the two kernels together bit for bit.  No per-sample weights are stored.  Lane 0 applies the
-// renderer epilogue of LSENeRFModel.render_packed per ray; the depth numerator and the ray's mid-point range go to the workspace
-// for eval_depth_finish (depth_finish_kernel: the chunk-wide clip range of DepthRenderer("expected")).
-__global__ __launch_bounds__(256) void eval_composite_kernel(const float *__restrict__ ts, const float *__restrict__ te,
-                                                             const float *__restrict__ sigma, const float *__restrict__ rgb,
-                                                             int rgb_stride, const int64_t *__restrict__ packed, int n_rays,
-                                                             int flags, float background, float *__restrict__ mid_range,
-                                                             float *__restrict__ num, float *__restrict__ out_rgb,
-                                                             float *__restrict__ out_acc, int64_t *__restrict__ out_nsamples)
+// Lane accumulators of an eval render's ray: colour, accumulation, depth numerator and the range of the interval mid-points
+struct RayAccum {
+    float r, g, b, w, d, mlo, mhi;
+};
+
+// One valid sample into the lane accumulators (eval_composite_kernel and its segmented form): colour and depth numerator by fmaf,
+// the accumulation by a plain add, as volrend_fwd_kernel forms them.
+__device__ __forceinline__ void accumulate_sample(RayAccum &acc, float w, float a, float b, const float *__restrict__ c, bool fix_nan)
 {
-#pragma clang fp contract(off)   // every + - * below rounds on its own; the fused steps are the explicit fmaf
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
-    const bool fix_nan = (flags & LSE_EVAL_NAN_TO_NUM) != 0;
-    float carry = 0.f, ar = 0.f, ag = 0.f, ab = 0.f, aw = 0.f, ad = 0.f;
-    float mlo = INFINITY, mhi = -INFINITY;
-    for (int64_t base = 0; base < cnt; base += 64) {
-        const int64_t i = s0 + base + lane;
-        const bool valid = base + lane < cnt;
-        float a = 0.f, b = 0.f, sg = 0.f;
-        if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
-        const float dt = b - a;
-        const float sd = sg * dt;
-        float incl = sd;
-        {
-            const float nb = __shfl_up(incl, 1, 64);
-            if (lane >= 1) incl = fmaf(sg, dt, nb);
-        }
-#pragma unroll
-        for (int off = 2; off < 64; off <<= 1) {
-            const float nb = __shfl_up(incl, off, 64);
-            if (lane >= off) incl = incl + nb;
-        }
-        float excl = __shfl_up(incl, 1, 64);     // shifted, not `incl - sd`: see volrend_fwd_kernel
-        if (lane == 0) excl = 0.f;
-        const float T = expf(-(excl + carry));
-        const float alpha = 1.f - expf(-sd);
-        const float w = valid ? T * alpha : 0.f;
-        if (valid) {
-            const float mid = (a + b) * 0.5f;
-            mlo = fminf(mlo, mid);
-            mhi = fmaxf(mhi, mid);
-            const float *c = rgb + i * rgb_stride;
-            float c0 = c[0], c1 = c[1], c2 = c[2];
-            if (fix_nan) { c0 = nan_to_num(c0); c1 = nan_to_num(c1); c2 = nan_to_num(c2); }
-            ar = fmaf(w, c0, ar);
-            ag = fmaf(w, c1, ag);
-            ab = fmaf(w, c2, ab);
-            aw = aw + w;
-            ad = fmaf(w, mid, ad);
-        }
-        carry = carry + __shfl(incl, 63, 64);
-    }
-    ar = lse::wave_sum(ar); ag = lse::wave_sum(ag); ab = lse::wave_sum(ab);
-    aw = lse::wave_sum(aw); ad = lse::wave_sum(ad);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mlo = fminf(mlo, __shfl_xor(mlo, off, 64));
-        mhi = fmaxf(mhi, __shfl_xor(mhi, off, 64));
-    }
+#pragma clang fp contract(off)
+    const float mid = (a + b) * 0.5f;
+    acc.mlo = fminf(acc.mlo, mid);
+    acc.mhi = fmaxf(acc.mhi, mid);
+    float c0 = c[0], c1 = c[1], c2 = c[2];
+    if (fix_nan) { c0 = nan_to_num(c0); c1 = nan_to_num(c1); c2 = nan_to_num(c2); }
+    acc.r = fmaf(w, c0, acc.r);
+    acc.g = fmaf(w, c1, acc.g);
+    acc.b = fmaf(w, c2, acc.b);
+    acc.w = acc.w + w;
+    acc.d = fmaf(w, mid, acc.d);
+}
+
+// The end of an eval render's ray (eval_composite_kernel and eval_segment_finish_kernel): the five wave reductions in this order,
+// then on lane 0 the renderer epilogue of LSENeRFModel.render_packed; the depth numerator and the ray's mid-point range (acc.mlo /
+// acc.mhi, already reduced) go to the workspace for depth_finish_kernel (the chunk-wide clip range of DepthRenderer("expected")).
+__device__ __forceinline__ void finish_ray(RayAccum acc, int64_t nsamples, int lane, int ray, int flags, float background,
+                                           float *__restrict__ mid_range, float *__restrict__ num, float *__restrict__ out_rgb,
+                                           float *__restrict__ out_acc, int64_t *__restrict__ out_nsamples)
+{
+#pragma clang fp contract(off)
+    float ar = lse::wave_sum(acc.r), ag = lse::wave_sum(acc.g), ab = lse::wave_sum(acc.b);
+    const float aw = lse::wave_sum(acc.w), ad = lse::wave_sum(acc.d);
     if (lane == 0) {
         if (flags & LSE_EVAL_BACKGROUND) {     // rgb + bg * (1 - acc)
             const float rest = background * (1.f - aw);
@@ -214,25 +206,53 @@ __global__ __launch_bounds__(256) void eval_composite_kernel(const float *__rest
         out_rgb[ray * 3 + 0] = ar; out_rgb[ray * 3 + 1] = ag; out_rgb[ray * 3 + 2] = ab;
         out_acc[ray] = aw;
         num[ray] = ad;
-        mid_range[2 * ray] = mlo; mid_range[2 * ray + 1] = mhi;
-        out_nsamples[ray] = cnt;
+        mid_range[2 * ray] = acc.mlo; mid_range[2 * ray + 1] = acc.mhi;
+        out_nsamples[ray] = nsamples;
     }
+}
+
+// Forward-only compositing of an evaluation render (lse_eval_composite): the per-ray walk of volrend_fwd_kernel with its weights
+// (group_weights) and no per-sample output; eval_depth_finish follows (depth_finish_kernel).
+__global__ __launch_bounds__(256) void eval_composite_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                             const float *__restrict__ sigma, const float *__restrict__ rgb,
+                                                             int rgb_stride, const int64_t *__restrict__ packed, int n_rays,
+                                                             int flags, float background, float *__restrict__ mid_range,
+                                                             float *__restrict__ num, float *__restrict__ out_rgb,
+                                                             float *__restrict__ out_acc, int64_t *__restrict__ out_nsamples)
+{
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
+    const bool fix_nan = (flags & LSE_EVAL_NAN_TO_NUM) != 0;
+    float carry = 0.f;
+    RayAccum acc = {0.f, 0.f, 0.f, 0.f, 0.f, INFINITY, -INFINITY};
+    for (int64_t base = 0; base < cnt; base += 64) {
+        const int64_t i = s0 + base + lane;
+        const bool valid = base + lane < cnt;
+        float a = 0.f, b = 0.f, sg = 0.f;
+        if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
+        const float w = group_weights(a, b, sg, valid, lane, carry).w;
+        if (valid) accumulate_sample(acc, w, a, b, rgb + i * rgb_stride, fix_nan);
+    }
+    wave_mid_range(acc.mlo, acc.mhi);
+    finish_ray(acc, cnt, lane, ray, flags, background, mid_range, num, out_rgb, out_acc, out_nsamples);
 }
 
 #include "positions.h"      // Box, positions_bwd_sample: the world-space Jacobian of the normals
 
-// Rendered normals of an evaluation render (lse_eval_composite_normals): the sample-to-lane walk and the weight arithmetic of
-// eval_composite_kernel (the same prefix scan with the same fused step, the same carry, w = T * alpha), with a vector in place of
-// the colour.  Per sample: g = d_x01 (the gradient of the density logit), optionally through the transposed Jacobian of the position
-// map at the sample's position (LSE_NORMALS_WORLD), n = -g / max(|g|, 1e-12) (F.normalize: a zero gradient gives a zero normal);
-// per ray N = sum w n, then N / (|N| + 1e-10) with LSE_NORMALS_RENORMALIZE (NormalsRenderer).  A ray without samples writes zeros.
+// Rendered normals of an evaluation render (lse_eval_composite_normals): the sample-to-lane walk and the weights of
+// eval_composite_kernel (group_weights), with a vector in place of the colour.  Per sample: g = d_x01 (the gradient of the density
+// logit), optionally through the transposed Jacobian of the position map at the sample's position (LSE_NORMALS_WORLD),
+// n = -g / max(|g|, 1e-12) (F.normalize: a zero gradient gives a zero normal); per ray N = sum w n, then N / (|N| + 1e-10) with
+// LSE_NORMALS_RENORMALIZE (NormalsRenderer).  A ray without samples writes zeros.
 __global__ __launch_bounds__(256) void eval_composite_normals_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                                      const float *__restrict__ sigma, const float *__restrict__ dx01,
                                                                      const int64_t *__restrict__ packed, int n_rays,
                                                                      const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                                      int contraction, Box box, int flags, float *__restrict__ out)
 {
-#pragma clang fp contract(off)   // the weight arithmetic is eval_composite_kernel's, operation by operation
+#pragma clang fp contract(off)   // the normal arithmetic below rounds step by step; the weights are group_weights'
     const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
     const int lane = threadIdx.x & 63;
@@ -249,23 +269,7 @@ __global__ __launch_bounds__(256) void eval_composite_normals_kernel(const float
         const bool valid = base + lane < cnt;
         float a = 0.f, b = 0.f, sg = 0.f;
         if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
-        const float dt = b - a;
-        const float sd = sg * dt;
-        float incl = sd;
-        {
-            const float nb = __shfl_up(incl, 1, 64);
-            if (lane >= 1) incl = fmaf(sg, dt, nb);
-        }
-#pragma unroll
-        for (int off = 2; off < 64; off <<= 1) {
-            const float nb = __shfl_up(incl, off, 64);
-            if (lane >= off) incl = incl + nb;
-        }
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 0.f;
-        const float T = expf(-(excl + carry));
-        const float alpha = 1.f - expf(-sd);
-        const float w = valid ? T * alpha : 0.f;
+        const float w = group_weights(a, b, sg, valid, lane, carry).w;
         if (valid) {
             float g[3] = {dx01[i * 3 + 0], dx01[i * 3 + 1], dx01[i * 3 + 2]};
             if (world) {
@@ -283,7 +287,6 @@ __global__ __launch_bounds__(256) void eval_composite_normals_kernel(const float
             ny = fmaf(w, g[1] * inv, ny);
             nz = fmaf(w, g[2] * inv, nz);
         }
-        carry = carry + __shfl(incl, 63, 64);
     }
     nx = lse::wave_sum(nx); ny = lse::wave_sum(ny); nz = lse::wave_sum(nz);
     if (lane == 0) {
@@ -298,10 +301,10 @@ __global__ __launch_bounds__(256) void eval_composite_normals_kernel(const float
 // Early ray termination of the eval render (lse_eval_segment_begin / lse_eval_composite_segment / lse_eval_composite_finish): the
 // walk of eval_composite_kernel cut into segments of the ray, with the field evaluated between two segments only for the rays that
 // are still alive.  Sample k of a ray goes to lane k mod 64 there; every segment starts at a multiple of 64, so here the same lane
-// meets the same samples, and the body below is a COPY of that kernel's body (contraction off, the same explicit fmaf sites, the
-// exclusive prefix as the shifted inclusive one): compositing the first m samples of a ray in segments gives the bits
-// eval_composite_kernel gives for a ray of m samples.  That needs the lane accumulators carried as they are -- the wave reduction
-// happens once, in the finishing kernel, in eval_composite_kernel's order.  State of one ray (kSegStateFloats floats, 1312 bytes):
+// meets the same samples, and the loop body is that kernel's (group_weights, accumulate_sample): compositing the first m samples of
+// a ray in segments gives the bits eval_composite_kernel gives for a ray of m samples.  That needs the lane accumulators carried as
+// they are -- the wave reduction happens once, in the finishing kernel (finish_ray).  State of one ray (kSegStateFloats floats,
+// 1312 bytes):
 //   [a * 64 + lane], a = 0..4   lane accumulators: r, g, b, weight, depth numerator
 //   [320] carry                 the optical depth in front of the next 64-sample group (the very value the scan carries)
 //   [321], [322]                smallest / largest interval mid-point composited so far (min / max are exact: reduced per segment)
@@ -338,7 +341,6 @@ __global__ __launch_bounds__(256) void eval_composite_segment_kernel(const float
                                                                      int64_t seg_end, int64_t next_len, float tau_stop,
                                                                      float *state, int64_t *__restrict__ next_seg_cnts)
 {
-#pragma clang fp contract(off)   // as in eval_composite_kernel
     const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
     const int lane = threadIdx.x & 63;
@@ -351,55 +353,21 @@ __global__ __launch_bounds__(256) void eval_composite_segment_kernel(const float
     const bool alive = si[1] != 0;
     float carry = st[kSegCarry];
     if (cnt > 0) {
-        float ar = st[lane], ag = st[64 + lane], ab = st[128 + lane], aw = st[192 + lane], ad = st[256 + lane];
-        float mlo = st[kSegMidLo], mhi = st[kSegMidHi];
+        RayAccum acc = {st[lane], st[64 + lane], st[128 + lane], st[192 + lane], st[256 + lane], st[kSegMidLo], st[kSegMidHi]};
         for (int64_t base = 0; base < cnt; base += 64) {
             const int64_t i = s0 + base + lane;
             const bool valid = base + lane < cnt;
             float a = 0.f, b = 0.f, sg = 0.f;
             if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
-            const float dt = b - a;
-            const float sd = sg * dt;
-            float incl = sd;
-            {
-                const float nb = __shfl_up(incl, 1, 64);
-                if (lane >= 1) incl = fmaf(sg, dt, nb);
-            }
-#pragma unroll
-            for (int off = 2; off < 64; off <<= 1) {
-                const float nb = __shfl_up(incl, off, 64);
-                if (lane >= off) incl = incl + nb;
-            }
-            float excl = __shfl_up(incl, 1, 64);     // shifted, not `incl - sd`: see volrend_fwd_kernel
-            if (lane == 0) excl = 0.f;
-            const float T = expf(-(excl + carry));
-            const float alpha = 1.f - expf(-sd);
-            const float w = valid ? T * alpha : 0.f;
-            if (valid) {
-                const float mid = (a + b) * 0.5f;
-                mlo = fminf(mlo, mid);
-                mhi = fmaxf(mhi, mid);
-                const float *c = rgb + i * rgb_stride;
-                float c0 = c[0], c1 = c[1], c2 = c[2];
-                if (fix_nan) { c0 = nan_to_num(c0); c1 = nan_to_num(c1); c2 = nan_to_num(c2); }
-                ar = fmaf(w, c0, ar);
-                ag = fmaf(w, c1, ag);
-                ab = fmaf(w, c2, ab);
-                aw = aw + w;
-                ad = fmaf(w, mid, ad);
-            }
-            carry = carry + __shfl(incl, 63, 64);
+            const float w = group_weights(a, b, sg, valid, lane, carry).w;
+            if (valid) accumulate_sample(acc, w, a, b, rgb + i * rgb_stride, fix_nan);
         }
-        st[lane] = ar; st[64 + lane] = ag; st[128 + lane] = ab; st[192 + lane] = aw; st[256 + lane] = ad;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mlo = fminf(mlo, __shfl_xor(mlo, off, 64));
-            mhi = fmaxf(mhi, __shfl_xor(mhi, off, 64));
-        }
+        st[lane] = acc.r; st[64 + lane] = acc.g; st[128 + lane] = acc.b; st[192 + lane] = acc.w; st[256 + lane] = acc.d;
+        wave_mid_range(acc.mlo, acc.mhi);
         if (lane == 0) {
             st[kSegCarry] = carry;
-            st[kSegMidLo] = mlo;
-            st[kSegMidHi] = mhi;
+            st[kSegMidLo] = acc.mlo;
+            st[kSegMidHi] = acc.mhi;
             si[0] += (int32_t)cnt;
         }
     }
@@ -413,32 +381,19 @@ __global__ __launch_bounds__(256) void eval_composite_segment_kernel(const float
     }
 }
 
-// The end of eval_composite_kernel for a segmented ray: the wave reductions in that kernel's order, then its lane-0 epilogue.
+// The end of eval_composite_kernel for a segmented ray: finish_ray on the state the segments left.
 __global__ __launch_bounds__(256) void eval_segment_finish_kernel(const float *__restrict__ state, int n_rays, int flags,
                                                                   float background, float *__restrict__ mid_range,
                                                                   float *__restrict__ num, float *__restrict__ out_rgb,
                                                                   float *__restrict__ out_acc, int64_t *__restrict__ out_nsamples)
 {
-#pragma clang fp contract(off)
     const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
     const int lane = threadIdx.x & 63;
     const float *st = state + (int64_t)ray * kSegStateFloats;
-    float ar = st[lane], ag = st[64 + lane], ab = st[128 + lane], aw = st[192 + lane], ad = st[256 + lane];
-    ar = lse::wave_sum(ar); ag = lse::wave_sum(ag); ab = lse::wave_sum(ab);
-    aw = lse::wave_sum(aw); ad = lse::wave_sum(ad);
-    if (lane == 0) {
-        if (flags & LSE_EVAL_BACKGROUND) {     // rgb + bg * (1 - acc)
-            const float rest = background * (1.f - aw);
-            ar = ar + rest; ag = ag + rest; ab = ab + rest;
-        }
-        if (flags & LSE_EVAL_CLAMP) { ar = clamp01(ar); ag = clamp01(ag); ab = clamp01(ab); }
-        out_rgb[ray * 3 + 0] = ar; out_rgb[ray * 3 + 1] = ag; out_rgb[ray * 3 + 2] = ab;
-        out_acc[ray] = aw;
-        num[ray] = ad;
-        mid_range[2 * ray] = st[kSegMidLo]; mid_range[2 * ray + 1] = st[kSegMidHi];
-        out_nsamples[ray] = reinterpret_cast<const int32_t *>(st + kSegInts)[0];
-    }
+    const RayAccum acc = {st[lane], st[64 + lane], st[128 + lane], st[192 + lane], st[256 + lane], st[kSegMidLo], st[kSegMidHi]};
+    finish_ray(acc, reinterpret_cast<const int32_t *>(st + kSegInts)[0], lane, ray, flags, background, mid_range, num, out_rgb,
+               out_acc, out_nsamples);
 }
 
 __global__ __launch_bounds__(256) void volrend_bwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,

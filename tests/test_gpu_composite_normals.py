@@ -108,6 +108,37 @@ def test_zero_gradients_zero_weights_and_nan_sigma():
     assert torch.equal(bad[keep], _run(b).cpu()[keep])
 
 
+def test_weights_are_the_colour_kernels_bit_for_bit():
+    """d_x01 = (-1, 0, 0) in field space without renormalisation makes every sample's normal (1, 0, 0) exactly, so the x sum is
+    fmaf(w, 1, nx) = nx + w rounded once -- the accumulation of ``eval_composite`` over the same samples, reduced over the wave in
+    the same order: equal bit patterns pin the weights of the two kernels (group_weights) to each other."""
+    from lsenerf_amd import ops
+    lengths = (0, 1, 63, 64, 65, 128, 129)
+    g = torch.Generator().manual_seed(78)
+    R, n = len(lengths), sum(lengths)
+    packed = torch.tensor([[sum(lengths[:i]), c] for i, c in enumerate(lengths)], dtype=torch.int64).cuda()
+    dt = 0.002 + torch.rand(n, generator=g) * 0.004
+    ts = torch.cat([0.3 + torch.cumsum(dt[sum(lengths[:i]):sum(lengths[:i + 1])], 0) for i in range(R)]) - dt
+    te = ts + dt
+    sigma = torch.rand(n, generator=g) * 8.0
+    surface = int(packed[6, 0]) + 100                    # a surface sample of a trained scene behind more than one group of ray 6
+    sigma[surface] = 2500.0 / float(dt[surface])
+    assert 1e3 < float(sigma[surface] * (te[surface] - ts[surface])) < 1e4
+    ts, te, sigma = ts.cuda(), te.cuda(), sigma.cuda()
+    d_x01 = torch.tensor([-1.0, 0.0, 0.0]).repeat(n, 1).cuda()
+    normals = torch.full((R, 3), SENTINEL, device="cuda")
+    ops.eval_composite_normals(ts, te, sigma, d_x01, packed, normals, world=False, renormalize=False)
+    rgb = torch.rand(n, 3, generator=g).cuda()
+    out_rgb, acc, depth = torch.empty(R, 3, device="cuda"), torch.empty(R, device="cuda"), torch.empty(R, device="cuda")
+    nsamples = torch.empty(R, dtype=torch.int64, device="cuda")
+    ops.eval_composite(ts, te, sigma, rgb, packed, out_rgb, acc, depth, nsamples, nan_to_num=False, background=None, clamp=False)
+    print("COMPOSITE_NORMALS weights: acc", acc.tolist(), "N_x", normals[:, 0].tolist())
+    assert nsamples.tolist() == list(lengths)
+    assert float(acc[1:].min()) > 0.0 and float(acc[6]) > 0.5          # not vacuous: every ray with samples has weight
+    assert torch.equal(normals[:, 0].contiguous().view(torch.int32), acc.view(torch.int32))
+    assert bool((normals[:, 1:] == 0.0).all())
+
+
 def test_bad_arguments():
     from lsenerf_amd import ops
     b = _batch()

@@ -77,6 +77,19 @@ def main():
                 out.backward(go, retain_graph=True)
             med, mn = timeit(bwd)
             print(f"mlp_bwd {name} (autograd backward incl. zero-fills) median {med:.3f} ms  min {mn:.3f}", flush=True)
+    if want("volrend"):      # the compositors that share group_weights (csrc/volrend.hip), forward only
+        sigma = torch.rand(N, generator=g).to(dev) * 4.0
+        rgb = torch.rand(N, 4, generator=g).to(dev)
+        dx01 = torch.randn(N, 3, generator=g).to(dev)
+        out = (torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev),
+               torch.empty(R, dtype=torch.int64, device=dev))
+        ws, normals = torch.empty(3 * R, device=dev), torch.empty(R, 3, device=dev)
+        with torch.no_grad():
+            for name, fn in (("volrend_fwd", lambda: ops.volume_render(ts, te, sigma, rgb, packed)),
+                             ("eval_composite", lambda: ops.eval_composite(ts, te, sigma, rgb, packed, *out, True, 1.0, True, workspace=ws)),
+                             ("eval_composite_normals", lambda: ops.eval_composite_normals(ts, te, sigma, dx01, packed, normals))):
+                med, mn = timeit(fn)
+                print(f"{name} median {med:.3f} ms  min {mn:.3f} ms", flush=True)
     if want("traverse"):
         from lsenerf_amd import LSEOccGridEstimator
         est = LSEOccGridEstimator([-1, -1, -1, 1, 1, 1], 128, 4).to(dev); est.mark_all_occupied()
