@@ -637,6 +637,59 @@ int lse_surface_nets_emit(const float *sigma, int32_t nx, int32_t ny, int32_t nz
 int lse_point_normals_world(const float *d_x01, const float *positions, int32_t contraction, const float *h_aabb, int64_t n,
                             const int64_t *n_dev, float *out, lse_stream_t stream);
 
+/* ---- point-cloud export (csrc/pointcloud.hip; ABI 6, additive): eval renders -> one merged, filtered cloud ---------------------
+ * All floats are f32, every operation is rounded on its own, every comparison is false on NaN.  The three compacting entry points
+ * (append, merge, filter) share one ordered compaction: one wave owns LSE_PC_SEGMENT consecutive items, ballot / popcount give every
+ * kept item its rank inside the segment, one block scans the segment counts as int64, the emit pass writes at offset + rank.  Fixed
+ * grids sized from the extent, no atomics, no host read: two runs give the same bytes.  Each takes a workspace of the size its
+ * *_workspace function returns for the same extent (per segment an int64, per item an int32 rank; 8-byte aligned, contents need not
+ * survive the call) and a device int64 `total` (8-byte aligned).  Rows at or beyond `cap` are not written and `total` keeps the true
+ * count, as lse_surface_nets_emit's totals do.  Outputs must not alias inputs.  An extent is at most 2^40.
+ *
+ * lse_unproject_append.  origins, directions [n_rays, 3], depth, acc [n_rays]; colors, normals [n_rays, 3] nullable.
+ *   p_k = o_k + d_k * depth (the product rounded, then the sum).  Ray r is kept iff acc[r] >= min_acc, depth[r] > 0,
+ *   depth[r] < +inf and lo_k <= p_k <= hi_k for k = 0, 1, 2.  Kept rays take the rows *total + rank in ascending r, *total being
+ *   the value on entry; out_points [cap, 3] gets p, out_colors / out_normals [cap, 3] (each nullable; needs its input) get the
+ *   ray's row bit for bit.  Afterwards *total += kept: successive images append without a host read.  n_rays == 0: no-op.
+ * lse_voxel_keys.  points [n, 3]; count = min(n, *n_dev) (n_dev nullable: count = n).  For i < count
+ *   f_k = floorf((p_k - lo_k) / voxel),  v_k = f_k >= (float)(n_k - 1) ? n_k - 1 : (f_k > 0 ? (int)f_k : 0)  (NaN -> 0),
+ *   keys[i] = ((int64)vx * ny + vy) * nz + vz;  for count <= i < n keys[i] = INT64_MAX.  Refused: an n_k outside [1, 2^20], a voxel
+ *   size that is not positive and finite.  Sorting is the caller's: a STABLE sort of keys gives sorted_keys and order, so equal
+ *   keys keep ascending original index.
+ * lse_voxel_merge.  sorted_keys, order [n] (order: a permutation of 0 .. n - 1; an index outside is skipped, never read through);
+ *   points [n, 3], colors / normals [n, 3] nullable, indexed through order.  Position i is a head iff sorted_keys[i] != INT64_MAX
+ *   and (i == 0 or sorted_keys[i] != sorted_keys[i - 1]); its run extends to the next position with another key.  Voxel j is the
+ *   j-th head (keys ascending and unique): out_keys[j], out_counts[j] = run length c (int32), position and colour = s / (float)c
+ *   where s starts as the run's first element and adds the others one by one in run order, normal = s_n / max(len, 1e-12f) with
+ *   s_n summed the same way and len = sqrtf((sx * sx + sy * sy) + sz * sz) -- a zero sum stays zero.  *total = voxels (set, not
+ *   incremented; 0 for n == 0).  The thread that owns a head walks its run -- the pixels of all views inside one voxel -- so the
+ *   cost is O(longest run).
+ * lse_voxel_support_filter.  keys (ascending, unique), counts, points [m, 3], colors / normals nullable: the merge's outputs;
+ *   present voxels are j < min(m, *m_dev) (m_dev nullable).  Coordinates come back from the key (z = key % nz, y = (key / nz) % ny,
+ *   x = key / (nz * ny)); support_j = the sum of counts over the present voxels among the 27 offsets (dx, dy, dz) in {-1, 0, 1}^3
+ *   whose coordinates lie inside the lattice, j itself included, each found by binary search over keys (an adjacent key is not
+ *   necessarily a neighbour: (x, y, nz - 1) and (x, y + 1, 0) differ by one).  Voxel j is kept iff support_j >= min_support; the
+ *   kept voxels' keys, counts, points, colours and normals are compacted in order, *total = kept.  out_support (int32 [m], nullable,
+ *   indexed by INPUT voxel) receives every support, saturated at INT32_MAX, and 0 for j that is not present. */
+#define LSE_PC_SEGMENT 1024
+int lse_unproject_workspace(int64_t n_rays, int64_t *h_bytes);
+int lse_unproject_append(const float *origins, const float *directions, const float *depth, const float *acc, const float *colors,
+                         const float *normals, int64_t n_rays, const float *h_lo, const float *h_hi, float min_acc, void *workspace,
+                         int64_t workspace_bytes, int64_t cap, float *out_points, float *out_colors, float *out_normals,
+                         int64_t *total, lse_stream_t stream);
+int lse_voxel_keys(const float *points, int64_t n, const int64_t *n_dev, const float *h_lo, float voxel, int32_t nx, int32_t ny,
+                   int32_t nz, int64_t *keys, lse_stream_t stream);
+int lse_voxel_merge_workspace(int64_t n, int64_t *h_bytes);
+int lse_voxel_merge(const int64_t *sorted_keys, const int64_t *order, const float *points, const float *colors, const float *normals,
+                    int64_t n, void *workspace, int64_t workspace_bytes, int64_t cap, int64_t *out_keys, int32_t *out_counts,
+                    float *out_points, float *out_colors, float *out_normals, int64_t *total, lse_stream_t stream);
+int lse_voxel_support_workspace(int64_t m, int64_t *h_bytes);
+int lse_voxel_support_filter(const int64_t *keys, const int32_t *counts, const float *points, const float *colors,
+                             const float *normals, int64_t m, const int64_t *m_dev, int32_t nx, int32_t ny, int32_t nz,
+                             int32_t min_support, void *workspace, int64_t workspace_bytes, int64_t cap, int64_t *out_keys,
+                             int32_t *out_counts, float *out_points, float *out_colors, float *out_normals, int32_t *out_support,
+                             int64_t *total, lse_stream_t stream);
+
 /* ---- training epilogue: output routing + intensity mappers + both losses, O(rays), one launch each way
  *      (R:lse_nerf/lsenerf.py:329-377 routing, :392-439 losses; R:lse_nerf/intensity_mappers.py:64-94 mappers).
  * Colour bundle:  v = rgb_mapped ? m_rgb(max(rgb, 1e-5)) : rgb;  mean over deblur_group consecutive rays (the 4 virtual

@@ -639,6 +639,14 @@ class LSENeRFModel(nn.Module):
         from . import mesh as _mesh
         return _mesh.extract_mesh(self, **kwargs)
 
+    def export_point_cloud(self, views, **kwargs):
+        """Point cloud of what ``views`` (an ``eval_set.EvalSet`` or ray bundles) see of the field: unprojected eval renders, merged
+        per voxel and filtered by neighbour support on request (``lsenerf_amd.pointcloud.export_point_cloud``: image_indices,
+        min_accumulation, bounds, voxel_size, min_support, normals, colors, max_points).  Runs without gradients in eval mode and
+        restores the model's mode and eval settings."""
+        from . import pointcloud as _pointcloud
+        return _pointcloud.export_point_cloud(self, views, **kwargs)
+
     def _ngp_metrics_dict(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]) -> Dict[str, Tensor]:
         image = batch["image"].to(outputs["rgb"].device)
         return {"psnr": self.psnr(outputs["rgb"], image), "num_samples_per_batch": outputs["num_samples_per_ray"].sum()}

@@ -2248,3 +2248,171 @@ def point_normals_world(d_x01: torch.Tensor, positions: torch.Tensor, contractio
         _call_n("lse_point_normals_world", n_dev, _f32(d_x01, "d_x01"), _f32(positions, "positions"), 1 if contraction else 0, aabb_arr,
                 n, _f32(out, "out"), _stream())
     return out
+
+
+# ---- point-cloud export (csrc/pointcloud.hip; driven by lsenerf_amd.pointcloud.export_point_cloud) ----
+PC_MAX_AXIS = 1 << 20      # voxels per axis lse_voxel_keys accepts
+
+
+def _rows3(t: Optional[torch.Tensor], n: int, name: str, allow_none: bool = False):
+    """Pointer of a float32 ``[n, 3]`` tensor."""
+    ptr = _f32(t, name, allow_none)
+    if t is not None and tuple(t.shape) != (n, 3):
+        raise ValueError(f"{name}: [{n}, 3] expected, got {tuple(t.shape)}")
+    return ptr
+
+
+def _vec(t: Optional[torch.Tensor], dtype, n: int, name: str, allow_none: bool = False):
+    ptr = _chk(t, dtype, name, allow_none)
+    if t is not None and tuple(t.shape) != (n,):
+        raise ValueError(f"{name}: [{n}] expected, got {tuple(t.shape)}")
+    return ptr
+
+
+def _count1(t: Optional[torch.Tensor], name: str, allow_none: bool = False):
+    ptr = _chk(t, torch.int64, name, allow_none)
+    if t is not None and t.numel() != 1:
+        raise ValueError(f"{name}: one int64 on the device expected")
+    return ptr
+
+
+def _pc_workspace_bytes(fn: str, n: int) -> int:
+    v = ctypes.c_int64(0)
+    _lib.call(fn, int(n), ctypes.byref(v))
+    return int(v.value)
+
+
+def unproject_workspace_bytes(n_rays: int) -> int:
+    return _pc_workspace_bytes("lse_unproject_workspace", n_rays)
+
+
+def voxel_merge_workspace_bytes(n: int) -> int:
+    return _pc_workspace_bytes("lse_voxel_merge_workspace", n)
+
+
+def voxel_support_workspace_bytes(m: int) -> int:
+    return _pc_workspace_bytes("lse_voxel_support_workspace", m)
+
+
+def _pc_workspace(fn: str, n: int, workspace: Optional[torch.Tensor], dev):
+    """(tensor, pointer, bytes) of a compaction workspace for an extent of ``n``: the caller's (uint8) or a fresh one."""
+    if workspace is None:
+        workspace = torch.empty(_pc_workspace_bytes(fn, n), dtype=torch.uint8, device=dev)
+    ptr = _chk(workspace, torch.uint8, "workspace")
+    return workspace, (ptr if workspace.numel() else None), workspace.numel()
+
+
+def voxel_lattice(lo, hi, voxel_size: float) -> Tuple[int, int, int]:
+    """Voxels per axis of the box ``lo .. hi`` at ``voxel_size``: ``max(1, ceil((hi_k - lo_k) / voxel_size))`` in double.
+    ValueError: a size that is not positive and finite, a count above 2^20 (lse_voxel_keys' limit).  Pure host code."""
+    import math
+    v = float(voxel_size)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"voxel_size must be positive and finite, got {voxel_size}")
+    res = tuple(max(1, int(math.ceil((float(h) - float(l)) / v))) for l, h in zip(lo, hi))
+    if len(res) != 3:
+        raise ValueError("lo and hi: three floats each expected")
+    if max(res) > PC_MAX_AXIS:
+        raise ValueError(f"voxel_size {v} over {list(lo)} .. {list(hi)} gives a lattice of {res}: more than 2^20 voxels on an axis")
+    return res
+
+
+@torch.no_grad()
+def unproject_append(origins: torch.Tensor, directions: torch.Tensor, depth: torch.Tensor, acc: torch.Tensor, lo, hi,
+                     min_acc: float, out_points: torch.Tensor, total: torch.Tensor, colors: Optional[torch.Tensor] = None,
+                     normals: Optional[torch.Tensor] = None, out_colors: Optional[torch.Tensor] = None,
+                     out_normals: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """Appends the valid rays' points ``o + d * depth`` (and their ``colors`` / ``normals`` rows) to ``out_points`` (``out_colors``,
+    ``out_normals``; float32 [cap, 3]) behind row ``total[0]`` in ray order and adds their number to ``total`` (int64 [1] on the
+    device) -- lse_unproject_append; the validity rule is in include/lse_hip.h ("point-cloud export").  Rows beyond ``cap`` are
+    dropped while ``total`` keeps counting.  No host read."""
+    n = origins.shape[0]
+    args = [_rows3(origins, n, "origins"), _rows3(directions, n, "directions"), _vec(depth, torch.float32, n, "depth"),
+            _vec(acc, torch.float32, n, "acc"), _rows3(colors, n, "colors", True), _rows3(normals, n, "normals", True)]
+    cap = out_points.shape[0]
+    outs = [_rows3(out_points, cap, "out_points"), _rows3(out_colors, cap, "out_colors", True),
+            _rows3(out_normals, cap, "out_normals", True), _count1(total, "total")]
+    if (out_colors is not None and colors is None) or (out_normals is not None and normals is None):
+        raise ValueError("unproject_append: an output without its input")
+    c_lo, c_hi = _box3(lo, hi)
+    _, ws, ws_bytes = _pc_workspace("lse_unproject_workspace", n, workspace, origins.device)
+    _lib.call("lse_unproject_append", *args, n, c_lo, c_hi, float(min_acc), ws, ws_bytes, cap, *(o if cap else None for o in outs[:3]),
+              outs[3], _stream())
+
+
+@torch.no_grad()
+def voxel_keys(points: torch.Tensor, lo, voxel_size: float, res, n_dev: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [n] voxel keys ``(vx * ny + vy) * nz + vz`` of ``points`` [n, 3] on the ``res = (nx, ny, nz)`` lattice of ``voxel_size``
+    cells from ``lo`` (coordinates clamped into the lattice); rows at or beyond ``n_dev[0]`` get INT64_MAX, so a stable sort leaves
+    them last (lse_voxel_keys)."""
+    n = points.shape[0]
+    p = _rows3(points, n, "points")
+    nd = _count1(n_dev, "n_dev", True)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=points.device)
+    k = _vec(out, torch.int64, n, "out")
+    nx, ny, nz = _res3(res)
+    c_lo, _ = _box3(lo, lo)
+    _lib.call("lse_voxel_keys", p if n else None, n, nd, c_lo, float(voxel_size), nx, ny, nz, k if n else None, _stream())
+    return out
+
+
+@torch.no_grad()
+def voxel_merge(sorted_keys: torch.Tensor, order: torch.Tensor, points: torch.Tensor, colors: Optional[torch.Tensor] = None,
+                normals: Optional[torch.Tensor] = None, cap: Optional[int] = None, workspace: Optional[torch.Tensor] = None):
+    """One point per voxel from a cloud sorted by key (``sorted_keys, order = torch.sort(keys, stable=True)``): ``(keys int64 [cap],
+    counts int32 [cap], points, colors | None, normals | None [cap, 3], total int64 [1])`` -- means in run order, normals
+    renormalised, voxels in ascending key (lse_voxel_merge).  ``cap`` defaults to n; rows at or beyond ``total[0]`` are unwritten.
+    No host read."""
+    n = sorted_keys.shape[0]
+    args = [_vec(sorted_keys, torch.int64, n, "sorted_keys"), _vec(order, torch.int64, n, "order"), _rows3(points, n, "points"),
+            _rows3(colors, n, "colors", True), _rows3(normals, n, "normals", True)]
+    cap = n if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("voxel_merge: negative capacity")
+    dev = points.device
+    new3 = lambda src: None if src is None else torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    out_keys = torch.empty(cap, dtype=torch.int64, device=dev)
+    out_counts = torch.empty(cap, dtype=torch.int32, device=dev)
+    out_p, out_c, out_n = new3(points), new3(colors), new3(normals)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    _, ws, ws_bytes = _pc_workspace("lse_voxel_merge_workspace", n, workspace, dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if (t is not None and t.numel()) else None
+    _lib.call("lse_voxel_merge", *(a if n else None for a in args), n, ws, ws_bytes, cap, ptr(out_keys), ptr(out_counts), ptr(out_p),
+              ptr(out_c), ptr(out_n), ptr(total), _stream())
+    return out_keys, out_counts, out_p, out_c, out_n, total
+
+
+@torch.no_grad()
+def voxel_support_filter(keys: torch.Tensor, counts: torch.Tensor, points: torch.Tensor, res, min_support: int,
+                         colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                         m_dev: Optional[torch.Tensor] = None, cap: Optional[int] = None, want_support: bool = False,
+                         workspace: Optional[torch.Tensor] = None):
+    """Keeps the voxels whose 3 x 3 x 3 neighbourhood on the ``res`` lattice holds at least ``min_support`` raw points (the sum of
+    ``counts`` over the present neighbours, the voxel included): ``(keys, counts, points, colors | None, normals | None, total int64
+    [1], support int32 [m] | None)``, compacted in order (lse_voxel_support_filter).  ``keys`` ascending and unique, as
+    ``voxel_merge`` writes them; ``m_dev``: device count of the present voxels (``voxel_merge``'s total).  No host read."""
+    m = keys.shape[0]
+    args = [_vec(keys, torch.int64, m, "keys"), _vec(counts, torch.int32, m, "counts"), _rows3(points, m, "points"),
+            _rows3(colors, m, "colors", True), _rows3(normals, m, "normals", True)]
+    md = _count1(m_dev, "m_dev", True)
+    cap = m if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("voxel_support_filter: negative capacity")
+    min_support = int(min_support)
+    if not -(1 << 31) <= min_support < (1 << 31):
+        raise ValueError("voxel_support_filter: min_support must fit an int32")
+    nx, ny, nz = _res3(res)
+    dev = points.device
+    new3 = lambda src: None if src is None else torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    out_keys = torch.empty(cap, dtype=torch.int64, device=dev)
+    out_counts = torch.empty(cap, dtype=torch.int32, device=dev)
+    out_p, out_c, out_n = new3(points), new3(colors), new3(normals)
+    support = torch.empty(m, dtype=torch.int32, device=dev) if want_support else None
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    _, ws, ws_bytes = _pc_workspace("lse_voxel_support_workspace", m, workspace, dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if (t is not None and t.numel()) else None
+    _lib.call("lse_voxel_support_filter", *(a if m else None for a in args), m, md, nx, ny, nz, min_support, ws, ws_bytes, cap,
+              ptr(out_keys), ptr(out_counts), ptr(out_p), ptr(out_c), ptr(out_n), ptr(support), ptr(total), _stream())
+    return out_keys, out_counts, out_p, out_c, out_n, total, support
