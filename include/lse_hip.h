@@ -690,6 +690,60 @@ int lse_voxel_support_filter(const int64_t *keys, const int32_t *counts, const f
                              int32_t *out_counts, float *out_points, float *out_colors, float *out_normals, int32_t *out_support,
                              int64_t *total, lse_stream_t stream);
 
+/* ---- event synthesis (csrc/events.hip; ABI 6, additive): log-intensity planes -> event counts and an event stream, and back -------
+ * The sensor model is ideal, noise-free and per pixel: the linear-interpolation model of ESIM.  Inputs: K + 1 log-intensity planes
+ * L[k][p], f32, plane-major [K + 1, P] with P = H * W in row-major pixel order; times t[k], f64 [K + 1], on the device, ascending; a
+ * per-pixel reference level ref[p], f32; the thresholds c_pos, c_neg, positive and finite; a per-interval cap cap_step in
+ * [1, 32767].  Every f32 operation is rounded on its own, every comparison is false on NaN.
+ *
+ * The walk of interval k at pixel p, with L0 = L[k][p], L1 = L[k + 1][p], n = 0 and ref the level the previous interval left
+ * (ref_in[p] for k = 0):
+ *   if (L1 - ref >= c_pos)      while (L1 - ref >= c_pos && n < cap_step) { ref = ref + c_pos; emit(+1, ref); n++; }
+ *   else if (ref - L1 >= c_neg) while (ref - L1 >= c_neg && n < cap_step) { ref = ref - c_neg; emit(-1, ref); n++; }
+ *   if (n == cap_step) ref = L1;             (a saturated pixel: the level is re-armed at the interval's end)
+ *   counts[k][p] = polarity * n              (int32, signed)
+ * and ref_out[p] is the level behind the last interval.  NaN in L or ref gives no event and leaves ref unchanged.
+ * emit(pol, level) gives the event its time:
+ *   d    = L1 - L0
+ *   frac = (d == 0 || q is NaN) ? 0 : min(max(q, 0), 1)   with q = (level - L0) / d, the correctly rounded f32 quotient
+ *          ((float)((double)a / (double)d) is exactly that)
+ *   time = t[k] + (double)frac * (t[k + 1] - t[k])         in f64: the difference, then the product, then the sum, each rounded
+ * An event is x = p % W (int16), y = p / W (int16), t (f64), p (int8, +1 or -1); the stream order is (k ascending, pixel ascending,
+ * emission order).  Every device loop is bounded by cap_step or a host-known extent.
+ *
+ * Conventions are those of the point-cloud section: fixed grids sized from the extent, no host read, a workspace of the size
+ * lse_event_workspace returns for the same (K, P) (8-byte aligned, contents need not survive the call: per segment of
+ * LSE_EVENT_SEGMENT consecutive items (k, p) an int64, per item the interval's starting level, its signed count and the rank of its
+ * first event), a device int64 `total` (8-byte aligned), rows at or beyond `cap` not written while `total` keeps the true count,
+ * outputs that do not alias inputs (ref_out is not ref_in), and two runs that give the same bytes.  The rank of an item is a wave
+ * prefix SUM of |n| (an item carries |n| events, not 0 or 1), one block scans the segment sums as int64, the emit pass rewalks one
+ * interval per item.  Refused: K or P negative, P > 2^30, K * P > 2^40, a threshold that is not positive and finite, cap_step
+ * outside [1, 32767].
+ *
+ * lse_event_count.  The walk without emission: counts (int32 [K, P]), ref_out, and *window_total = the sum of |counts| (int64, set,
+ *   summed in a fixed order).  K == 0: ref_out = ref_in, *window_total = 0.
+ * lse_event_append.  The same walk; the window's events take the rows *total + rank in stream order, *total being the value on
+ *   entry; afterwards *total += the window's events, so successive windows (ref_out of one as ref_in of the next, the last plane of
+ *   one as the first of the next) chain without a host read.  out_x, out_y (int16), out_t (f64), out_p (int8): [cap]; counts is
+ *   nullable.  Also refused: P % W != 0, W outside [1, 32767], P / W > 32767, a workspace too small.  K == 0 is a no-op that copies
+ *   ref_in to ref_out.
+ * lse_event_accumulate.  A stream -> frames.  x, y, t, p [n]; count = min(n, *n_dev) (n_dev nullable: count = n); bounds: f64
+ *   [F + 1] on the device, ascending.  For i < count, frame f is the largest index with bounds[f] <= t_i; the event counts iff
+ *   bounds[0] <= t_i < bounds[F], 0 <= x_i < W and 0 <= y_i < H, and a counted event does acc[f][y_i][x_i] += (int)p_i (acc: int32
+ *   [F, H, W]).  It ADDS into acc, so a stream can arrive in pieces and the caller zeroes acc first.  The adds are 32-bit integer
+ *   vector atomics: integer sums do not depend on the order of their terms, so the result is still bit-reproducible.  Saturation
+ *   to int8 (the format of eimgs_1x.npy) is the caller's. */
+#define LSE_EVENT_SEGMENT 1024
+int lse_event_workspace(int64_t K, int64_t P, int64_t *h_bytes);
+int lse_event_count(const float *L, int64_t K, int64_t P, const float *ref_in, float c_pos, float c_neg, int32_t cap_step,
+                    int32_t *counts, float *ref_out, int64_t *window_total, lse_stream_t stream);
+int lse_event_append(const float *L, const double *times, int64_t K, int64_t P, int32_t W, const float *ref_in, float c_pos,
+                     float c_neg, int32_t cap_step, void *workspace, int64_t workspace_bytes, int64_t cap, int16_t *out_x,
+                     int16_t *out_y, double *out_t, int8_t *out_p, int32_t *counts, float *ref_out, int64_t *total,
+                     lse_stream_t stream);
+int lse_event_accumulate(const int16_t *x, const int16_t *y, const double *t, const int8_t *p, int64_t n, const int64_t *n_dev,
+                         const double *bounds, int32_t F, int32_t H, int32_t W, int32_t *acc, lse_stream_t stream);
+
 /* ---- training epilogue: output routing + intensity mappers + both losses, O(rays), one launch each way
  *      (R:lse_nerf/lsenerf.py:329-377 routing, :392-439 losses; R:lse_nerf/intensity_mappers.py:64-94 mappers).
  * Colour bundle:  v = rgb_mapped ? m_rgb(max(rgb, 1e-5)) : rgb;  mean over deblur_group consecutive rays (the 4 virtual

@@ -29,6 +29,7 @@ LSE_PREP_EVENT_STATS = 1
 LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
 LSE_MESH_SEGMENT = 1024
 LSE_PC_SEGMENT = 1024
+LSE_EVENT_SEGMENT = 1024
 LSE_PANEL_IMG, LSE_PANEL_DEPTH, LSE_PANEL_ERR_MAP, LSE_PANEL_OVERLAY, LSE_PANEL_EV_OUT = 1, 2, 4, 8, 16
 
 
@@ -204,6 +205,10 @@ SIGNATURES = {
     "lse_voxel_merge": [P, P, P, P, P, I64, P, I64, I64, P, P, P, P, P, P, P],
     "lse_voxel_support_workspace": [I64, POINTER(c_int64)],
     "lse_voxel_support_filter": [P, P, P, P, P, I64, P, I32, I32, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P],
+    "lse_event_workspace": [I64, I64, POINTER(c_int64)],
+    "lse_event_count": [P, I64, I64, P, F32, F32, I32, P, P, P, P],
+    "lse_event_append": [P, P, I64, I64, I32, P, F32, F32, I32, P, I64, I64, P, P, P, P, P, P, P, P],
+    "lse_event_accumulate": [P, P, P, P, I64, P, P, I32, I32, I32, P, P],
     "lse_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, I32, F32, P],
     "lse_adam_step_f64": [P, P, P, P, I64, c_double, c_double, c_double, c_double, I32, F32, P],
     "lse_adam_step_dev": [P, P, P, P, I64, P, F32, P],

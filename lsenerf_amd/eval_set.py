@@ -66,6 +66,24 @@ class EvalSet:
 
 
 @torch.no_grad()
+def pose_bundle(cam_desc, pose: Tensor, H: int, W: int, camera_index: int, appearance_id: Tensor, time: Optional[Tensor] = None,
+                metadata_rows: Optional[Dict[str, Tensor]] = None) -> RayBundle:
+    """The [H, W] bundle of one device pose ``pose`` [3, 4]: rays from ``ops.camera_rays``, ``camera_indices``, ``times`` when
+    ``time`` (one element, on the device) is given, and the metadata ``generate_rays`` and the composer attach: ``directions_norm``,
+    ``appearance_id`` (one element, on the device) and ``metadata_rows`` (the camera's row of every per-camera metadata tensor).
+    What ``camera_bundle`` and ``events.log_intensity_planes`` share.  No host-to-device copy, no synchronisation."""
+    o, dirs, area, norm = ops.camera_rays(cam_desc, pose, 0, H * W)
+    dev = o.device
+    meta = {"directions_norm": norm.reshape(H, W, 1), "appearance_id": appearance_id.reshape(1, 1, 1).expand(H, W, 1)}
+    for k, row in (metadata_rows or {}).items():
+        meta[k] = row.expand(H, W, *row.shape)
+    times = time.reshape(1, 1, 1).expand(H, W, 1) if time is not None else None
+    return RayBundle(origins=o.reshape(H, W, 3), directions=dirs.reshape(H, W, 3), pixel_area=area.reshape(H, W, 1),
+                     camera_indices=torch.full((H, W, 1), int(camera_index), dtype=torch.long, device=dev), times=times,
+                     metadata=meta)
+
+
+@torch.no_grad()
 def camera_bundle(eval_set: EvalSet, i: int) -> RayBundle:
     """The [H, W] bundle of eval image ``i``: rays from ``ops.camera_rays`` over the set's device pose table (the values of
     ``EdCameras.generate_rays`` over ``get_image_coords()``, bit-equal to the composer's), ``camera_indices``, ``times`` when the
@@ -74,16 +92,10 @@ def camera_bundle(eval_set: EvalSet, i: int) -> RayBundle:
     d = eval_set.data
     if not 0 <= int(i) < d.n_images:
         raise IndexError(f"eval image {i} of {d.n_images}")
-    H, W = d.H, d.W
     cam = int(d.image_idx_host[int(i)])
-    o, dirs, area, norm = ops.camera_rays(eval_set.cam_desc, eval_set.poses[cam], 0, H * W)
-    dev = o.device
-    meta = {"directions_norm": norm.reshape(H, W, 1), "appearance_id": d.appearance_id[int(i)].reshape(1, 1, 1).expand(H, W, 1)}
-    for k, v in eval_set.camera_metadata.items():
-        meta[k] = v[cam].expand(H, W, *v.shape[1:])
-    times = d.times[cam].reshape(1, 1, 1).expand(H, W, 1) if eval_set.cameras.times is not None else None
-    return RayBundle(origins=o.reshape(H, W, 3), directions=dirs.reshape(H, W, 3), pixel_area=area.reshape(H, W, 1),
-                     camera_indices=torch.full((H, W, 1), cam, dtype=torch.long, device=dev), times=times, metadata=meta)
+    return pose_bundle(eval_set.cam_desc, eval_set.poses[cam], d.H, d.W, cam, d.appearance_id[int(i)],
+                       d.times[cam] if eval_set.cameras.times is not None else None,
+                       {k: v[cam] for k, v in eval_set.camera_metadata.items()})
 
 
 class PanelSet:

@@ -647,6 +647,19 @@ class LSENeRFModel(nn.Module):
         from . import pointcloud as _pointcloud
         return _pointcloud.export_point_cloud(self, views, **kwargs)
 
+    def simulate_events(self, cameras, poses, times, threshold: float, **kwargs):
+        """Events an ideal sensor sees of the field along ``poses`` at ``times``: ``(EventStream, ref_out, counts_total)``
+        (``lsenerf_amd.events.simulate_events``: threshold_neg, window, cap_step, max_events, ref, sort, appearance_id,
+        camera_index).  Runs without gradients in eval mode and restores the model's mode and eval settings."""
+        from . import events as _events
+        return _events.simulate_events(self, cameras, poses, times, threshold, **kwargs)
+
+    def predict_event_frames(self, cameras, poses, threshold: float, **kwargs):
+        """Signed event counts per frame of ``poses`` [F, S + 1, 3, 4], int32 [F, H, W] -- the quantity the recorded event frames
+        hold (``lsenerf_amd.events.predict_event_frames``: threshold_neg, cap_step, times, appearance_id, camera_index)."""
+        from . import events as _events
+        return _events.predict_event_frames(self, cameras, poses, threshold, **kwargs)
+
     def _ngp_metrics_dict(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]) -> Dict[str, Tensor]:
         image = batch["image"].to(outputs["rgb"].device)
         return {"psnr": self.psnr(outputs["rgb"], image), "num_samples_per_batch": outputs["num_samples_per_ray"].sum()}

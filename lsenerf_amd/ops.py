@@ -2416,3 +2416,140 @@ def voxel_support_filter(keys: torch.Tensor, counts: torch.Tensor, points: torch
     _lib.call("lse_voxel_support_filter", *(a if m else None for a in args), m, md, nx, ny, nz, min_support, ws, ws_bytes, cap,
               ptr(out_keys), ptr(out_counts), ptr(out_p), ptr(out_c), ptr(out_n), ptr(support), ptr(total), _stream())
     return out_keys, out_counts, out_p, out_c, out_n, total, support
+
+
+# ---- event synthesis (csrc/events.hip; driven by lsenerf_amd.events) ----
+EVENT_MAX_AXIS = 32767     # x and y of an event are int16
+EVENT_MAX_CAP_STEP = 32767
+
+
+def _ev(t: Optional[torch.Tensor], dtype, shape, name: str, allow_none: bool = False):
+    """Pointer of a contiguous device tensor of ``dtype`` and ``shape``; every violation is a ValueError."""
+    if t is None:
+        if allow_none:
+            return None
+        raise ValueError(f"{name} is None")
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (got {getattr(t, 'device', type(t))}); the HIP path has no CPU fallback")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {list(shape)} expected, got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+
+
+def _ev_sensor(c_pos: float, c_neg: float, cap_step: int):
+    import math
+    c_pos, c_neg, cap_step = float(c_pos), float(c_neg), int(cap_step)
+    if not (c_pos > 0.0 and math.isfinite(c_pos) and c_neg > 0.0 and math.isfinite(c_neg)):
+        raise ValueError(f"the thresholds must be positive and finite, got {c_pos} and {c_neg}")
+    if not 1 <= cap_step <= EVENT_MAX_CAP_STEP:
+        raise ValueError(f"cap_step {cap_step} outside [1, {EVENT_MAX_CAP_STEP}]")
+    return c_pos, c_neg, cap_step
+
+
+def _ev_planes(planes: torch.Tensor):
+    if not torch.is_tensor(planes) or planes.dim() != 2 or planes.shape[0] < 1:
+        raise ValueError(f"planes: [K + 1, P] expected, got {list(getattr(planes, 'shape', ()))}")
+    return planes.shape[0] - 1, planes.shape[1]
+
+
+def event_workspace_bytes(K: int, P: int) -> int:
+    """Bytes of the workspace ``event_append`` needs for ``K`` intervals of ``P`` pixels (lse_event_workspace)."""
+    v = ctypes.c_int64(0)
+    _lib.call("lse_event_workspace", int(K), int(P), ctypes.byref(v))
+    return int(v.value)
+
+
+@torch.no_grad()
+def event_count(planes: torch.Tensor, ref_in: torch.Tensor, c_pos: float, c_neg: float, cap_step: int,
+                counts: Optional[torch.Tensor] = None, ref_out: Optional[torch.Tensor] = None,
+                window_total: Optional[torch.Tensor] = None):
+    """The sensor walk of include/lse_hip.h ("event synthesis") over ``planes`` (float32 [K + 1, P], log intensity) from the levels
+    ``ref_in`` (float32 [P]), without a stream: ``(counts int32 [K, P], ref_out float32 [P], window_total int64 [1])`` --
+    lse_event_count.  ``window_total`` = the sum of ``|counts|``.  No host read."""
+    K, P = _ev_planes(planes)
+    c_pos, c_neg, cap_step = _ev_sensor(c_pos, c_neg, cap_step)
+    lp = _ev(planes, torch.float32, (K + 1, P), "planes")
+    ri = _ev(ref_in, torch.float32, (P,), "ref_in")
+    dev = planes.device
+    if counts is None:
+        counts = torch.empty((K, P), dtype=torch.int32, device=dev)
+    if ref_out is None:
+        ref_out = torch.empty(P, dtype=torch.float32, device=dev)
+    if window_total is None:
+        window_total = torch.empty(1, dtype=torch.int64, device=dev)
+    outs = (_ev(counts, torch.int32, (K, P), "counts"), _ev(ref_out, torch.float32, (P,), "ref_out"),
+            _ev(window_total, torch.int64, (1,), "window_total"))
+    if P and ref_out.data_ptr() == ref_in.data_ptr():
+        raise ValueError("event_count: ref_out must not alias ref_in")
+    _lib.call("lse_event_count", lp, K, P, ri, c_pos, c_neg, cap_step, *outs, _stream())
+    return counts, ref_out, window_total
+
+
+@torch.no_grad()
+def event_append(planes: torch.Tensor, times: torch.Tensor, W: int, ref_in: torch.Tensor, c_pos: float, c_neg: float, cap_step: int,
+                 out_x: torch.Tensor, out_y: torch.Tensor, out_t: torch.Tensor, out_p: torch.Tensor, total: torch.Tensor,
+                 counts: Optional[torch.Tensor] = None, ref_out: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Appends the events of the window ``planes`` (float32 [K + 1, P]) at ``times`` (float64 [K + 1], device, ascending) to ``out_x``,
+    ``out_y`` (int16), ``out_t`` (float64), ``out_p`` (int8), all [cap], behind row ``total[0]`` in stream order (interval, pixel,
+    emission) and adds their number to ``total`` (int64 [1] on the device) -- lse_event_append.  ``counts`` (int32 [K, P]) is
+    optional; returns ``ref_out`` (float32 [P], not ``ref_in``).  Rows beyond ``cap`` are dropped while ``total`` keeps counting.
+    No host read."""
+    K, P = _ev_planes(planes)
+    c_pos, c_neg, cap_step = _ev_sensor(c_pos, c_neg, cap_step)
+    W = int(W)
+    if not 1 <= W <= EVENT_MAX_AXIS or P % W != 0 or P // W > EVENT_MAX_AXIS:
+        raise ValueError(f"event_append: {P} pixels in rows of {W}: the width and the height must divide the plane and lie in "
+                         f"[1, {EVENT_MAX_AXIS}]")
+    lp = _ev(planes, torch.float32, (K + 1, P), "planes")
+    tp = _ev(times, torch.float64, (K + 1,), "times")
+    ri = _ev(ref_in, torch.float32, (P,), "ref_in")
+    cap = int(out_t.shape[0]) if torch.is_tensor(out_t) and out_t.dim() == 1 else -1
+    if cap < 0:
+        raise ValueError("out_t: [cap] expected")
+    outs = (_ev(out_x, torch.int16, (cap,), "out_x"), _ev(out_y, torch.int16, (cap,), "out_y"),
+            _ev(out_t, torch.float64, (cap,), "out_t"), _ev(out_p, torch.int8, (cap,), "out_p"))
+    tot = _ev(total, torch.int64, (1,), "total")
+    cn = _ev(counts, torch.int32, (K, P), "counts", True)
+    dev = planes.device
+    if ref_out is None:
+        ref_out = torch.empty(P, dtype=torch.float32, device=dev)
+    ro = _ev(ref_out, torch.float32, (P,), "ref_out")
+    if P and ref_out.data_ptr() == ref_in.data_ptr():
+        raise ValueError("event_append: ref_out must not alias ref_in")
+    need = event_workspace_bytes(K, P)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if not torch.is_tensor(workspace) or workspace.dim() != 1:
+        raise ValueError("workspace: a flat uint8 tensor expected")
+    ws = _ev(workspace, torch.uint8, (workspace.numel(),), "workspace")
+    if workspace.numel() < need:
+        raise ValueError(f"event_append: workspace of {workspace.numel()} bytes < {need}")
+    _lib.call("lse_event_append", lp, tp, K, P, W, ri, c_pos, c_neg, cap_step, ws, workspace.numel(), cap, *outs, cn, ro, tot, _stream())
+    return ref_out
+
+
+@torch.no_grad()
+def event_accumulate(x: torch.Tensor, y: torch.Tensor, t: torch.Tensor, p: torch.Tensor, bounds: torch.Tensor, acc: torch.Tensor,
+                     n_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adds the events ``x, y`` (int16), ``t`` (float64), ``p`` (int8), all [n] -- the first ``n_dev[0]`` of them with ``n_dev`` --
+    into the frames ``acc`` (int32 [F, H, W]): frame f holds ``bounds[f] <= t < bounds[f + 1]`` (``bounds`` float64 [F + 1], device,
+    ascending) -- lse_event_accumulate.  Events outside the bounds or the image are skipped.  ``acc`` is not zeroed: a stream can
+    arrive in pieces.  Integer atomics: bit-reproducible."""
+    if not torch.is_tensor(acc) or acc.dim() != 3 or min(acc.shape) < 1:
+        raise ValueError(f"acc: int32 [F, H, W] with every extent at least 1 expected, got {list(getattr(acc, 'shape', ()))}")
+    F, H, W = (int(s) for s in acc.shape)
+    n = int(t.shape[0]) if torch.is_tensor(t) and t.dim() == 1 else -1
+    if n < 0:
+        raise ValueError("t: [n] expected")
+    args = (_ev(x, torch.int16, (n,), "x"), _ev(y, torch.int16, (n,), "y"), _ev(t, torch.float64, (n,), "t"),
+            _ev(p, torch.int8, (n,), "p"))
+    nd = _ev(n_dev, torch.int64, (1,), "n_dev", True)
+    b = _ev(bounds, torch.float64, (F + 1,), "bounds")
+    a = _ev(acc, torch.int32, (F, H, W), "acc")
+    _lib.call("lse_event_accumulate", *args, n, nd, b, F, H, W, a, _stream())
+    return acc
