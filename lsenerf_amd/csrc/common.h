@@ -81,6 +81,13 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+__device__ __forceinline__ double wave_sum_d(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 // one value of a resident image or mask of element type LSE_PIX_* as float
 __device__ __forceinline__ float load_pix(const void *p, int type, int64_t i)
 {
@@ -91,6 +98,14 @@ __device__ __forceinline__ float load_pix(const void *p, int type, int64_t i)
     case LSE_PIX_I32: return (float)static_cast<const int32_t *>(p)[i];
     default: return static_cast<const float *>(p)[i];
     }
+}
+
+// to_gray of the reference (img @ [0.2989, 0.5870, 0.1140]): three products summed left to right, every operation rounded once,
+// also where the file is compiled with contraction
+__device__ __forceinline__ float gray3(float r, float g, float b)
+{
+#pragma clang fp contract(off)
+    return (r * 0.2989f + g * 0.5870f) + b * 0.1140f;
 }
 
 }  // namespace lse

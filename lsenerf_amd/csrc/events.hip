@@ -4,17 +4,17 @@
 // restate it operation by operation, hence -ffp-contract=off.
 //   walk_kernel      lane = pixel: one pass over the K intervals carries the reference level, writes counts[k][p] and ref_out[p] and,
 //                    for the stream, the interval's starting level and signed count per item (k, p) into the workspace
-//   rank_kernel      one wave owns LSE_EVENT_SEGMENT consecutive items; a wave prefix SUM of |n| gives every item the rank of its
-//                    first event inside the segment and the segment its event count (an item carries |n| events, not 0 or 1: a
-//                    shuffle scan where pointcloud.hip has ballot / popcount)
-//   scan_kernel      one block: segment counts -> exclusive offsets in place (int64) behind the *total of entry, *total += the sum
+//   rank_kernel      the rank pass of compact.h over segments of LSE_EVENT_SEGMENT items, weighted: an item carries |n| events, not
+//                    0 or 1, so a wave prefix SUM of |n| (a shuffle scan in place of ballot / popcount) gives every item the rank
+//                    of its first event inside the segment and the segment its event count
+//   scan_kernel      compact.h's scan, all in int64, behind the *total of entry: *total += the sum
 //   emit_kernel      one thread per item rewalks its one interval from the stored level and writes its events at offset + rank + e;
 //                    rows at or beyond cap are not written
 //   sum_kernel       lse_event_count's window total: one block sums |counts| in a fixed order (int64)
 //   accumulate_kernel one thread per event: frame by binary search over the bounds, a 32-bit integer vector atomic add into acc
 // Fixed grids sized from the extent, plain vector stores, no host read.  The only atomics are accumulate's integer adds, whose sum
 // does not depend on their order: two runs give the same bytes everywhere.
-#include "common.h"
+#include "compact.h"
 
 namespace {
 
@@ -23,6 +23,7 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kSumThreads = 1024;            // the one block of lse_event_count's total
 constexpr int kSeg = LSE_EVENT_SEGMENT;       // consecutive items owned by one wave
 constexpr int kIters = kSeg / 64;
+static_assert(kThreads == lse::kScanThreads, "scan_kernel is one block of kScanThreads");
 constexpr int64_t kMaxItems = 1ll << 40;      // K * P, and the events of one accumulate call
 constexpr int64_t kMaxPixels = 1ll << 30;     // P: 32767 x 32767 lies below
 constexpr int kMaxAxis = 32767;               // x and y are int16
@@ -87,33 +88,6 @@ __global__ __launch_bounds__(kThreads) void walk_kernel(const float *__restrict_
     ref_out[p] = ref;
 }
 
-__device__ __forceinline__ int wave_inclusive_sum_i(int v)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(v, off, 64);
-        if (lse::lane_id() >= off) v += n;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int64_t shfl_up_i64(int64_t v, int off)
-{
-    const int lo = __shfl_up((int)(uint32_t)(uint64_t)v, off, 64);
-    const int hi = __shfl_up((int)(uint32_t)((uint64_t)v >> 32), off, 64);
-    return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
-}
-
-__device__ __forceinline__ int64_t wave_inclusive_sum_i64(int64_t v)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t n = shfl_up_i64(v, off);
-        if (lse::lane_id() >= off) v += n;
-    }
-    return v;
-}
-
 // A segment holds at most kSeg * 32767 < 2^25 events: ranks and the running count fit an int.
 __global__ __launch_bounds__(kThreads) void rank_kernel(const int32_t *__restrict__ ws_n, int64_t items, int n_segs,
                                                         int32_t *__restrict__ rank, int64_t *__restrict__ seg_counts)
@@ -127,7 +101,7 @@ __global__ __launch_bounds__(kThreads) void rank_kernel(const int32_t *__restric
         const bool valid = i < items;
         const int n = valid ? ws_n[i] : 0;
         const int v = n < 0 ? -n : n;
-        const int inc = wave_inclusive_sum_i(v);
+        const int inc = lse::wave_inclusive_sum_i(v);
         if (valid) rank[i] = run + inc - v;
         run += __shfl(inc, 63, 64);
     }
@@ -137,26 +111,8 @@ __global__ __launch_bounds__(kThreads) void rank_kernel(const int32_t *__restric
 // one block.  Counts -> exclusive offsets in place, starting at the *total of entry; *total += sum.  All in int64.
 __global__ __launch_bounds__(kThreads) void scan_kernel(int64_t *__restrict__ seg, int n_segs, int64_t *__restrict__ total)
 {
-    __shared__ int64_t wsum[kWaves];
-    const int w = threadIdx.x >> 6, lane = lse::lane_id();
-    int64_t carry = *total;
-    for (int c0 = 0; c0 < n_segs; c0 += kThreads) {
-        const int i = c0 + threadIdx.x;
-        const int64_t v = i < n_segs ? seg[i] : 0;
-        const int64_t inc = wave_inclusive_sum_i64(v);
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int64_t woff = 0, sum = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; ++k) {
-            if (k < w) woff += wsum[k];
-            sum += wsum[k];
-        }
-        if (i < n_segs) seg[i] = carry + woff + inc - v;
-        carry += sum;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;       // (every thread has read the entry value: the loop's barriers lie in between)
+    const int64_t sum = lse::block_exclusive_scan<int64_t>(seg, n_segs, *total);
+    if (threadIdx.x == 0) *total = sum;
 }
 
 __global__ __launch_bounds__(kThreads) void emit_kernel(const float *__restrict__ L, const double *__restrict__ times, int64_t items,
@@ -169,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void emit_kernel(const float *__restrict_
     if (i >= items) return;
     const int n = ws_n[i];
     if (n == 0) return;
-    const int64_t row0 = seg_off[i / kSeg] + rank[i];
+    const int64_t row0 = lse::segment_row<kSeg>(i, rank, seg_off);
     if (row0 >= cap) return;
     const int64_t k = i / P, p = i - k * P;
     const float L0 = L[i], L1 = L[i + P];
@@ -242,9 +198,6 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const int16_t *__r
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-inline int n_segments(int64_t items) { return (int)((items + kSeg - 1) / kSeg); }
-inline unsigned blocks_for(int64_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
 inline dim3 item_grid(int64_t items)
 {
     const int64_t blocks = (items + kThreads - 1) / kThreads;
@@ -253,7 +206,7 @@ inline dim3 item_grid(int64_t items)
 }
 
 // per segment an int64 count / offset; per item the interval's starting level (f32), its signed count and its rank (int32)
-inline int64_t workspace_bytes_for(int64_t items) { return 8 * (int64_t)n_segments(items) + 12 * items; }
+inline int64_t workspace_bytes_for(int64_t items) { return 8 * (int64_t)lse::n_segments<kSeg>(items) + 12 * items; }
 
 int check_extent(const char *what, int64_t K, int64_t P)
 {
@@ -310,7 +263,7 @@ extern "C" int lse_event_count(const float *L, int64_t K, int64_t P, const float
     if (items == 0) {
         if (int rc = copy_levels(what, ref_in, ref_out, P, st)) return rc;
     } else {
-        hipLaunchKernelGGL(walk_kernel, dim3(blocks_for(P, kThreads)), dim3(kThreads), 0, st, L, K, P, ref_in, s, counts, ref_out,
+        hipLaunchKernelGGL(walk_kernel, dim3(lse::blocks_for(P, kThreads)), dim3(kThreads), 0, st, L, K, P, ref_in, s, counts, ref_out,
                            (float *)nullptr, (int32_t *)nullptr);
     }
     hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(kSumThreads), 0, st, (const int32_t *)counts, items, window_total);
@@ -340,15 +293,15 @@ extern "C" int lse_event_append(const float *L, const double *times, int64_t K, 
     LSE_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes < %lld", what, (long long)workspace_bytes, (long long)need);
     LSE_REQUIRE(L && times, "%s: null pointer", what);
     LSE_REQUIRE(cap == 0 || (out_x && out_y && out_t && out_p), "%s: null output for a capacity > 0", what);
-    const int n_segs = n_segments(items);
+    const int n_segs = lse::n_segments<kSeg>(items);
     int64_t *seg = static_cast<int64_t *>(workspace);
     float *ws_ref = reinterpret_cast<float *>(seg + n_segs);
     int32_t *ws_n = reinterpret_cast<int32_t *>(ws_ref + items);
     int32_t *rank = ws_n + items;
-    hipLaunchKernelGGL(walk_kernel, dim3(blocks_for(P, kThreads)), dim3(kThreads), 0, st, L, K, P, ref_in, s, counts, ref_out, ws_ref,
+    hipLaunchKernelGGL(walk_kernel, dim3(lse::blocks_for(P, kThreads)), dim3(kThreads), 0, st, L, K, P, ref_in, s, counts, ref_out, ws_ref,
                        ws_n);
-    hipLaunchKernelGGL(rank_kernel, dim3(blocks_for(n_segs, kWaves)), dim3(kThreads), 0, st, (const int32_t *)ws_n, items, n_segs, rank,
-                       seg);
+    hipLaunchKernelGGL(rank_kernel, dim3(lse::blocks_for(n_segs, kWaves)), dim3(kThreads), 0, st, (const int32_t *)ws_n, items, n_segs,
+                       rank, seg);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, st, seg, n_segs, total);
     if (cap > 0)
         hipLaunchKernelGGL(emit_kernel, item_grid(items), dim3(kThreads), 0, st, L, times, items, P, (int)W, s, (const float *)ws_ref,

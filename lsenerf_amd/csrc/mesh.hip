@@ -1,14 +1,16 @@
 // Mesh export for gfx950: naive surface nets of a density lattice (one vertex per active cell, one quad per sign-changing interior
 // lattice edge), the lattice's point positions, and world-space normals at arbitrary points.  The definition is in include/lse_hip.h
 // (and, as numpy, in tests/mesh_ref.py); the kernels restate it operation by operation, hence -ffp-contract=off.
-//   count_cells / count_quads   one wave owns LSE_MESH_SEGMENT consecutive cells (lattice points); ballot + popcount give the rank of
-//                    every active cell (quad) inside the segment and the segment's count.  Cell ranks go to the workspace.
-//   scan_kernel      one block per row (vertices, quads): segment counts -> exclusive offsets in place, totals -> device int64[2].
+// Vertices and quads are two ordered compactions (compact.h) over segments of LSE_MESH_SEGMENT cells / lattice points:
+//   count_cells      the active cells; cell ranks go to the workspace.
+//   count_quads      a lattice point carries up to three quads (one per axis), so its rank is "all quads of lower lanes, then its
+//                    own in axis order": three prefix counts per iteration.  Only the segment counts are kept.
+//   scan_kernel      one block per row (vertices, quads), totals -> device int64[2].
 //   emit_vertices    one thread per cell: rank >= 0 -> the mean of the edge crossings, mapped to world.
 //   emit_quads       the walk of count_quads again, with the ranks: two triangles per quad, in ascending (point, axis).
-// Fixed grids, no atomics, no host read: two runs give the same bytes.  All passes are bandwidth-bound flat maps over sigma with iz
-// fastest (a wave's corner reads are coalesced rows); nothing is staged in LDS.
-#include "common.h"
+// All passes are bandwidth-bound flat maps over sigma with iz fastest (a wave's corner reads are coalesced rows); nothing is staged
+// in LDS.
+#include "compact.h"
 
 namespace {
 
@@ -18,6 +20,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kSeg = LSE_MESH_SEGMENT;        // consecutive cells / lattice points owned by one wave
 constexpr int kIters = kSeg / 64;
+static_assert(kThreads == lse::kScanThreads, "scan_kernel is one block of kScanThreads");
 
 struct Lattice {
     int n[3];               // cells per axis
@@ -25,14 +28,13 @@ struct Lattice {
     int64_t cells, points;
 };
 
-__device__ __forceinline__ int wave_inclusive_sum_i(int v)
+// cell index -> (cx, cy, cz), cz fastest
+__device__ __forceinline__ void cell_coords(const Lattice &L, int64_t c, int cc[3])
 {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(v, off, 64);
-        if (lse::lane_id() >= off) v += n;
-    }
-    return v;
+    const uint32_t u = (uint32_t)c;
+    cc[2] = (int)(u % (uint32_t)L.n[2]);
+    cc[1] = (int)((u / (uint32_t)L.n[2]) % (uint32_t)L.n[1]);
+    cc[0] = (int)(u / ((uint32_t)L.n[2] * (uint32_t)L.n[1]));
 }
 
 // 8 corner values of cell (cx, cy, cz), index dx * 4 + dy * 2 + dz; all 8 points are inside the lattice for every valid cell
@@ -55,27 +57,15 @@ __device__ __forceinline__ bool cell_active(const float s[8], float level)
 __global__ __launch_bounds__(kThreads) void count_cells_kernel(const float *__restrict__ sigma, Lattice L, float level, int n_segs,
                                                                int32_t *__restrict__ cell_rank, int64_t *__restrict__ seg_counts)
 {
-    const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = lse::lane_id();
+    const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (seg >= n_segs) return;                          // (wave-uniform)
-    const uint64_t below = (1ull << lane) - 1ull;
-    int run = 0;
-    for (int it = 0; it < kIters; ++it) {
-        const int64_t c = (int64_t)seg * kSeg + it * 64 + lane;
-        const bool valid = c < L.cells;
-        bool act = false;
-        if (valid) {
-            const uint32_t u = (uint32_t)c;
-            const int cz = (int)(u % (uint32_t)L.n[2]), cy = (int)((u / (uint32_t)L.n[2]) % (uint32_t)L.n[1]);
-            const int cx = (int)(u / ((uint32_t)L.n[2] * (uint32_t)L.n[1]));
-            float s[8];
-            load_corners(sigma, L, cx, cy, cz, s);
-            act = cell_active(s, level);
-        }
-        const uint64_t mask = __ballot(act);
-        if (valid) cell_rank[c] = act ? run + __popcll(mask & below) : -1;
-        run += __popcll(mask);
-    }
-    if (lane == 0) seg_counts[seg] = run;
+    lse::segment_rank<kSeg>(seg, L.cells, cell_rank, seg_counts, [&](int64_t c) {
+        int cc[3];
+        float s[8];
+        cell_coords(L, c, cc);
+        load_corners(sigma, L, cc[0], cc[1], cc[2], s);
+        return cell_active(s, level);
+    });
 }
 
 // bit a: the lattice edge (p, a) gives a quad -- q = p + e_a exists, the edge is interior in the other two axes, inside(p) != inside(q)
@@ -122,7 +112,11 @@ __global__ __launch_bounds__(kThreads) void count_quads_kernel(const float *__re
             point_coords(L, p, i);
             bits = quad_bits(sigma, L, p, i, level, in_p);
         }
-        run += __popcll(__ballot(bits & 1)) + __popcll(__ballot(bits & 2)) + __popcll(__ballot(bits & 4));
+        int t0, t1, t2;
+        lse::wave_prefix_count(bits & 1, t0);
+        lse::wave_prefix_count(bits & 2, t1);
+        lse::wave_prefix_count(bits & 4, t2);
+        run += t0 + t1 + t2;
     }
     if (lane == 0) seg_counts[seg] = run;
 }
@@ -132,28 +126,8 @@ __global__ __launch_bounds__(kThreads) void count_quads_kernel(const float *__re
 __global__ __launch_bounds__(kThreads) void scan_kernel(int64_t *__restrict__ seg_v, int n_v, int64_t *__restrict__ seg_q, int n_q,
                                                         int64_t *__restrict__ totals)
 {
-    __shared__ int wsum[kWaves];
-    int64_t *t = blockIdx.x ? seg_q : seg_v;
-    const int n = blockIdx.x ? n_q : n_v;
-    const int w = threadIdx.x >> 6, lane = lse::lane_id();
-    int64_t carry = 0;
-    for (int c0 = 0; c0 < n; c0 += kThreads) {
-        const int i = c0 + threadIdx.x;
-        const int v = i < n ? (int)t[i] : 0;
-        const int inc = wave_inclusive_sum_i(v);
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int woff = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; ++k) {
-            if (k < w) woff += wsum[k];
-            total += wsum[k];
-        }
-        if (i < n) t[i] = carry + woff + inc - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+    const int64_t sum = lse::block_exclusive_scan<int>(blockIdx.x ? seg_q : seg_v, blockIdx.x ? n_q : n_v, (int64_t)0);
+    if (threadIdx.x == 0) totals[blockIdx.x] = sum;
 }
 
 // ---- emit -----------------------------------------------------------------------------------------------------------------------
@@ -164,16 +138,11 @@ __global__ __launch_bounds__(kThreads) void emit_vertices_kernel(const float *__
 {
     const int64_t c = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (c >= L.cells) return;
-    const int r = cell_rank[c];
-    if (r < 0) return;
-    const int64_t vid = seg_off[c / kSeg] + r;
-    if (vid >= cap) return;
-    const uint32_t u = (uint32_t)c;
+    const int64_t vid = lse::emit_row<kSeg>(c, cell_rank, seg_off, cap);
+    if (vid < 0) return;
     int cc[3];
-    cc[2] = (int)(u % (uint32_t)L.n[2]);
-    cc[1] = (int)((u / (uint32_t)L.n[2]) % (uint32_t)L.n[1]);
-    cc[0] = (int)(u / ((uint32_t)L.n[2] * (uint32_t)L.n[1]));
     float s[8];
+    cell_coords(L, c, cc);
     load_corners(sigma, L, cc[0], cc[1], cc[2], s);
     float sum[3] = {0.f, 0.f, 0.f};
     int count = 0;
@@ -218,7 +187,6 @@ __global__ __launch_bounds__(kThreads) void emit_quads_kernel(const float *__res
 {
     const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = lse::lane_id();
     if (seg >= n_segs) return;                          // (wave-uniform)
-    const uint64_t below = (1ull << lane) - 1ull;
     int64_t off = seg_off_q[seg];
     for (int it = 0; it < kIters; ++it) {
         const int64_t p = (int64_t)seg * kSeg + it * 64 + lane;
@@ -228,9 +196,11 @@ __global__ __launch_bounds__(kThreads) void emit_quads_kernel(const float *__res
             point_coords(L, p, i);
             bits = quad_bits(sigma, L, p, i, level, in_p);
         }
-        const uint64_t m0 = __ballot(bits & 1), m1 = __ballot(bits & 2), m2 = __ballot(bits & 4);
-        int64_t qid = off + __popcll(m0 & below) + __popcll(m1 & below) + __popcll(m2 & below);
-        off += __popcll(m0) + __popcll(m1) + __popcll(m2);
+        int t0, t1, t2;
+        const int b0 = lse::wave_prefix_count(bits & 1, t0), b1 = lse::wave_prefix_count(bits & 2, t1);
+        const int b2 = lse::wave_prefix_count(bits & 4, t2);
+        int64_t qid = off + b0 + b1 + b2;       // all quads of lower lanes, then this point's own in axis order
+        off += t0 + t1 + t2;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             if (!(bits & (1 << a))) continue;
@@ -245,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void emit_quads_kernel(const float *__res
                 cc[b] -= (k == 0 || k == 3) ? 1 : 0;        // C0 = p - e_b - e_c, C1 = p - e_c, C2 = p, C3 = p - e_b
                 cc[c] -= (k == 0 || k == 1) ? 1 : 0;
                 const int64_t ci = ((int64_t)cc[0] * L.n[1] + cc[1]) * L.n[2] + cc[2];
-                w[k] = (int32_t)(seg_off_v[ci / kSeg] + cell_rank[ci]);
+                w[k] = (int32_t)lse::segment_row<kSeg>(ci, cell_rank, seg_off_v);
             }
             if (!in_p) {
                 const int32_t t0 = w[0], t1 = w[1];
@@ -304,8 +274,6 @@ bool make_lattice(int32_t nx, int32_t ny, int32_t nz, Lattice &L)
     return true;
 }
 
-inline int n_segments(int64_t items) { return (int)((items + kSeg - 1) / kSeg); }
-
 struct Workspace {
     int64_t *seg_v, *seg_q;
     int32_t *cell_rank;
@@ -316,8 +284,8 @@ struct Workspace {
 Workspace carve(const Lattice &L, void *base)
 {
     Workspace w;
-    w.n_v = n_segments(L.cells);
-    w.n_q = n_segments(L.points);
+    w.n_v = lse::n_segments<kSeg>(L.cells);
+    w.n_q = lse::n_segments<kSeg>(L.points);
     w.seg_v = static_cast<int64_t *>(base);
     w.seg_q = w.seg_v + w.n_v;
     w.cell_rank = reinterpret_cast<int32_t *>(w.seg_q + w.n_q);
@@ -331,8 +299,6 @@ Box make_box(const float *h_lo, const float *h_hi)
     for (int k = 0; k < 3; ++k) { box.lo[k] = h_lo[k]; box.hi[k] = h_hi[k]; }
     return box;
 }
-
-inline unsigned blocks_for(int64_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
 }  // namespace
 
@@ -348,7 +314,7 @@ extern "C" int lse_lattice_positions(const float *h_lo, const float *h_hi, int32
                 (long long)first, (long long)first, (long long)n, (long long)L.points);
     if (n == 0) return LSE_OK;
     LSE_REQUIRE(positions, "%s: null pointer", what);
-    hipLaunchKernelGGL(lattice_positions_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, lse::as_stream(stream), L,
+    hipLaunchKernelGGL(lattice_positions_kernel, dim3(lse::blocks_for(n, kThreads)), dim3(kThreads), 0, lse::as_stream(stream), L,
                        make_box(h_lo, h_hi), first, n, positions);
     return lse::check_launch(what);
 }
@@ -378,9 +344,9 @@ extern "C" int lse_surface_nets_count(const float *sigma, int32_t nx, int32_t ny
     LSE_REQUIRE(workspace_bytes >= w.bytes, "%s: workspace of %lld bytes < %lld (lse_surface_nets_workspace)", what,
                 (long long)workspace_bytes, (long long)w.bytes);
     hipStream_t st = lse::as_stream(stream);
-    hipLaunchKernelGGL(count_cells_kernel, dim3(blocks_for(w.n_v, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_v, w.cell_rank,
+    hipLaunchKernelGGL(count_cells_kernel, dim3(lse::blocks_for(w.n_v, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_v, w.cell_rank,
                        w.seg_v);
-    hipLaunchKernelGGL(count_quads_kernel, dim3(blocks_for(w.n_q, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_q, w.seg_q);
+    hipLaunchKernelGGL(count_quads_kernel, dim3(lse::blocks_for(w.n_q, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_q, w.seg_q);
     hipLaunchKernelGGL(scan_kernel, dim3(2), dim3(kThreads), 0, st, w.seg_v, w.n_v, w.seg_q, w.n_q, totals);
     return lse::check_launch(what);
 }
@@ -402,10 +368,10 @@ extern "C" int lse_surface_nets_emit(const float *sigma, int32_t nx, int32_t ny,
     LSE_REQUIRE((cap_vertices == 0 || vertices) && (cap_quads == 0 || triangles), "%s: null output for a capacity > 0", what);
     hipStream_t st = lse::as_stream(stream);
     if (cap_vertices > 0)
-        hipLaunchKernelGGL(emit_vertices_kernel, dim3(blocks_for(L.cells, kThreads)), dim3(kThreads), 0, st, sigma, L,
+        hipLaunchKernelGGL(emit_vertices_kernel, dim3(lse::blocks_for(L.cells, kThreads)), dim3(kThreads), 0, st, sigma, L,
                            make_box(h_lo, h_hi), level, (const int32_t *)w.cell_rank, (const int64_t *)w.seg_v, cap_vertices, vertices);
     if (cap_quads > 0)
-        hipLaunchKernelGGL(emit_quads_kernel, dim3(blocks_for(w.n_q, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_q,
+        hipLaunchKernelGGL(emit_quads_kernel, dim3(lse::blocks_for(w.n_q, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_q,
                            (const int32_t *)w.cell_rank, (const int64_t *)w.seg_v, (const int64_t *)w.seg_q, cap_quads, triangles);
     return lse::check_launch(what);
 }
@@ -420,7 +386,7 @@ extern "C" int lse_point_normals_world(const float *d_x01, const float *position
     LSE_REQUIRE(d_x01 && positions && out, "%s: null pointer", what);
     Box box;
     for (int k = 0; k < 3; ++k) { box.lo[k] = h_aabb ? h_aabb[k] : -1.f; box.hi[k] = h_aabb ? h_aabb[3 + k] : 1.f; }
-    hipLaunchKernelGGL(point_normals_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, lse::as_stream(stream), d_x01, positions,
+    hipLaunchKernelGGL(point_normals_kernel, dim3(lse::blocks_for(n, kThreads)), dim3(kThreads), 0, lse::as_stream(stream), d_x01, positions,
                        (int)contraction, box, n, n_dev, out);
     return lse::check_launch(what);
 }

@@ -36,12 +36,8 @@ struct Window {
     float w[kWin];
 };
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+using lse::gray3;
+using lse::wave_sum_d;
 
 __device__ __forceinline__ float wave_min(float v)
 {
@@ -198,13 +194,6 @@ __global__ __launch_bounds__(kFinalThreads) void metrics_final_kernel(const doub
 
 // ---- eval images: ground truth + render -> metric planes, and the event-only metric's log-space scale correction ----------------
 constexpr int kPrepThreads = 256;
-
-// to_gray of the reference (img @ [0.2989, 0.5870, 0.1140]): three products summed left to right, every operation rounded once
-__device__ __forceinline__ float gray3(float r, float g, float b)
-{
-#pragma clang fp contract(off)
-    return (r * 0.2989f + g * 0.5870f) + b * 0.1140f;
-}
 
 // log of the prediction's R + G (its blue channel zeroed, then summed over the channels), unmasked
 __device__ __forceinline__ float log_pred(const float *__restrict__ rgb, int64_t p)

@@ -1,15 +1,17 @@
 // Count-free occupancy-grid refresh for gfx950: the index generation of nerfacc's OccGridEstimator._update as
 // device code, so that a refresh sizes nothing from a device value and captures into a HIP graph.
-//   list_count / list_scan / list_write   ascending indices of the set cells of every level (== torch.nonzero): one wave owns 1024
-//                    consecutive cells of a 4096-cell tile, ballot + popcount give its count and the lanes' ranks; the tile
-//                    counts are scanned by one block per level; the write pass recomputes the ballots.  No atomics.
-//   draw_kernel      one thread per slot: Philox4x32-10 (the stream of compose.hip: counter (step, slot, level, 0)), the cell
-//                    (occupied list / uniform / every cell during warm-up), its jittered position, n_dev of the level.
+//   list_count / list_scan / list_write   ascending indices of the set cells of every level (== torch.nonzero): the ordered
+//                    compaction of compact.h in this file's own layout -- one wave owns 1024 consecutive cells of a 4096-cell
+//                    tile, int32 tile counts are scanned by one block per level, and the write pass recomputes the ballots
+//                    instead of reading stored ranks.  No atomics.
+//   draw_kernel      one thread per slot: Philox4x32-10 (philox.h, shared with compose.hip) at counter (step, slot, level, 0), the
+//                    cell (occupied list / uniform / every cell during warm-up), its jittered position, n_dev of the level.
 //   ema_pass1..3     lse_occ_update_cells' three passes with the count read from n_dev and ids < 0 skipped.
 //   mean_stage1 / 2  mean(occs) and min(mean(occs[occs >= 0]), occ_thre): fixed grid, double accumulators, fixed order.
 // All of it is bandwidth- or latency-bound work over at most a few million cells.  Compiled with -ffp-contract=off: the position
 // arithmetic restates the torch expression of _update_samples operation by operation (lsenerf_amd/occ_refresh.py: draw_cells_host).
-#include "common.h"
+#include "compact.h"
+#include "philox.h"
 
 namespace {
 
@@ -17,34 +19,10 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kWaveCells = LSE_OCC_LIST_TILE / kWaves;      // consecutive cells owned by one wave
 constexpr int kIters = kWaveCells / 64;
+static_assert(kThreads == lse::kScanThreads, "list_scan_kernel is blocks of kScanThreads");
 
-// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) -- as in compose.hip
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-__device__ __forceinline__ int wave_inclusive_sum_i(int v)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(v, off, 64);
-        if (lse::lane_id() >= off) v += n;
-    }
-    return v;
-}
+using lse::U4;
+using lse::wave_sum_d;
 
 // ---- 1. occupied-cell list ----------------------------------------------------------------------------------------------------
 // set cells among the 1024 cells of this wave that start at `base` (wave-uniform result; every lane takes every iteration)
@@ -54,8 +32,9 @@ __device__ __forceinline__ int wave_segment_count(const uint8_t *__restrict__ lv
 #pragma unroll 4
     for (int it = 0; it < kIters; ++it) {
         const int64_t i = base + it * 64 + lane;
-        const bool set = i < cells && lv[i] != 0;
-        c += __popcll(__ballot(set));
+        int total;
+        lse::wave_prefix_count(i < cells && lv[i] != 0, total);
+        c += total;
     }
     return c;
 }
@@ -74,27 +53,8 @@ __global__ __launch_bounds__(kThreads) void list_count_kernel(const uint8_t *__r
 // one block per level: tile counts -> exclusive offsets (in place), total -> counts[level]
 __global__ __launch_bounds__(kThreads) void list_scan_kernel(int32_t *__restrict__ tile_counts, int n_tiles, int64_t *__restrict__ counts)
 {
-    __shared__ int wsum[kWaves];
-    int32_t *t = tile_counts + (int64_t)blockIdx.x * n_tiles;
-    const int w = threadIdx.x >> 6, lane = lse::lane_id();
-    int carry = 0;
-    for (int c0 = 0; c0 < n_tiles; c0 += kThreads) {
-        const int i = c0 + threadIdx.x;
-        const int v = i < n_tiles ? t[i] : 0;
-        const int inc = wave_inclusive_sum_i(v);
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int woff = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; ++k) {
-            if (k < w) woff += wsum[k];
-            total += wsum[k];
-        }
-        if (i < n_tiles) t[i] = carry + woff + inc - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[blockIdx.x] = carry;
+    const int sum = lse::block_exclusive_scan<int>(tile_counts + (int64_t)blockIdx.x * n_tiles, n_tiles, 0);
+    if (threadIdx.x == 0) counts[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kThreads) void list_write_kernel(const uint8_t *__restrict__ bin, int64_t cells, int n_tiles,
@@ -113,14 +73,14 @@ __global__ __launch_bounds__(kThreads) void list_write_kernel(const uint8_t *__r
         if (k < w) off += sh[k];
     if (c == 0) return;                         // (wave-uniform)
     int32_t *out = list + (int64_t)level * cells;
-    const uint64_t below = (1ull << lane) - 1ull;
     for (int it = 0; it < kIters; ++it) {
         const int64_t i = base + it * 64 + lane;
         const bool set = i < cells && lv[i] != 0;
-        const uint64_t mask = __ballot(set);
+        int total;
+        const int below = lse::wave_prefix_count(set, total);
         // rank < the level's count <= cells: inside the level's row of the list
-        if (set) out[off + __popcll(mask & below)] = (int32_t)i;
-        off += __popcll(mask);
+        if (set) out[off + below] = (int32_t)i;
+        off += total;
     }
 }
 
@@ -143,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void draw_kernel(const float *__restrict_
     if (n > cap) n = cap;                       // (the entry point checks cap >= cells / 2 N: never taken)
     if (i == 0) *n_dev = n;
     if (i >= n) return;
-    const U4 r = philox4x32_10(U4{(uint32_t)*step_dev, (uint32_t)i, (uint32_t)level, 0u}, k0, k1);
+    const U4 r = lse::philox4x32_10(U4{(uint32_t)*step_dev, (uint32_t)i, (uint32_t)level, 0u}, k0, k1);
     const int64_t row = (int64_t)level * cells;
     int64_t idx;
     if (warmup)
@@ -191,13 +151,6 @@ __global__ void ema_pass3(float *__restrict__ occs, const int64_t *__restrict__ 
 }
 
 // ---- 4. mean and threshold ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // sums of one block's three accumulators, in a fixed order; valid in thread 0
 __device__ __forceinline__ void block_sum3(double &a, double &b, double &c)
 {

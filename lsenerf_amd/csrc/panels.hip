@@ -15,8 +15,7 @@ constexpr int kMinMaxBlocks = 256;              // at most this many partials of
 // (uint8) trunc(min(max(v * 255, 0), 255)); a NaN gives 0 (fmaxf returns its other argument)
 __device__ __forceinline__ uint8_t to_u8(float v) { return (uint8_t)(int)fminf(fmaxf(v * 255.0f, 0.0f), 255.0f); }
 
-// the grey of lse_eval_image_prep: (0.2989 r + 0.5870 g) + 0.1140 b, each operation rounded
-__device__ __forceinline__ float gray3(float r, float g, float b) { return (r * 0.2989f + g * 0.5870f) + b * 0.1140f; }
+using lse::gray3;       // the grey of lse_eval_image_prep
 
 __global__ __launch_bounds__(kThreads) void gray8_kernel(const float *__restrict__ a, const float *__restrict__ b, int64_t HW,
                                                          uint8_t *__restrict__ out)

@@ -2,87 +2,25 @@
 // voxel keys, the per-voxel merge of a key-sorted cloud, and the neighbour-support ("floater") filter.  The definition is in
 // include/lse_hip.h ("point-cloud export") and, as numpy, in tests/pointcloud_ref.py; the kernels restate it operation by operation,
 // hence -ffp-contract=off.
-// The three compacting entry points share one ordered compaction (the pattern of mesh.hip):
-//   count_*          one wave owns LSE_PC_SEGMENT consecutive items; ballot + popcount give every kept item its rank inside the
-//                    segment (-1: dropped) and the segment its count                                       (segment_rank)
-//   scan_kernel      one block: segment counts -> exclusive offsets in place (int64), *total += or = the sum
-//   emit_*           one thread per item: row = offset of its segment + rank; rows at or beyond cap are not written   (emit_row)
-// Fixed grids sized from the extent, no atomics, plain vector stores, no host read: two runs give the same bytes.
-#include "common.h"
+// The three compacting entry points (count_* / scan_kernel / emit_*) are the ordered compaction of compact.h over segments of
+// LSE_PC_SEGMENT items, with the plain workspace.
+#include "compact.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kSeg = LSE_PC_SEGMENT;          // consecutive items owned by one wave
-constexpr int kIters = kSeg / 64;
-constexpr int64_t kMaxItems = 1ll << 40;      // extent limit of every entry point: segment and block counts stay far inside int
+static_assert(kThreads == lse::kScanThreads, "scan_kernel is one block of kScanThreads");
 constexpr int kMaxAxis = 1 << 20;             // voxels per axis: a key stays below 2^60
 constexpr int64_t kNoKey = INT64_MAX;
-
-__device__ __forceinline__ int wave_inclusive_sum_i(int v)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(v, off, 64);
-        if (lse::lane_id() >= off) v += n;
-    }
-    return v;
-}
-
-// ---- the ordered compaction, written once -----------------------------------------------------------------------------------------
-// Called by every lane of the wave that owns segment `seg`; keep(i) is evaluated once per item i < n, in ascending i per lane.
-template <class Keep>
-__device__ __forceinline__ void segment_rank(int seg, int64_t n, int32_t *__restrict__ rank, int64_t *__restrict__ seg_counts, Keep keep)
-{
-    const int lane = lse::lane_id();
-    const uint64_t below = (1ull << lane) - 1ull;
-    int run = 0;
-    for (int it = 0; it < kIters; ++it) {
-        const int64_t i = (int64_t)seg * kSeg + it * 64 + lane;
-        const bool valid = i < n;
-        const bool k = valid ? keep(i) : false;
-        const uint64_t mask = __ballot(k);
-        if (valid) rank[i] = k ? run + __popcll(mask & below) : -1;
-        run += __popcll(mask);
-    }
-    if (lane == 0) seg_counts[seg] = run;
-}
 
 // one block.  Counts -> exclusive offsets in place; append: offsets start at the *total of entry and *total += sum, else *total = sum.
 // A segment's count is at most kSeg, so a 256-segment step sums in int; the carry is int64.
 __global__ __launch_bounds__(kThreads) void scan_kernel(int64_t *__restrict__ seg, int n_segs, int append, int64_t *__restrict__ total)
 {
-    __shared__ int wsum[kWaves];
-    const int w = threadIdx.x >> 6, lane = lse::lane_id();
-    int64_t carry = append ? *total : 0;
-    for (int c0 = 0; c0 < n_segs; c0 += kThreads) {
-        const int i = c0 + threadIdx.x;
-        const int v = i < n_segs ? (int)seg[i] : 0;
-        const int inc = wave_inclusive_sum_i(v);
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int woff = 0, sum = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; ++k) {
-            if (k < w) woff += wsum[k];
-            sum += wsum[k];
-        }
-        if (i < n_segs) seg[i] = carry + woff + inc - v;
-        carry += sum;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;       // (every thread has read the entry value: the loop's barriers lie in between,
-                                                //  and with no segment nothing else reads it)
-}
-
-// output row of item i, or -1: dropped, or at or beyond the capacity
-__device__ __forceinline__ int64_t emit_row(int64_t i, const int32_t *__restrict__ rank, const int64_t *__restrict__ seg_off, int64_t cap)
-{
-    const int r = rank[i];
-    if (r < 0) return -1;
-    const int64_t row = seg_off[i / kSeg] + r;
-    return row < cap ? row : -1;
+    const int64_t sum = lse::block_exclusive_scan<int>(seg, n_segs, append ? *total : (int64_t)0);
+    if (threadIdx.x == 0) *total = sum;
 }
 
 __device__ __forceinline__ void copy3(float *__restrict__ dst, int64_t row, const float *__restrict__ src, int64_t i)
@@ -112,7 +50,7 @@ __global__ __launch_bounds__(kThreads) void count_rays_kernel(const float *__res
 {
     const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (seg >= n_segs) return;                          // (wave-uniform)
-    segment_rank(seg, n, rank, seg_counts, [&](int64_t r) {
+    lse::segment_rank<kSeg>(seg, n, rank, seg_counts, [&](int64_t r) {
         const float t = depth[r];
         bool keep = acc[r] >= min_acc && t > 0.f && t < INFINITY;       // every comparison is false on NaN
         float p[3];
@@ -132,7 +70,7 @@ __global__ __launch_bounds__(kThreads) void emit_rays_kernel(const float *__rest
 {
     const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (r >= n) return;
-    const int64_t row = emit_row(r, rank, seg_off, cap);
+    const int64_t row = lse::emit_row<kSeg>(r, rank, seg_off, cap);
     if (row < 0) return;
     float p[3];
     unproject(origins, directions, depth[r], r, p);
@@ -177,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void count_heads_kernel(const int64_t *__
 {
     const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (seg >= n_segs) return;                          // (wave-uniform)
-    segment_rank(seg, n, rank, seg_counts, [&](int64_t i) { return is_head(sorted_keys, i); });
+    lse::segment_rank<kSeg>(seg, n, rank, seg_counts, [&](int64_t i) { return is_head(sorted_keys, i); });
 }
 
 // s = first element, then + the others one by one in run order; an index outside [0, n) is skipped (never an out-of-bounds read)
@@ -206,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void emit_voxels_kernel(const int64_t *__
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
-    const int64_t row = emit_row(i, rank, seg_off, cap);
+    const int64_t row = lse::emit_row<kSeg>(i, rank, seg_off, cap);
     if (row < 0) return;
     const int64_t key = sorted_keys[i];
     int c = 1;
@@ -277,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void count_support_kernel(const int64_t *
     const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (seg >= n_segs) return;                          // (wave-uniform)
     const int64_t count = lse::clamp_count(m, m_dev);
-    segment_rank(seg, m, rank, seg_counts, [&](int64_t j) {
+    lse::segment_rank<kSeg>(seg, m, rank, seg_counts, [&](int64_t j) {
         const bool present = j < count;
         const int64_t s = present ? support_of(keys, counts, count, V, j) : 0;
         if (out_support) out_support[j] = s > INT32_MAX ? INT32_MAX : (int32_t)s;
@@ -295,7 +233,7 @@ __global__ __launch_bounds__(kThreads) void emit_kept_kernel(const int64_t *__re
 {
     const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (j >= m) return;
-    const int64_t row = emit_row(j, rank, seg_off, cap);
+    const int64_t row = lse::emit_row<kSeg>(j, rank, seg_off, cap);
     if (row < 0) return;
     out_keys[row] = keys[j];
     out_counts[row] = counts[j];
@@ -305,47 +243,11 @@ __global__ __launch_bounds__(kThreads) void emit_kept_kernel(const int64_t *__re
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-inline int n_segments(int64_t items) { return (int)((items + kSeg - 1) / kSeg); }
-inline unsigned blocks_for(int64_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
-// the workspace of every compacting entry point: per segment an int64 count / offset, per item an int32 rank
-struct Workspace {
-    int64_t *seg;
-    int32_t *rank;
-    int n_segs;
-    int64_t bytes;
-};
-
-inline int64_t workspace_bytes_for(int64_t items) { return 8 * (int64_t)n_segments(items) + 4 * items; }
-
-Workspace carve(int64_t items, void *base)
-{
-    Workspace w;
-    w.n_segs = n_segments(items);
-    w.seg = static_cast<int64_t *>(base);
-    w.rank = base ? reinterpret_cast<int32_t *>(w.seg + w.n_segs) : nullptr;      // (no workspace: an extent of 0)
-    w.bytes = workspace_bytes_for(items);
-    return w;
-}
-
 int workspace_bytes_of(const char *what, int64_t items, int64_t *h_bytes)
 {
-    LSE_REQUIRE(items >= 0 && items <= kMaxItems, "%s: extent %lld outside [0, 2^40]", what, (long long)items);
+    LSE_REQUIRE(items >= 0 && items <= lse::kMaxCompactItems, "%s: extent %lld outside [0, 2^40]", what, (long long)items);
     LSE_REQUIRE(h_bytes, "%s: null pointer", what);
-    *h_bytes = workspace_bytes_for(items);
-    return LSE_OK;
-}
-
-// what every compacting entry point checks about (extent, workspace, cap, total) before it launches anything
-int check_compaction(const char *what, int64_t items, const void *workspace, int64_t workspace_bytes, int64_t cap, const int64_t *total)
-{
-    LSE_REQUIRE(items >= 0 && items <= kMaxItems, "%s: extent %lld outside [0, 2^40]", what, (long long)items);
-    LSE_REQUIRE(cap >= 0, "%s: negative capacity", what);
-    LSE_REQUIRE(total && ((uintptr_t)total & 7) == 0, "%s: total must be a non-null, 8-byte aligned device pointer", what);
-    if (items == 0) return LSE_OK;
-    const int64_t need = workspace_bytes_for(items);
-    LSE_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0, "%s: workspace must be a non-null, 8-byte aligned device pointer", what);
-    LSE_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes < %lld", what, (long long)workspace_bytes, (long long)need);
+    *h_bytes = lse::compact_workspace_bytes<kSeg>(items);
     return LSE_OK;
 }
 
@@ -376,20 +278,20 @@ extern "C" int lse_unproject_append(const float *origins, const float *direction
                                     float *out_colors, float *out_normals, int64_t *total, lse_stream_t stream)
 {
     const char *what = "lse_unproject_append";
-    if (int rc = check_compaction(what, n_rays, workspace, workspace_bytes, cap, total)) return rc;
+    if (int rc = lse::check_compaction<kSeg>(what, n_rays, workspace, workspace_bytes, cap, total)) return rc;
     LSE_REQUIRE(h_lo && h_hi, "%s: null box", what);
     if (n_rays == 0) return LSE_OK;                     // nothing to append: *total stays
     LSE_REQUIRE((!out_colors || colors) && (!out_normals || normals), "%s: an output without its input", what);
     LSE_REQUIRE(origins && directions && depth && acc, "%s: null pointer", what);
     LSE_REQUIRE(cap == 0 || out_points, "%s: null output for a capacity > 0", what);
-    const Workspace w = carve(n_rays, workspace);
+    const lse::CompactWorkspace w = lse::carve_compact<kSeg>(n_rays, workspace);
     hipStream_t st = lse::as_stream(stream);
-    hipLaunchKernelGGL(count_rays_kernel, dim3(blocks_for(w.n_segs, kWaves)), dim3(kThreads), 0, st, origins, directions, depth, acc,
+    hipLaunchKernelGGL(count_rays_kernel, dim3(lse::blocks_for(w.n_segs, kWaves)), dim3(kThreads), 0, st, origins, directions, depth, acc,
                        n_rays, make_box(h_lo, h_hi), min_acc, w.n_segs, w.rank, w.seg);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, st, w.seg, w.n_segs, 1, total);
     if (cap > 0)
-        hipLaunchKernelGGL(emit_rays_kernel, dim3(blocks_for(n_rays, kThreads)), dim3(kThreads), 0, st, origins, directions, depth, colors,
-                           normals, n_rays, (const int32_t *)w.rank, (const int64_t *)w.seg, cap, out_points, out_colors, out_normals);
+        hipLaunchKernelGGL(emit_rays_kernel, dim3(lse::blocks_for(n_rays, kThreads)), dim3(kThreads), 0, st, origins, directions, depth,
+                           colors, normals, n_rays, (const int32_t *)w.rank, (const int64_t *)w.seg, cap, out_points, out_colors, out_normals);
     return lse::check_launch(what);
 }
 
@@ -399,12 +301,12 @@ extern "C" int lse_voxel_keys(const float *points, int64_t n, const int64_t *n_d
     const char *what = "lse_voxel_keys";
     Voxels V;
     LSE_REQUIRE(make_voxels(nx, ny, nz, V), "%s: lattice %d x %d x %d: every count in [1, 2^20]", what, nx, ny, nz);
-    LSE_REQUIRE(n >= 0 && n <= kMaxItems, "%s: extent %lld outside [0, 2^40]", what, (long long)n);
+    LSE_REQUIRE(n >= 0 && n <= lse::kMaxCompactItems, "%s: extent %lld outside [0, 2^40]", what, (long long)n);
     LSE_REQUIRE(voxel > 0.f && voxel < INFINITY, "%s: the voxel size must be positive and finite", what);
     LSE_REQUIRE(h_lo, "%s: null box", what);
     if (n == 0) return LSE_OK;
     LSE_REQUIRE(points && keys, "%s: null pointer", what);
-    hipLaunchKernelGGL(voxel_keys_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, lse::as_stream(stream), points, n, n_dev,
+    hipLaunchKernelGGL(voxel_keys_kernel, dim3(lse::blocks_for(n, kThreads)), dim3(kThreads), 0, lse::as_stream(stream), points, n, n_dev,
                        make_box(h_lo, nullptr), voxel, V, keys);
     return lse::check_launch(what);
 }
@@ -420,20 +322,20 @@ extern "C" int lse_voxel_merge(const int64_t *sorted_keys, const int64_t *order,
                                int64_t *total, lse_stream_t stream)
 {
     const char *what = "lse_voxel_merge";
-    if (int rc = check_compaction(what, n, workspace, workspace_bytes, cap, total)) return rc;
+    if (int rc = lse::check_compaction<kSeg>(what, n, workspace, workspace_bytes, cap, total)) return rc;
     LSE_REQUIRE(n == 0 || ((!out_colors || colors) && (!out_normals || normals)), "%s: an output without its input", what);
     LSE_REQUIRE(n == 0 || (sorted_keys && order && points), "%s: null pointer", what);
     LSE_REQUIRE(n == 0 || cap == 0 || (out_keys && out_counts && out_points), "%s: null output for a capacity > 0", what);
-    const Workspace w = carve(n, workspace);
+    const lse::CompactWorkspace w = lse::carve_compact<kSeg>(n, workspace);
     hipStream_t st = lse::as_stream(stream);
     if (n > 0)
-        hipLaunchKernelGGL(count_heads_kernel, dim3(blocks_for(w.n_segs, kWaves)), dim3(kThreads), 0, st, sorted_keys, n, w.n_segs, w.rank,
-                           w.seg);
+        hipLaunchKernelGGL(count_heads_kernel, dim3(lse::blocks_for(w.n_segs, kWaves)), dim3(kThreads), 0, st, sorted_keys, n, w.n_segs,
+                           w.rank, w.seg);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, st, w.seg, w.n_segs, 0, total);       // (no segment: *total = 0)
     if (n > 0 && cap > 0)
-        hipLaunchKernelGGL(emit_voxels_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, st, sorted_keys, order, points, colors,
-                           normals, n, (const int32_t *)w.rank, (const int64_t *)w.seg, cap, out_keys, out_counts, out_points, out_colors,
-                           out_normals);
+        hipLaunchKernelGGL(emit_voxels_kernel, dim3(lse::blocks_for(n, kThreads)), dim3(kThreads), 0, st, sorted_keys, order, points,
+                           colors, normals, n, (const int32_t *)w.rank, (const int64_t *)w.seg, cap, out_keys, out_counts, out_points,
+                           out_colors, out_normals);
     return lse::check_launch(what);
 }
 
@@ -451,19 +353,19 @@ extern "C" int lse_voxel_support_filter(const int64_t *keys, const int32_t *coun
     const char *what = "lse_voxel_support_filter";
     Voxels V;
     LSE_REQUIRE(make_voxels(nx, ny, nz, V), "%s: lattice %d x %d x %d: every count in [1, 2^20]", what, nx, ny, nz);
-    if (int rc = check_compaction(what, m, workspace, workspace_bytes, cap, total)) return rc;
+    if (int rc = lse::check_compaction<kSeg>(what, m, workspace, workspace_bytes, cap, total)) return rc;
     LSE_REQUIRE(m == 0 || ((!out_colors || colors) && (!out_normals || normals)), "%s: an output without its input", what);
     LSE_REQUIRE(m == 0 || (keys && counts && points), "%s: null pointer", what);
     LSE_REQUIRE(m == 0 || cap == 0 || (out_keys && out_counts && out_points), "%s: null output for a capacity > 0", what);
-    const Workspace w = carve(m, workspace);
+    const lse::CompactWorkspace w = lse::carve_compact<kSeg>(m, workspace);
     hipStream_t st = lse::as_stream(stream);
     if (m > 0)
-        hipLaunchKernelGGL(count_support_kernel, dim3(blocks_for(w.n_segs, kWaves)), dim3(kThreads), 0, st, keys, counts, m, m_dev, V,
+        hipLaunchKernelGGL(count_support_kernel, dim3(lse::blocks_for(w.n_segs, kWaves)), dim3(kThreads), 0, st, keys, counts, m, m_dev, V,
                            min_support, w.n_segs, w.rank, w.seg, out_support);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, st, w.seg, w.n_segs, 0, total);       // (no segment: *total = 0)
     if (m > 0 && cap > 0)
-        hipLaunchKernelGGL(emit_kept_kernel, dim3(blocks_for(m, kThreads)), dim3(kThreads), 0, st, keys, counts, points, colors, normals, m,
-                           (const int32_t *)w.rank, (const int64_t *)w.seg, cap, out_keys, out_counts, out_points, out_colors,
+        hipLaunchKernelGGL(emit_kept_kernel, dim3(lse::blocks_for(m, kThreads)), dim3(kThreads), 0, st, keys, counts, points, colors, normals,
+                           m, (const int32_t *)w.rank, (const int64_t *)w.seg, cap, out_keys, out_counts, out_points, out_colors,
                            out_normals);
     return lse::check_launch(what);
 }

@@ -1,7 +1,8 @@
 """The event synthesis entry points (csrc/events.hip) against the numpy twin (tests/events_ref.py), bit for bit: counts, x, y, p, the
 float64 times, ref_out and the totals.  Shapes: one pixel, less than a wave, several waves, planes that are no multiple of 64 or of
 the 1024-item segment, segment borders inside an interval and across intervals; a wave without any event and a wave whose every lane
-saturates at cap_step."""
+saturates at cap_step; 300 x 300 pixels over 3 intervals are 264 segments, more than the scan block's 256 threads: a second scan step,
+in the chained windows behind a non-zero total."""
 import functools
 
 import numpy as np
@@ -12,7 +13,7 @@ from tests import events_ref as er
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1, 1), (1, 5, 7), (9, 5, 7), (4, 3, 343), (3, 24, 40), (2, 1, 2050)]
+SHAPES = [(1, 1, 1), (1, 5, 7), (9, 5, 7), (4, 3, 343), (3, 24, 40), (2, 1, 2050), (3, 300, 300)]
 C_POS, C_NEG = 0.2, 0.25
 SENTINEL = -77
 
@@ -127,7 +128,7 @@ def test_nan_and_infinite_planes_and_a_far_level(shape):
         _assert_stream(bufs, ev)
 
 
-@pytest.mark.parametrize("shape", [(9, 5, 7), (4, 3, 343)])
+@pytest.mark.parametrize("shape", [(9, 5, 7), (4, 3, 343), (6, 300, 300)])        # the last: 3 intervals, 264 segments, per window
 def test_windows_chain_behind_one_total(shape):
     from lsenerf_amd import ops
     K, H, W = shape

@@ -134,6 +134,16 @@ def test_three_appends_share_one_total():
     assert int(t.item()) == 40 + wtotal and same_bits(P[40:40 + wtotal], wp) and bool((P[:40] == SENTINEL).all())
 
 
+def test_append_of_more_segments_than_scan_threads_behind_a_total():
+    """263 169 rays are 258 segments: the scan block takes a second step, its last segment holds one ray, and its carry starts at the
+    non-zero total the first view left."""
+    n = 257 * 1024 + 1
+    small, large = ray_field(5000, seed=40), ray_field(n, seed=41)
+    total = check_append([small, large], 5000 + n, True, False)
+    kept_small = int(pr.unproject(*small[:4], LO, HI, MIN_ACC)[1].sum())
+    assert kept_small > 0 and 0 < total - kept_small < n
+
+
 def test_append_with_every_ray_dropped_and_with_no_ray():
     o, d, t, a, c, n = ray_field(1500, seed=3)
     P, C, N, total = gpu_append([(o, d, t, np.zeros_like(a), c, n)], 1500)

@@ -32,7 +32,10 @@ def test_header_library_and_binding_carry_the_refresh_entry_points():
     with open(os.path.join(ROOT, "lsenerf_amd", "csrc", "Makefile")) as fh:
         mk = fh.read()
     assert re.search(r"^SRCS = .*\bocc_refresh\b", mk, re.M)
-    assert mk.count("-ffp-contract=off -c $< -o $@") == 6                        # traverse, compose, occ_refresh: shipped and dev
+    strict = re.search(r"^STRICT = (.*)$", mk, re.M).group(1).split()           # the sources built without FMA contraction ...
+    assert {"traverse", "compose", "occ_refresh"} <= set(strict) <= set(re.search(r"^SRCS = (.*)$", mk, re.M).group(1).split())
+    # ... by one rule, shipped and dev
+    assert re.search(r"^\$\(STRICT:%=%\.o\) \$\(STRICT:%=dev/%\.o\): FLAGS \+= -ffp-contract=off$", mk, re.M)
 
 
 def test_fixed_counters_give_fixed_words():

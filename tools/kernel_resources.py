@@ -22,5 +22,5 @@ for line in out.splitlines():
         rows[cur][k] = v
 print(f"{'kernel':60s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'spill':>5s} {'scratch':>7s} {'occ':>3s} {'LDS':>6s}")
 for k, r in rows.items():
-    print(f"{k[:60]:60s} {r.get('VGPRs','?'):>5s} {r.get('AGPRs','?'):>5s} {r.get('SGPRs','?'):>5s} "
+    print(f"{k[:60]:60s} {r.get('VGPRs','?'):>5s} {r.get('AGPRs','?'):>5s} {r.get('TotalSGPRs', r.get('SGPRs','?')):>5s} "
           f"{r.get('VGPRs Spill','?'):>5s} {r.get('ScratchSize','?'):>7s} {r.get('Occupancy','?'):>3s} {r.get('LDS Size','?'):>6s}")
