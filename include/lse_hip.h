@@ -1010,6 +1010,74 @@ int lse_pose_delta_tables(const lse_pose_delta_desc *desc, float *col_pose, floa
 int lse_pose_delta_tables_bwd(const lse_pose_delta_desc *desc, const float *d_col_pose, const float *d_prev_pose,
                               const float *d_next_pose, float *d_adj_col, float *d_adj_prev, float *d_adj_next, lse_stream_t stream);
 
+/* ---- TSDF fusion (csrc/tsdf.hip, csrc/mesh.hip; ABI 6, additive): depth renders -> a mesh of the observed surface ----------------
+ * All floats are f32, every operation is rounded on its own (no FMA), `/` and sqrtf are the correctly rounded ones, every
+ * comparison is false on NaN.  The lattice, its point order and its positions are those of the mesh-export section
+ * (lse_lattice_positions, bit for bit).
+ *
+ * State.  tw f32 [points, 2] = (tsdf, weight) and cw f32 [points, 4] = (r, g, b, colour weight), both zero before the first view;
+ *   tw 8-byte, cw 16-byte aligned.  Colours are fused iff cw and rgb are both non-null; otherwise cw is not touched.
+ * lse_tsdf_integrate.  cam: intrinsics of all views; poses f32 [n_views, 3, 4] (device; rows M[r][c] of a pose table, camera to
+ *   world, the camera looks along -z); depth, acc f32 [n_views, H * W] row-major; rgb f32 [n_views, H * W, 3] or NULL.  For every
+ *   lattice point x the views j = 0 .. n_views - 1 are folded in ascending order; "skip" leaves the point's state as it is:
+ *     v_k  = x_k - M[k][3]
+ *     xc   = (v_0 * M[0][0] + v_1 * M[1][0]) + v_2 * M[2][0],  yc and zc with columns 1 and 2         (R^T v)
+ *     z    = -zc;  skip unless z > 0
+ *     X    = xc / z,  Y = yc / z
+ *     if cam.distort, with (k1, k2, k3, k4, p1, p2) = cam.dist:
+ *       r  = X * X + Y * Y;  skip unless r <= r2_max
+ *       d  = 1 + r * (k1 + r * (k2 + r * (k3 + r * k4)))
+ *       xd = (d * X + ((2 * p1) * X) * Y) + p2 * (r + (2 * X) * X)
+ *       yd = (d * Y + ((2 * p2) * X) * Y) + p1 * (r + (2 * Y) * Y);  (X, Y) = (xd, yd)
+ *     u    = rintf(X * fx + cx),  v = rintf(cy - Y * fy)       (rays sit at integer pixel coordinates; ties to even)
+ *     skip unless u >= 0 && u < (float)W && v >= 0 && v < (float)H        (in float, before any conversion)
+ *     dp   = depth[j][(int)v * W + (int)u],  a = acc[j][same]
+ *     dist = sqrtf((v_0 * v_0 + v_1 * v_1) + v_2 * v_2)
+ *     if a >= min_acc:  skip unless dp > 0 && dp < +inf;  sdf = dp - dist          ("surface")
+ *     else if carve:    sdf = +inf                       (the ray sees through: observed empty; a NaN accumulation lands here)
+ *     else skip
+ *     skip if sdf < -truncation                                                    (occluded)
+ *     t    = fminf(1, sdf / truncation)
+ *     tsdf = (tsdf * weight + t) / (weight + 1);  weight = weight + 1
+ *     if colours are fused, "surface" and sdf <= truncation, with q = rgb[j][pixel]:
+ *       c_k = (c_k * cweight + q_k) / (cweight + 1) for k = 0, 1, 2;  cweight = cweight + 1
+ *   The state passes through f32 registers only, so one call with V views gives the bytes of V calls with one view each, in order.
+ *   r2_max: the largest X^2 + Y^2 of the undistorted camera points of the image's border pixels (+inf for a pinhole camera; unread
+ *   without cam.distort): beyond it the polynomial may fold far-off points back into the image.
+ *   One thread per lattice point; per launch the state costs one 8-byte and one 16-byte load and store per point (48 B), whatever
+ *   n_views.  LSE_E_INVALID before any launch: a bad lattice, n_views < 0, a truncation that is not positive and finite, a zero focal
+ *   length, H or W outside [1, 2^24] or 2^31 pixels or more, a null tw / cam / box (and, with n_views > 0, poses / depth / acc),
+ *   misaligned tw or cw.  n_views == 0: no-op.
+ * Field.  The surface-nets input of a fused volume is -tsdf where weight >= min_weight and NaN elsewhere ("unobserved"), at level 0:
+ *   inside = behind the observed surface.
+ * lse_surface_nets_count_ex / lse_surface_nets_emit_ex: the mesh-export pair with `flags`; flags == 0 is that pair, bit for bit (the
+ *   old entry points call the same bodies with 0), any other unknown bit is refused.  With LSE_NETS_SKIP_NAN
+ *     a cell is active iff its corners are neither all inside nor all outside AND none of the 8 is NaN;
+ *     a lattice edge gives its quad iff it does without the flag AND the four cells C0 .. C3 around it are all active (equivalently:
+ *     none of the 18 lattice points of those cells is NaN);
+ *   order, winding, vertex placement, workspace and capacities are unchanged.  Count and emit must be given the same flags.  No
+ *   surface is built against unobserved space: the mesh is open where observation ends.
+ * lse_tsdf_vertex_colors.  vertices, out f32 [n, 3]; count = min(n, *n_dev) (n_dev nullable); rows at or beyond count are not
+ *   written.  Per vertex and axis k
+ *     u_k = ((vertex_k - lo_k) / (hi_k - lo_k)) * (float)n_k,  fl = floorf(u_k)
+ *     c_k = fl >= (float)(n_k - 1) ? n_k - 1 : (fl > 0 ? (int)fl : 0)         (NaN -> 0: clamped into the first / last cell)
+ *     f_k = fminf(fmaxf(u_k - (float)c_k, 0), 1)                              (NaN -> 0)
+ *   and over the corners (dx, dy, dz) of cell c in ascending dx * 4 + dy * 2 + dz, starting from sums of 0:
+ *     wt = ((dx ? f_0 : 1 - f_0) * (dy ? f_1 : 1 - f_1)) * (dz ? f_2 : 1 - f_2)
+ *     if cw[corner].weight > 0:  s_k = s_k + wt * cw[corner].c_k;  W = W + wt
+ *   out_k = W > 0 ? s_k / W : 0. */
+#define LSE_NETS_SKIP_NAN 1
+int lse_tsdf_integrate(float *tw, float *cw, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi,
+                       const lse_camera_desc *cam, const float *poses, int32_t n_views, const float *depth, const float *acc,
+                       const float *rgb, float truncation, float min_acc, int32_t carve, float r2_max, lse_stream_t stream);
+int lse_surface_nets_count_ex(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, int32_t flags, void *workspace,
+                              int64_t workspace_bytes, int64_t *totals, lse_stream_t stream);
+int lse_surface_nets_emit_ex(const float *sigma, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi, float level,
+                             int32_t flags, const void *workspace, int64_t workspace_bytes, int64_t cap_vertices, int64_t cap_quads,
+                             float *vertices, int32_t *triangles, lse_stream_t stream);
+int lse_tsdf_vertex_colors(const float *cw, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi,
+                           const float *vertices, int64_t n, const int64_t *n_dev, float *out, lse_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ LSE_PREP_EVENT_STATS = 1
 LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
 LSE_MESH_SEGMENT = 1024
 LSE_PC_SEGMENT = 1024
+LSE_NETS_SKIP_NAN = 1
 LSE_EVENT_SEGMENT = 1024
 LSE_PANEL_IMG, LSE_PANEL_DEPTH, LSE_PANEL_ERR_MAP, LSE_PANEL_OVERLAY, LSE_PANEL_EV_OUT = 1, 2, 4, 8, 16
 
@@ -197,6 +198,8 @@ SIGNATURES = {
     "lse_surface_nets_workspace": [I32, I32, I32, POINTER(c_int64)],
     "lse_surface_nets_count": [P, I32, I32, I32, F32, P, I64, P, P],
     "lse_surface_nets_emit": [P, I32, I32, I32, P, P, F32, P, I64, I64, I64, P, P, P],
+    "lse_surface_nets_count_ex": [P, I32, I32, I32, F32, I32, P, I64, P, P],
+    "lse_surface_nets_emit_ex": [P, I32, I32, I32, P, P, F32, I32, P, I64, I64, I64, P, P, P],
     "lse_point_normals_world": [P, P, I32, P, I64, P, P, P],
     "lse_unproject_workspace": [I64, POINTER(c_int64)],
     "lse_unproject_append": [P, P, P, P, P, P, I64, P, P, F32, P, I64, I64, P, P, P, P, P],
@@ -217,6 +220,8 @@ SIGNATURES = {
     "lse_compose_batch": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, I64, I32, P, P, P],
     "lse_compose_rays_bwd": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, P, P, P, P, P],
     "lse_camera_rays": [POINTER(CameraDesc), P, I64, I64, P, P, P, P, P],
+    "lse_tsdf_integrate": [P, P, I32, I32, I32, P, P, POINTER(CameraDesc), P, I32, P, P, P, F32, F32, I32, F32, P],
+    "lse_tsdf_vertex_colors": [P, I32, I32, I32, P, P, P, I64, P, P, P],
     "lse_spline_poses": [POINTER(SplineDesc), P, P, P, P],
     "lse_spline_poses_bwd": [POINTER(SplineDesc), P, P, P, P, P, P],
     "lse_pose_delta_tables": [POINTER(PoseDeltaDesc), P, P, P, P],

@@ -10,32 +10,21 @@
 //   emit_quads       the walk of count_quads again, with the ranks: two triangles per quad, in ascending (point, axis).
 // All passes are bandwidth-bound flat maps over sigma with iz fastest (a wave's corner reads are coalesced rows); nothing is staged
 // in LDS.
+// LSE_NETS_SKIP_NAN (the _ex entry points; include/lse_hip.h, "TSDF fusion"): NaN marks unobserved points.  count_cells keeps no cell
+// with a NaN corner, and both quad walks keep an edge only if the four cells around it have a rank >= 0 -- the cell pass runs first
+// on the same stream.  With flags == 0 the kernels take the paths they always took.
 #include "compact.h"
 
 namespace {
 
 #include "positions.h"      // Box, positions_bwd_sample: the world-space Jacobian of the normals
+#include "lattice.h"        // Lattice, cell_coords, point_coords, make_lattice, make_box
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kSeg = LSE_MESH_SEGMENT;        // consecutive cells / lattice points owned by one wave
 constexpr int kIters = kSeg / 64;
 static_assert(kThreads == lse::kScanThreads, "scan_kernel is one block of kScanThreads");
-
-struct Lattice {
-    int n[3];               // cells per axis
-    int64_t sx, sy;         // point strides of ix and iy (iz is fastest)
-    int64_t cells, points;
-};
-
-// cell index -> (cx, cy, cz), cz fastest
-__device__ __forceinline__ void cell_coords(const Lattice &L, int64_t c, int cc[3])
-{
-    const uint32_t u = (uint32_t)c;
-    cc[2] = (int)(u % (uint32_t)L.n[2]);
-    cc[1] = (int)((u / (uint32_t)L.n[2]) % (uint32_t)L.n[1]);
-    cc[0] = (int)(u / ((uint32_t)L.n[2] * (uint32_t)L.n[1]));
-}
 
 // 8 corner values of cell (cx, cy, cz), index dx * 4 + dy * 2 + dz; all 8 points are inside the lattice for every valid cell
 __device__ __forceinline__ void load_corners(const float *__restrict__ sigma, const Lattice &L, int cx, int cy, int cz, float s[8])
@@ -45,17 +34,22 @@ __device__ __forceinline__ void load_corners(const float *__restrict__ sigma, co
     for (int k = 0; k < 8; ++k) s[k] = sigma[p + (k >> 2) * L.sx + ((k >> 1) & 1) * L.sy + (k & 1)];
 }
 
-__device__ __forceinline__ bool cell_active(const float s[8], float level)
+// skip_nan (LSE_NETS_SKIP_NAN): a cell with a NaN corner is never active
+__device__ __forceinline__ bool cell_active(const float s[8], float level, bool skip_nan)
 {
-    int in = 0;
+    int in = 0, nan = 0;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) in += s[k] > level ? 1 : 0;      // NaN is outside
-    return in != 0 && in != 8;
+    for (int k = 0; k < 8; ++k) {
+        in += s[k] > level ? 1 : 0;      // NaN is outside
+        nan += s[k] != s[k] ? 1 : 0;
+    }
+    return in != 0 && in != 8 && !(skip_nan && nan != 0);
 }
 
 // ---- count ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void count_cells_kernel(const float *__restrict__ sigma, Lattice L, float level, int n_segs,
-                                                               int32_t *__restrict__ cell_rank, int64_t *__restrict__ seg_counts)
+                                                               bool skip_nan, int32_t *__restrict__ cell_rank,
+                                                               int64_t *__restrict__ seg_counts)
 {
     const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (seg >= n_segs) return;                          // (wave-uniform)
@@ -64,13 +58,23 @@ __global__ __launch_bounds__(kThreads) void count_cells_kernel(const float *__re
         float s[8];
         cell_coords(L, c, cc);
         load_corners(sigma, L, cc[0], cc[1], cc[2], s);
-        return cell_active(s, level);
+        return cell_active(s, level, skip_nan);
     });
 }
 
+// index of the cell C_k around the edge (i, a): C0 = i - e_b - e_c, C1 = i - e_c, C2 = i, C3 = i - e_b
+__device__ __forceinline__ int64_t edge_cell(const Lattice &L, const int i[3], int b, int c, int k)
+{
+    int cc[3] = {i[0], i[1], i[2]};
+    cc[b] -= (k == 0 || k == 3) ? 1 : 0;
+    cc[c] -= (k == 0 || k == 1) ? 1 : 0;
+    return ((int64_t)cc[0] * L.n[1] + cc[1]) * L.n[2] + cc[2];
+}
+
 // bit a: the lattice edge (p, a) gives a quad -- q = p + e_a exists, the edge is interior in the other two axes, inside(p) != inside(q)
+// and, with active_rank (LSE_NETS_SKIP_NAN: the ranks count_cells_kernel wrote), all four cells around the edge are active
 __device__ __forceinline__ int quad_bits(const float *__restrict__ sigma, const Lattice &L, int64_t p, const int i[3], float level,
-                                         bool &in_p)
+                                         const int32_t *__restrict__ active_rank, bool &in_p)
 {
     in_p = sigma[p] > level;
     const int64_t stride[3] = {L.sx, L.sy, 1};
@@ -83,21 +87,19 @@ __device__ __forceinline__ int quad_bits(const float *__restrict__ sigma, const 
         const int b = (a + 1) % 3, c = (a + 2) % 3;
         if (i[a] < L.n[a] && mid[b] && mid[c]) {
             const bool in_q = sigma[p + stride[a]] > level;
-            bits |= (in_q != in_p) ? (1 << a) : 0;
+            bool quad = in_q != in_p;
+            if (quad && active_rank) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) quad = quad && active_rank[edge_cell(L, i, b, c, k)] >= 0;
+            }
+            bits |= quad ? (1 << a) : 0;
         }
     }
     return bits;
 }
 
-__device__ __forceinline__ void point_coords(const Lattice &L, int64_t p, int i[3])
-{
-    const uint32_t u = (uint32_t)p, mz = (uint32_t)L.n[2] + 1u, my = (uint32_t)L.n[1] + 1u;
-    i[2] = (int)(u % mz);
-    i[1] = (int)((u / mz) % my);
-    i[0] = (int)(u / (mz * my));
-}
-
 __global__ __launch_bounds__(kThreads) void count_quads_kernel(const float *__restrict__ sigma, Lattice L, float level, int n_segs,
+                                                               const int32_t *__restrict__ active_rank,
                                                                int64_t *__restrict__ seg_counts)
 {
     const int seg = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = lse::lane_id();
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void count_quads_kernel(const float *__re
             int i[3];
             bool in_p;
             point_coords(L, p, i);
-            bits = quad_bits(sigma, L, p, i, level, in_p);
+            bits = quad_bits(sigma, L, p, i, level, active_rank, in_p);
         }
         int t0, t1, t2;
         lse::wave_prefix_count(bits & 1, t0);
@@ -180,6 +182,7 @@ __global__ __launch_bounds__(kThreads) void emit_vertices_kernel(const float *__
 }
 
 __global__ __launch_bounds__(kThreads) void emit_quads_kernel(const float *__restrict__ sigma, Lattice L, float level, int n_segs,
+                                                              const int32_t *__restrict__ active_rank,
                                                               const int32_t *__restrict__ cell_rank,
                                                               const int64_t *__restrict__ seg_off_v,
                                                               const int64_t *__restrict__ seg_off_q, int64_t cap,
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void emit_quads_kernel(const float *__res
         bool in_p = false;
         if (p < L.points) {
             point_coords(L, p, i);
-            bits = quad_bits(sigma, L, p, i, level, in_p);
+            bits = quad_bits(sigma, L, p, i, level, active_rank, in_p);
         }
         int t0, t1, t2;
         const int b0 = lse::wave_prefix_count(bits & 1, t0), b1 = lse::wave_prefix_count(bits & 2, t1);
@@ -210,13 +213,7 @@ __global__ __launch_bounds__(kThreads) void emit_quads_kernel(const float *__res
             // the four cells around the edge: i_a <= n_a - 1 and 1 <= i_b, i_c <= n_b - 1, n_c - 1, so all four are cells of the lattice
             int32_t w[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int cc[3] = {i[0], i[1], i[2]};
-                cc[b] -= (k == 0 || k == 3) ? 1 : 0;        // C0 = p - e_b - e_c, C1 = p - e_c, C2 = p, C3 = p - e_b
-                cc[c] -= (k == 0 || k == 1) ? 1 : 0;
-                const int64_t ci = ((int64_t)cc[0] * L.n[1] + cc[1]) * L.n[2] + cc[2];
-                w[k] = (int32_t)lse::segment_row<kSeg>(ci, cell_rank, seg_off_v);
-            }
+            for (int k = 0; k < 4; ++k) w[k] = (int32_t)lse::segment_row<kSeg>(edge_cell(L, i, b, c, k), cell_rank, seg_off_v);
             if (!in_p) {
                 const int32_t t0 = w[0], t1 = w[1];
                 w[0] = w[3], w[1] = w[2], w[2] = t1, w[3] = t0;
@@ -257,23 +254,6 @@ __global__ __launch_bounds__(kThreads) void point_normals_kernel(const float *__
     for (int k = 0; k < 3; ++k) out[j * 3 + k] = gw[k] * inv;
 }
 
-// false when the resolution is not a lattice the kernels index: every n_k >= 1 and fewer than 2^31 points
-bool make_lattice(int32_t nx, int32_t ny, int32_t nz, Lattice &L)
-{
-    if (nx < 1 || ny < 1 || nz < 1) return false;
-    const int64_t lim = 1ll << 31;
-    const int64_t yz = ((int64_t)ny + 1) * ((int64_t)nz + 1);
-    if (yz >= lim) return false;
-    const int64_t points = ((int64_t)nx + 1) * yz;      // < 2^31 * 2^31: no overflow
-    if (points >= lim) return false;
-    L.n[0] = nx, L.n[1] = ny, L.n[2] = nz;
-    L.sy = (int64_t)nz + 1;
-    L.sx = yz;
-    L.points = points;
-    L.cells = (int64_t)nx * ny * nz;
-    return true;
-}
-
 struct Workspace {
     int64_t *seg_v, *seg_q;
     int32_t *cell_rank;
@@ -291,13 +271,6 @@ Workspace carve(const Lattice &L, void *base)
     w.cell_rank = reinterpret_cast<int32_t *>(w.seg_q + w.n_q);
     w.bytes = 8 * ((int64_t)w.n_v + w.n_q) + 4 * L.cells;
     return w;
-}
-
-Box make_box(const float *h_lo, const float *h_hi)
-{
-    Box box;
-    for (int k = 0; k < 3; ++k) { box.lo[k] = h_lo[k]; box.hi[k] = h_hi[k]; }
-    return box;
 }
 
 }  // namespace
@@ -330,35 +303,40 @@ extern "C" int lse_surface_nets_workspace(int32_t nx, int32_t ny, int32_t nz, in
     return LSE_OK;
 }
 
-extern "C" int lse_surface_nets_count(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
-                                      int64_t workspace_bytes, int64_t *totals, lse_stream_t stream)
+// the body of lse_surface_nets_count and lse_surface_nets_count_ex
+static int nets_count(const char *what, const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, int32_t flags,
+                      void *workspace, int64_t workspace_bytes, int64_t *totals, lse_stream_t stream)
 {
-    const char *what = "lse_surface_nets_count";
     Lattice L;
     LSE_REQUIRE(make_lattice(nx, ny, nz, L), "%s: resolution %d x %d x %d: every count >= 1 and fewer than 2^31 points", what, nx, ny,
                 nz);
+    LSE_REQUIRE((flags & ~LSE_NETS_SKIP_NAN) == 0, "%s: unknown flags 0x%x", what, (unsigned)flags);
     LSE_REQUIRE(sigma && workspace && totals, "%s: null pointer", what);
     LSE_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)totals & 7) == 0, "%s: workspace and totals must be 8-byte aligned",
                 what);
     const Workspace w = carve(L, workspace);
     LSE_REQUIRE(workspace_bytes >= w.bytes, "%s: workspace of %lld bytes < %lld (lse_surface_nets_workspace)", what,
                 (long long)workspace_bytes, (long long)w.bytes);
+    const bool skip_nan = (flags & LSE_NETS_SKIP_NAN) != 0;
     hipStream_t st = lse::as_stream(stream);
-    hipLaunchKernelGGL(count_cells_kernel, dim3(lse::blocks_for(w.n_v, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_v, w.cell_rank,
-                       w.seg_v);
-    hipLaunchKernelGGL(count_quads_kernel, dim3(lse::blocks_for(w.n_q, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_q, w.seg_q);
+    hipLaunchKernelGGL(count_cells_kernel, dim3(lse::blocks_for(w.n_v, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_v, skip_nan,
+                       w.cell_rank, w.seg_v);
+    // (stream order: the quad pass of the masked mode reads the ranks the cell pass wrote)
+    hipLaunchKernelGGL(count_quads_kernel, dim3(lse::blocks_for(w.n_q, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_q,
+                       skip_nan ? (const int32_t *)w.cell_rank : nullptr, w.seg_q);
     hipLaunchKernelGGL(scan_kernel, dim3(2), dim3(kThreads), 0, st, w.seg_v, w.n_v, w.seg_q, w.n_q, totals);
     return lse::check_launch(what);
 }
 
-extern "C" int lse_surface_nets_emit(const float *sigma, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi,
-                                     float level, const void *workspace, int64_t workspace_bytes, int64_t cap_vertices,
-                                     int64_t cap_quads, float *vertices, int32_t *triangles, lse_stream_t stream)
+// the body of lse_surface_nets_emit and lse_surface_nets_emit_ex
+static int nets_emit(const char *what, const float *sigma, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi,
+                     float level, int32_t flags, const void *workspace, int64_t workspace_bytes, int64_t cap_vertices,
+                     int64_t cap_quads, float *vertices, int32_t *triangles, lse_stream_t stream)
 {
-    const char *what = "lse_surface_nets_emit";
     Lattice L;
     LSE_REQUIRE(make_lattice(nx, ny, nz, L), "%s: resolution %d x %d x %d: every count >= 1 and fewer than 2^31 points", what, nx, ny,
                 nz);
+    LSE_REQUIRE((flags & ~LSE_NETS_SKIP_NAN) == 0, "%s: unknown flags 0x%x", what, (unsigned)flags);
     LSE_REQUIRE(sigma && workspace && h_lo && h_hi, "%s: null pointer", what);
     LSE_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
     const Workspace w = carve(L, const_cast<void *>(workspace));
@@ -366,14 +344,45 @@ extern "C" int lse_surface_nets_emit(const float *sigma, int32_t nx, int32_t ny,
                 (long long)workspace_bytes, (long long)w.bytes);
     LSE_REQUIRE(cap_vertices >= 0 && cap_quads >= 0, "%s: negative capacity", what);
     LSE_REQUIRE((cap_vertices == 0 || vertices) && (cap_quads == 0 || triangles), "%s: null output for a capacity > 0", what);
+    const bool skip_nan = (flags & LSE_NETS_SKIP_NAN) != 0;
     hipStream_t st = lse::as_stream(stream);
     if (cap_vertices > 0)
         hipLaunchKernelGGL(emit_vertices_kernel, dim3(lse::blocks_for(L.cells, kThreads)), dim3(kThreads), 0, st, sigma, L,
                            make_box(h_lo, h_hi), level, (const int32_t *)w.cell_rank, (const int64_t *)w.seg_v, cap_vertices, vertices);
     if (cap_quads > 0)
         hipLaunchKernelGGL(emit_quads_kernel, dim3(lse::blocks_for(w.n_q, kWaves)), dim3(kThreads), 0, st, sigma, L, level, w.n_q,
-                           (const int32_t *)w.cell_rank, (const int64_t *)w.seg_v, (const int64_t *)w.seg_q, cap_quads, triangles);
+                           skip_nan ? (const int32_t *)w.cell_rank : nullptr, (const int32_t *)w.cell_rank, (const int64_t *)w.seg_v,
+                           (const int64_t *)w.seg_q, cap_quads, triangles);
     return lse::check_launch(what);
+}
+
+extern "C" int lse_surface_nets_count(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
+                                      int64_t workspace_bytes, int64_t *totals, lse_stream_t stream)
+{
+    return nets_count("lse_surface_nets_count", sigma, nx, ny, nz, level, 0, workspace, workspace_bytes, totals, stream);
+}
+
+extern "C" int lse_surface_nets_count_ex(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, int32_t flags,
+                                         void *workspace, int64_t workspace_bytes, int64_t *totals, lse_stream_t stream)
+{
+    return nets_count("lse_surface_nets_count_ex", sigma, nx, ny, nz, level, flags, workspace, workspace_bytes, totals, stream);
+}
+
+extern "C" int lse_surface_nets_emit(const float *sigma, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi,
+                                     float level, const void *workspace, int64_t workspace_bytes, int64_t cap_vertices,
+                                     int64_t cap_quads, float *vertices, int32_t *triangles, lse_stream_t stream)
+{
+    return nets_emit("lse_surface_nets_emit", sigma, nx, ny, nz, h_lo, h_hi, level, 0, workspace, workspace_bytes, cap_vertices,
+                     cap_quads, vertices, triangles, stream);
+}
+
+extern "C" int lse_surface_nets_emit_ex(const float *sigma, int32_t nx, int32_t ny, int32_t nz, const float *h_lo, const float *h_hi,
+                                        float level, int32_t flags, const void *workspace, int64_t workspace_bytes,
+                                        int64_t cap_vertices, int64_t cap_quads, float *vertices, int32_t *triangles,
+                                        lse_stream_t stream)
+{
+    return nets_emit("lse_surface_nets_emit_ex", sigma, nx, ny, nz, h_lo, h_hi, level, flags, workspace, workspace_bytes,
+                     cap_vertices, cap_quads, vertices, triangles, stream);
 }
 
 extern "C" int lse_point_normals_world(const float *d_x01, const float *positions, int32_t contraction, const float *h_aabb, int64_t n,

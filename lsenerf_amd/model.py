@@ -639,6 +639,14 @@ class LSENeRFModel(nn.Module):
         from . import mesh as _mesh
         return _mesh.extract_mesh(self, **kwargs)
 
+    def export_tsdf_mesh(self, views, **kwargs):
+        """Triangle mesh of the surface ``views`` (an ``eval_set.EvalSet`` or ``(EdCameras, poses)``) see of the field: eval depth
+        renders fused into a truncated signed distance volume, meshed without a surface against unobserved space
+        (``lsenerf_amd.tsdf.export_tsdf_mesh``: image_indices, resolution, bounds, truncation, min_accumulation, carve, min_weight,
+        colors, normals, views_per_launch).  Runs without gradients in eval mode and restores the model's mode and eval settings."""
+        from . import tsdf as _tsdf
+        return _tsdf.export_tsdf_mesh(self, views, **kwargs)
+
     def export_point_cloud(self, views, **kwargs):
         """Point cloud of what ``views`` (an ``eval_set.EvalSet`` or ray bundles) see of the field: unprojected eval renders, merged
         per voxel and filtered by neighbour support on request (``lsenerf_amd.pointcloud.export_point_cloud``: image_indices,

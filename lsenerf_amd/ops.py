@@ -47,7 +47,8 @@ def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-_N_DEV_AT = {"lse_positions_fwd": 6, "lse_positions_bwd": 6, "lse_hash_bwd_ex": 10, "lse_point_normals_world": 5}    # elsewhere: right before the stream
+_N_DEV_AT = {"lse_positions_fwd": 6, "lse_positions_bwd": 6, "lse_hash_bwd_ex": 10, "lse_point_normals_world": 5,
+             "lse_tsdf_vertex_colors": 8}    # elsewhere: right before the stream
 
 
 def _call_n(name: str, n_dev: Optional[torch.Tensor], *args):
@@ -2180,51 +2181,57 @@ def surface_nets_workspace_bytes(res) -> int:
 
 
 @torch.no_grad()
-def surface_nets_count(sigma: torch.Tensor, res, level: float, workspace: torch.Tensor, totals: torch.Tensor) -> None:
+def surface_nets_count(sigma: torch.Tensor, res, level: float, workspace: torch.Tensor, totals: torch.Tensor,
+                       skip_nan: bool = False) -> None:
     """First pass of ``surface_nets``: fills ``workspace`` (uint8, ``surface_nets_workspace_bytes(res)``) and ``totals`` (int64 [2] on
-    the device: vertices, quads).  No host read."""
+    the device: vertices, quads).  No host read.  ``skip_nan``: lse_surface_nets_count_ex with LSE_NETS_SKIP_NAN."""
     if sigma.numel() != lattice_points(res):
         raise ValueError(f"surface_nets: sigma has {sigma.numel()} values, the lattice {lattice_points(res)} points")
-    _lib.call("lse_surface_nets_count", _f32(sigma, "sigma"), *_res3(res), float(level), _chk(workspace, torch.uint8, "workspace"),
+    name, flags = ("lse_surface_nets_count_ex", (_lib.LSE_NETS_SKIP_NAN,)) if skip_nan else ("lse_surface_nets_count", ())
+    _lib.call(name, _f32(sigma, "sigma"), *_res3(res), float(level), *flags, _chk(workspace, torch.uint8, "workspace"),
               workspace.numel(), _chk(totals, torch.int64, "totals"), _stream())
 
 
 @torch.no_grad()
 def surface_nets_emit(sigma: torch.Tensor, res, lo, hi, level: float, workspace: torch.Tensor, vertices: torch.Tensor,
-                      triangles: torch.Tensor) -> None:
-    """Second pass of ``surface_nets`` with the workspace ``surface_nets_count`` filled for the same ``sigma``, ``res`` and ``level``:
-    writes ``vertices`` (float32 [cap_vertices, 3]) and ``triangles`` (int32 [2 * cap_quads, 3]); rows beyond a buffer are dropped."""
+                      triangles: torch.Tensor, skip_nan: bool = False) -> None:
+    """Second pass of ``surface_nets`` with the workspace ``surface_nets_count`` filled for the same ``sigma``, ``res``, ``level`` and
+    ``skip_nan``: writes ``vertices`` (float32 [cap_vertices, 3]) and ``triangles`` (int32 [2 * cap_quads, 3]); rows beyond a buffer
+    are dropped."""
     if sigma.numel() != lattice_points(res):
         raise ValueError(f"surface_nets: sigma has {sigma.numel()} values, the lattice {lattice_points(res)} points")
     if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.shape[0] % 2:
         raise ValueError("surface_nets: vertices [cap_vertices, 3] and triangles [2 * cap_quads, 3] expected")
     c_lo, c_hi = _box3(lo, hi)
     cap_v, cap_q = vertices.shape[0], triangles.shape[0] // 2
-    _lib.call("lse_surface_nets_emit", _f32(sigma, "sigma"), *_res3(res), c_lo, c_hi, float(level),
+    name, flags = ("lse_surface_nets_emit_ex", (_lib.LSE_NETS_SKIP_NAN,)) if skip_nan else ("lse_surface_nets_emit", ())
+    _lib.call(name, _f32(sigma, "sigma"), *_res3(res), c_lo, c_hi, float(level), *flags,
               _chk(workspace, torch.uint8, "workspace"), workspace.numel(), cap_v, cap_q,
               _f32(vertices, "vertices") if cap_v else None, _chk(triangles, torch.int32, "triangles") if cap_q else None, _stream())
 
 
 @torch.no_grad()
-def surface_nets(sigma: torch.Tensor, res, lo, hi, level: float, caps: Optional[Tuple[int, int]] = None):
+def surface_nets(sigma: torch.Tensor, res, lo, hi, level: float, caps: Optional[Tuple[int, int]] = None, skip_nan: bool = False):
     """Naive surface nets of the density lattice ``sigma`` (float32, one value per point of the ``res``-cell lattice over the box
     ``lo .. hi``, iz fastest) at the iso value ``level``: ``(vertices [V, 3] float32, triangles [2 Q, 3] int32, totals int64 [2])``.
     The definition -- one vertex per active cell, one quad per sign-changing interior lattice edge, ordered, deterministic -- is in
     include/lse_hip.h ("mesh export").  Without ``caps`` the buffers are sized from ONE host read of ``totals`` between the two
     passes; with ``caps = (cap_vertices, cap_quads)`` nothing is read, the buffers have the capacities' extent, rows beyond the true
-    counts are left unwritten and ``totals`` (on the device) says how many there are."""
+    counts are left unwritten and ``totals`` (on the device) says how many there are.  ``skip_nan`` (LSE_NETS_SKIP_NAN; include/lse_hip.h,
+    "TSDF fusion"): NaN marks unobserved points -- a cell with a NaN corner gives no vertex and a quad next to such a cell is
+    dropped, so no surface is built against unobserved space."""
     sigma = _c(sigma.detach()).reshape(-1)
     dev = sigma.device
     ws = torch.empty(surface_nets_workspace_bytes(res), dtype=torch.uint8, device=dev)
     totals = torch.empty(2, dtype=torch.int64, device=dev)
-    surface_nets_count(sigma, res, level, ws, totals)
+    surface_nets_count(sigma, res, level, ws, totals, skip_nan)
     if caps is None:
         n_v, n_q = (int(v) for v in totals.tolist())
     else:
         n_v, n_q = int(caps[0]), int(caps[1])
     vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
     triangles = torch.empty((2 * n_q, 3), dtype=torch.int32, device=dev)
-    surface_nets_emit(sigma, res, lo, hi, level, ws, vertices, triangles)
+    surface_nets_emit(sigma, res, lo, hi, level, ws, vertices, triangles, skip_nan)
     return vertices, triangles, totals
 
 
@@ -2247,6 +2254,70 @@ def point_normals_world(d_x01: torch.Tensor, positions: torch.Tensor, contractio
     if n > 0:
         _call_n("lse_point_normals_world", n_dev, _f32(d_x01, "d_x01"), _f32(positions, "positions"), 1 if contraction else 0, aabb_arr,
                 n, _f32(out, "out"), _stream())
+    return out
+
+
+# ---- TSDF fusion (csrc/tsdf.hip; driven by lsenerf_amd.tsdf.export_tsdf_mesh) ----
+def _tsdf_ptrs(*specs):
+    """Pointers of contiguous float32 device tensors, one per spec ``(tensor, shape, name, allow_none)``.  Every violation is a
+    ValueError; dtype, shape and contiguity of ALL tensors are checked before the device of any."""
+    for t, shape, name, allow_none in specs:
+        if t is None:
+            if allow_none:
+                continue
+            raise ValueError(f"{name} is None")
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{name}: a float32 tensor expected, got {getattr(t, 'dtype', type(t))}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: {list(shape)} expected, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    for t, _, name, _ in specs:
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
+    return [ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None for t, _, _, _ in specs]
+
+
+@torch.no_grad()
+def tsdf_integrate(tw: torch.Tensor, cw: Optional[torch.Tensor], res, lo, hi, cam_desc, poses: torch.Tensor, depth: torch.Tensor,
+                   acc: torch.Tensor, rgb: Optional[torch.Tensor] = None, truncation: float = 0.0, min_acc: float = 0.5,
+                   carve: bool = True, r2_max: float = float("inf")) -> None:
+    """Folds the views ``poses`` [V, 3, 4] (rows of a device pose table) of the camera ``cam_desc`` (``camera_desc``) into the TSDF
+    state ``tw`` [points, 2] = (tsdf, weight) and, with ``cw`` [points, 4] = (r, g, b, weight) and ``rgb`` [V, H * W, 3], the fused
+    colours, in place and in view order (lse_tsdf_integrate; the update is in include/lse_hip.h, "TSDF fusion").  ``depth``, ``acc``:
+    [V, H * W].  One launch for the batch: the state is read and written once however many views it holds.  No host read."""
+    import math
+    n = lattice_points(res)
+    hw = int(cam_desc.H) * int(cam_desc.W)
+    truncation = float(truncation)
+    if not (truncation > 0.0 and math.isfinite(truncation)):
+        raise ValueError(f"truncation must be positive and finite, got {truncation}")
+    if not torch.is_tensor(poses) or poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4):
+        raise ValueError(f"poses: [V, 3, 4] expected, got {list(getattr(poses, 'shape', ()))}")
+    V = poses.shape[0]
+    p_tw, p_cw, p_poses, p_depth, p_acc, p_rgb = _tsdf_ptrs(
+        (tw, (n, 2), "tw", False), (cw, (n, 4), "cw", True), (poses, (V, 3, 4), "poses", False), (depth, (V, hw), "depth", False),
+        (acc, (V, hw), "acc", False), (rgb, (V, hw, 3), "rgb", True))
+    c_lo, c_hi = _box3(lo, hi)
+    _lib.call("lse_tsdf_integrate", p_tw, p_cw, *_res3(res), c_lo, c_hi, ctypes.byref(cam_desc), p_poses, V, p_depth, p_acc, p_rgb,
+              truncation, float(min_acc), 1 if carve else 0, float(r2_max), _stream())
+
+
+@torch.no_grad()
+def tsdf_vertex_colors(cw: torch.Tensor, res, lo, hi, vertices: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       n_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fused colours [n, 3] at ``vertices`` [n, 3]: the trilinear blend of the colours ``cw`` [points, 4] holds at the 8 corners of
+    each vertex's cell, over the corners with a colour weight > 0 (black where none has) -- lse_tsdf_vertex_colors.  ``n_dev``
+    (int64 [1] on the device): only the first ``n_dev[0]`` rows are written."""
+    if not torch.is_tensor(vertices) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices: [n, 3] expected, got {list(getattr(vertices, 'shape', ()))}")
+    n = vertices.shape[0]
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=vertices.device)
+    c_ptr, v_ptr, o_ptr = _tsdf_ptrs((cw, (lattice_points(res), 4), "cw", False), (vertices, (n, 3), "vertices", False),
+                                     (out, (n, 3), "out", False))
+    c_lo, c_hi = _box3(lo, hi)
+    _call_n("lse_tsdf_vertex_colors", n_dev, c_ptr, *_res3(res), c_lo, c_hi, v_ptr, n, o_ptr, _stream())
     return out
 
 
