@@ -464,6 +464,41 @@ int lse_eval_composite_segment(const float *t_starts, const float *t_ends, const
 int lse_eval_composite_finish(const void *state, int32_t n_rays, int32_t flags, float background, float *workspace, float *out_rgb,
                               float *out_acc, float *out_depth, int64_t *out_nsamples, lse_stream_t stream);
 
+/* Quantile depths of an evaluation render (csrc/volrend.hip; ABI 6, additive): the depth at which a ray's accumulated weight
+ * crosses q -- q = 0.5 is the median depth -- for up to four q at once.  One 64-lane wave per ray, the walk and the scan of
+ * lse_eval_composite.  Per ray with samples [a_k, b_k), sigma_k, mid_k = (a_k + b_k) * 0.5f:
+ *   tau_front(k), tau_behind(k): the optical depth in front of / behind sample k, as lse_eval_composite's scan forms them in f32
+ *      (exclusive / inclusive prefix of sigma * dt inside the 64-sample group + the carry in front of the group; tau_behind of a
+ *      group's last sample is the next group's carry, bit for bit).  The weights through sample k sum to 1 - exp(-tau_behind(k)),
+ *      so  sum_{i<=k} w_i >= q   is   tau_behind(k) >= tau_q = -ln(1 - q):  nothing is summed, nothing cancels.
+ *   k_j = the first k with tau_behind(k) >= tau_q[j]  (a NaN never compares true, +inf does).
+ *   k_j exists:  depth_q[r][j] = mid_{k_j}; with LSE_DEPTH_INTERPOLATE  clamp(a + (tau_q[j] - tau_front(k_j)) / sigma, a, b) of that
+ *      sample -- the exact crossing under piecewise-constant density; sigma = +inf gives a, a NaN quotient gives mid.  Bit j of
+ *      reached[r] is set.
+ *   no such k:   depth_q[r][j] = the mid-point of the ray's last sample (nerfstudio's clamp of searchsorted to n - 1); bit j clear.
+ *   a ray without samples: depth_q[r][*] = 0.0f, reached[r] = 0.
+ *   depth_sel[r] (nullable), sel = (flags >> 8) & 3 < n_q:  depth_q[r][sel] if bit sel of reached[r] is set and -- when max_spread is
+ *      finite -- bit n_q - 1 is set too and depth_q[r][n_q - 1] - depth_q[r][0] <= max_spread;  NaN otherwise, which is what
+ *      lse_unproject_append (the point is dropped) and lse_tsdf_integrate (the pixel is skipped without carving) take as "no usable
+ *      depth".  max_spread >= 0; +inf: no spread test.
+ * t_starts / t_ends / sigmas: packed f32, packed_info [n_rays,2] = (start, count) int64; h_tau_q: HOST array of n_q (1..4) strictly
+ * ascending positive values; depth_q f32 [n_rays, n_q], reached u8 [n_rays], depth_sel f32 [n_rays]: may be row offsets into image
+ * buffers.  No atomics, no LDS, no workspace.
+ *   lse_eval_depth_quantiles_segment: the same walk over ONE segment of the early-stop route (seg_packed as for
+ *      lse_eval_composite_segment).  state: [n_rays][2] 4-byte words owned by the caller -- the carry (f32) and the found mask (int32);
+ *      all zero is the start, and it is independent of lse_eval_composite_segment's state.  A ray whose segment count is 0 is left
+ *      alone, so depth_q / reached (/ depth_sel) must persist between the segments and start as what a ray without samples gets
+ *      (0.0f / 0 (/ NaN)); a quantile found in an earlier segment is read back from depth_q, not written again.  After every
+ *      segment depth_q holds the crossing where found and the mid-point of the last sample walked where not: once the last segment
+ *      has run, the outputs are those of lse_eval_depth_quantiles over the samples walked, bit for bit. */
+#define LSE_DEPTH_INTERPOLATE 1
+int lse_eval_depth_quantiles(const float *t_starts, const float *t_ends, const float *sigmas, const int64_t *packed_info,
+                             int32_t n_rays, int32_t n_q, const float *h_tau_q, int32_t flags, float max_spread, float *depth_q,
+                             uint8_t *reached, float *depth_sel, lse_stream_t stream);
+int lse_eval_depth_quantiles_segment(const float *t_starts, const float *t_ends, const float *sigmas, const int64_t *seg_packed,
+                                     int32_t n_rays, int32_t n_q, const float *h_tau_q, int32_t flags, float max_spread, void *state,
+                                     float *depth_q, uint8_t *reached, float *depth_sel, lse_stream_t stream);
+
 /* ---- image metrics: SSIM and MSE of preds / target, contiguous f32 [B,C,H,W] with H, W >= 11 (else LSE_E_INVALID) -----------
  *      torchmetrics structural_similarity_index_measure(preds, target) with its defaults (R:lse_nerf/lsenerf.py:206, :512), restated
  *      from the published algorithm (parity unpinned): data_range R = max(max p - min p, max t - min t) on the device,

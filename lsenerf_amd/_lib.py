@@ -25,6 +25,7 @@ LSE_MLP_ARITH_BF16X3, LSE_MLP_ARITH_BF16X1 = 2, 3      # reduced-piece inference
 LSE_TRAVERSE_FMA_SETUP = 1
 LSE_EVAL_NAN_TO_NUM, LSE_EVAL_BACKGROUND, LSE_EVAL_CLAMP = 1, 2, 4
 LSE_NORMALS_WORLD, LSE_NORMALS_RENORMALIZE = 1, 2
+LSE_DEPTH_INTERPOLATE = 1
 LSE_PREP_EVENT_STATS = 1
 LSE_OCC_LIST_TILE, LSE_OCC_MEAN_BLOCKS = 4096, 1024
 LSE_MESH_SEGMENT = 1024
@@ -171,6 +172,8 @@ SIGNATURES = {
     "lse_eval_segment_begin": [P, I32, I64, P, P, P],
     "lse_eval_composite_segment": [P, P, P, P, I32, P, P, I32, I32, I64, I64, F32, P, P, P],
     "lse_eval_composite_finish": [P, I32, I32, F32, P, P, P, P, P, P],
+    "lse_eval_depth_quantiles": [P, P, P, P, I32, I32, P, I32, F32, P, P, P, P],
+    "lse_eval_depth_quantiles_segment": [P, P, P, P, I32, I32, P, I32, F32, P, P, P, P, P],
     "lse_image_metrics_workspace": [I32, I32, I32, I32, POINTER(c_int64)],
     "lse_image_metrics": [P, P, I32, I32, I32, I32, P, P, I64, P, P, P],
     "lse_eval_image_prep": [P, I32, P, I32, P, I32, I32, I32, P, P, P, I64, P],

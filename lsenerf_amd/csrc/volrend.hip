@@ -31,7 +31,10 @@ __device__ __forceinline__ float wave_inclusive_sum_rev(float v)
 // The exclusive prefix is the inclusive one shifted by a lane (as in visibility_kernel), not `incl - sd`: a surface sample of a
 // trained scene has sd = 1e2 .. 1e5 and beyond, and the subtraction would return the optical depth in front of it -- which decides
 // that sample's weight, the largest of the ray -- to half an ulp of sd; at sd = +inf it is inf - inf = NaN.
-struct GroupWeights { float w, T, alpha; };
+// tau_front / tau_behind: the optical depth in front of and behind this lane's sample (excl + carry and incl + carry, the carry as it
+// stood before the group) -- the accumulated weight through the sample is 1 - exp(-tau_behind), and on lane 63 tau_behind is the
+// bit pattern the next group's carry starts from.  The depth-quantile kernels search them; the compositors do not read them.
+struct GroupWeights { float w, T, alpha, tau_front, tau_behind; };
 
 __device__ __forceinline__ GroupWeights group_weights(float a, float b, float sg, bool valid, int lane, float &carry)
 {
@@ -51,6 +54,8 @@ __device__ __forceinline__ GroupWeights group_weights(float a, float b, float sg
     float excl = __shfl_up(incl, 1, 64);
     if (lane == 0) excl = 0.f;
     GroupWeights g;
+    g.tau_front = excl + carry;
+    g.tau_behind = incl + carry;
     g.T = expf(-(excl + carry));
     g.alpha = 1.f - expf(-sd);
     g.w = valid ? g.T * g.alpha : 0.f;
@@ -396,6 +401,143 @@ __global__ __launch_bounds__(256) void eval_segment_finish_kernel(const float *_
                out_acc, out_nsamples);
 }
 
+// Quantile depths of an evaluation render (lse_eval_depth_quantiles and its segmented form; include/lse_hip.h has the definition):
+// the walk of eval_composite_kernel with its scan (group_weights), searched instead of summed.  The accumulated weight through
+// sample k is 1 - exp(-tau_behind(k)), so "the weights up to k reach q" is tau_behind(k) >= tau_q = -ln(1 - q): one comparison per
+// lane, the first crossing of a group by a ballot and a find-first-set, its depth fetched from that lane.  Everything that is kept
+// (the depths, the found mask) is the same on all 64 lanes; no atomics, no LDS.
+struct DepthTaus { float v[4]; };
+
+__device__ __forceinline__ float pick4(const float (&v)[4], int j)      // v[j] without a dynamically indexed register array
+{
+    return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
+}
+
+// One 64-sample group into the search: for every quantile not found yet, the first valid lane with tau_behind >= tau_q (a NaN never
+// compares true, +inf does) gives the depth -- the sample's mid-point, or with `interp` the crossing under piecewise-constant
+// density, a + (tau_q - tau_front) / sigma clamped to [a, b] (sigma = +inf: a; a NaN quotient: the mid-point).
+__device__ __forceinline__ void quantile_group(const GroupWeights &g, float a, float b, float sg, float mid, bool valid,
+                                               const DepthTaus &tau, int n_q, bool interp, float (&dq)[4], int &found)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j >= n_q || ((found >> j) & 1)) continue;
+        const unsigned long long hit = __ballot(valid && g.tau_behind >= tau.v[j]);
+        if (hit == 0ull) continue;
+        float d = mid;
+        if (interp) {
+            const float x = (tau.v[j] - g.tau_front) / sg;
+            if (x == x) d = fminf(fmaxf(a + x, a), b);
+        }
+        dq[j] = __shfl(d, __ffsll(hit) - 1, 64);
+        found |= 1 << j;
+    }
+}
+
+// depth_sel of one ray from its quantile depths: depth_q[sel] where quantile sel was reached and -- with a finite max_spread -- the
+// last quantile was reached too and lies at most max_spread behind the first; NaN ("no usable depth") otherwise.
+__device__ __forceinline__ float select_depth(const float (&dq)[4], int found, int n_q, int flags, float max_spread)
+{
+#pragma clang fp contract(off)
+    const int sel = (flags >> 8) & 3;
+    bool ok = ((found >> sel) & 1) != 0;
+    if (max_spread < INFINITY) ok = ok && ((found >> (n_q - 1)) & 1) && (pick4(dq, n_q - 1) - dq[0] <= max_spread);
+    return ok ? pick4(dq, sel) : NAN;
+}
+
+__global__ __launch_bounds__(256) void eval_depth_quantiles_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                                   const float *__restrict__ sigma, const int64_t *__restrict__ packed,
+                                                                   int n_rays, DepthTaus tau, int n_q, int flags, float max_spread,
+                                                                   float *__restrict__ depth_q, uint8_t *__restrict__ reached,
+                                                                   float *__restrict__ depth_sel)
+{
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
+    const bool interp = (flags & LSE_DEPTH_INTERPOLATE) != 0;
+    const int full = (1 << n_q) - 1;
+    float carry = 0.f, mid = 0.f;
+    float dq[4] = {0.f, 0.f, 0.f, 0.f};
+    int found = 0;
+    for (int64_t base = 0; base < cnt; base += 64) {
+        const int64_t i = s0 + base + lane;
+        const bool valid = base + lane < cnt;
+        float a = 0.f, b = 0.f, sg = 0.f;
+        if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
+        const GroupWeights g = group_weights(a, b, sg, valid, lane, carry);
+        mid = (a + b) * 0.5f;
+        quantile_group(g, a, b, sg, mid, valid, tau, n_q, interp, dq, found);
+        if (found == full) break;        // (the same on every lane) nothing behind the last crossing is needed
+    }
+    if (found != full && cnt > 0) {      // the loop ran to the ray's end: `mid` is the last group's, the last sample's lane holds it
+        const float last = __shfl(mid, (int)((cnt - 1) & 63), 64);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (!((found >> j) & 1)) dq[j] = last;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < n_q) depth_q[(int64_t)ray * n_q + j] = dq[j];
+        reached[ray] = (uint8_t)found;
+        if (depth_sel) depth_sel[ray] = select_depth(dq, found, n_q, flags, max_spread);
+    }
+}
+
+// The same search over one segment of the early-stop route.  State of a ray, [2] floats: the carry, and the found mask as int32; a
+// zero-filled state is the start.  The carry is group_weights' own, so it has the bits the compositor's state carries.  The depths
+// themselves live in depth_q between the segments: a quantile found in an earlier segment is read back, not written again.
+__global__ __launch_bounds__(256) void eval_depth_quantiles_segment_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                                           const float *__restrict__ sigma,
+                                                                           const int64_t *__restrict__ seg_packed, int n_rays,
+                                                                           DepthTaus tau, int n_q, int flags, float max_spread,
+                                                                           float *state, float *depth_q, uint8_t *__restrict__ reached,
+                                                                           float *__restrict__ depth_sel)
+{
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = seg_packed[2 * ray], cnt = seg_packed[2 * ray + 1];
+    if (cnt <= 0) return;                // a finished (or empty) ray is left alone
+    const bool interp = (flags & LSE_DEPTH_INTERPOLATE) != 0;
+    const int full = (1 << n_q) - 1;
+    float *st = state + 2 * (int64_t)ray;
+    float carry = st[0], mid = 0.f;
+    const int before = reinterpret_cast<const int32_t *>(st)[1] & full;
+    if (before == full) return;          // every quantile was found in an earlier segment: the outputs are final
+    float dq[4] = {0.f, 0.f, 0.f, 0.f};
+    int found = before;
+    for (int64_t base = 0; base < cnt; base += 64) {
+        const int64_t i = s0 + base + lane;
+        const bool valid = base + lane < cnt;
+        float a = 0.f, b = 0.f, sg = 0.f;
+        if (valid) { a = ts[i]; b = te[i]; sg = sigma[i]; }
+        const GroupWeights g = group_weights(a, b, sg, valid, lane, carry);
+        mid = (a + b) * 0.5f;
+        quantile_group(g, a, b, sg, mid, valid, tau, n_q, interp, dq, found);
+        if (found == full) break;
+    }
+    const float last = __shfl(mid, (int)((cnt - 1) & 63), 64);      // used only where the loop ran to the segment's end
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n_q) continue;
+            float *out = depth_q + (int64_t)ray * n_q + j;
+            if ((before >> j) & 1) dq[j] = *out;
+            else {
+                if (!((found >> j) & 1)) dq[j] = last;
+                *out = dq[j];
+            }
+        }
+        st[0] = carry;
+        reinterpret_cast<int32_t *>(st)[1] = found;
+        reached[ray] = (uint8_t)found;
+        if (depth_sel) depth_sel[ray] = select_depth(dq, found, n_q, flags, max_spread);
+    }
+}
+
 __global__ __launch_bounds__(256) void volrend_bwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                           const float *__restrict__ sigma, const float *__restrict__ rgb,
                                                           int rgb_stride, const int64_t *__restrict__ packed, int n_rays,
@@ -722,6 +864,54 @@ extern "C" int lse_eval_composite_finish(const void *state, int32_t n_rays, int3
     hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(1024), 0, st, (const float *)num, (const float *)out_acc,
                        (const float *)mid_range, n_rays, out_depth, (float *)nullptr);
     return lse::check_launch("lse_eval_composite_finish");
+}
+
+// the argument checks the two depth-quantile entry points share; fills `tau`
+static int depth_quantile_args(const char *who, int32_t n_rays, int32_t n_q, const float *h_tau_q, int32_t flags, float max_spread,
+                               DepthTaus &tau)
+{
+    LSE_REQUIRE(n_rays >= 0, "%s: n_rays < 0", who);
+    LSE_REQUIRE(n_q >= 1 && n_q <= 4, "%s: n_q %d outside 1..4", who, n_q);
+    LSE_REQUIRE(h_tau_q, "%s: null pointer (tau_q)", who);
+    for (int j = 0; j < 4; ++j) tau.v[j] = j < n_q ? h_tau_q[j] : INFINITY;
+    LSE_REQUIRE(tau.v[0] > 0.f, "%s: tau_q[0] = %g is not positive", who, (double)tau.v[0]);
+    for (int j = 1; j < n_q; ++j)
+        LSE_REQUIRE(tau.v[j] > tau.v[j - 1], "%s: tau_q is not ascending (tau_q[%d] = %g after %g)", who, j, (double)tau.v[j],
+                    (double)tau.v[j - 1]);
+    LSE_REQUIRE((flags & ~(LSE_DEPTH_INTERPOLATE | (3 << 8))) == 0, "%s: unknown flags %d", who, flags);
+    LSE_REQUIRE(((flags >> 8) & 3) < n_q, "%s: selected quantile %d of %d", who, (flags >> 8) & 3, n_q);
+    LSE_REQUIRE(max_spread >= 0.f, "%s: max_spread %g is negative or NaN", who, (double)max_spread);
+    return LSE_OK;
+}
+
+extern "C" int lse_eval_depth_quantiles(const float *t_starts, const float *t_ends, const float *sigmas, const int64_t *packed_info,
+                                        int32_t n_rays, int32_t n_q, const float *h_tau_q, int32_t flags, float max_spread,
+                                        float *depth_q, uint8_t *reached, float *depth_sel, lse_stream_t stream)
+{
+    DepthTaus tau;
+    if (int rc = depth_quantile_args("lse_eval_depth_quantiles", n_rays, n_q, h_tau_q, flags, max_spread, tau)) return rc;
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(t_starts && t_ends && sigmas && packed_info && depth_q && reached, "lse_eval_depth_quantiles: null pointer");
+    hipLaunchKernelGGL(eval_depth_quantiles_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), t_starts, t_ends,
+                       sigmas, packed_info, n_rays, tau, n_q, flags, max_spread, depth_q, reached, depth_sel);
+    return lse::check_launch("lse_eval_depth_quantiles");
+}
+
+extern "C" int lse_eval_depth_quantiles_segment(const float *t_starts, const float *t_ends, const float *sigmas,
+                                                const int64_t *seg_packed, int32_t n_rays, int32_t n_q, const float *h_tau_q,
+                                                int32_t flags, float max_spread, void *state, float *depth_q, uint8_t *reached,
+                                                float *depth_sel, lse_stream_t stream)
+{
+    DepthTaus tau;
+    if (int rc = depth_quantile_args("lse_eval_depth_quantiles_segment", n_rays, n_q, h_tau_q, flags, max_spread, tau)) return rc;
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(t_starts && t_ends && sigmas && seg_packed && state && depth_q && reached,
+                "lse_eval_depth_quantiles_segment: null pointer");
+    LSE_REQUIRE(((uintptr_t)state & 3) == 0, "lse_eval_depth_quantiles_segment: state is not 4-byte aligned");
+    hipLaunchKernelGGL(eval_depth_quantiles_segment_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), t_starts,
+                       t_ends, sigmas, seg_packed, n_rays, tau, n_q, flags, max_spread, static_cast<float *>(state), depth_q, reached,
+                       depth_sel);
+    return lse::check_launch("lse_eval_depth_quantiles_segment");
 }
 
 extern "C" int lse_render_weight_fwd(const float *t_starts, const float *t_ends, const float *sigmas,

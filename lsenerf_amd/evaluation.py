@@ -73,10 +73,84 @@ def _render_loop(model, rb: RayBundle, chunk: int) -> Dict[str, Tensor]:
     return {k: torch.cat(v) for k, v in lists.items()}
 
 
-def _render_count_free(model, rb: RayBundle, chunk: int, check_overflow: bool = True) -> Dict[str, Tensor]:
+def depth_quantile_settings(config) -> Tuple[Tuple[float, ...], bool]:
+    """(quantiles, interpolate) of ``config``, validated: ValueError unless the quantiles are at most 4 values strictly inside
+    (0, 1) in ascending order and -- with ``eval_early_stop_eps > 0`` -- every ``1 - q >= eps`` (a ray may be stopped once its
+    transmittance is below eps: a quantile beyond that could lie behind the stop).  Pure host code: nothing touches a device."""
+    raw = config.eval_depth_quantiles
+    try:
+        qs = tuple(float(q) for q in raw)
+    except TypeError:
+        raise ValueError(f"eval_depth_quantiles must be a tuple of floats, got {raw!r}") from None
+    if len(qs) > 4:
+        raise ValueError(f"eval_depth_quantiles takes at most 4 values, got {len(qs)}")
+    if any(not (0.0 < q < 1.0) for q in qs):          # (a NaN fails this too)
+        raise ValueError(f"eval_depth_quantiles must lie strictly inside (0, 1), got {qs}")
+    if any(b <= a for a, b in zip(qs[:-1], qs[1:])):
+        raise ValueError(f"eval_depth_quantiles must be ascending, got {qs}")
+    eps = float(config.eval_early_stop_eps)
+    if qs and eps > 0.0 and not (1.0 - qs[-1] >= eps):
+        raise ValueError(f"eval_depth_quantiles {qs} with eval_early_stop_eps = {eps}: every quantile needs 1 - q >= eps, or a ray "
+                         f"may be stopped before the crossing")
+    return qs, bool(config.eval_depth_interpolate)
+
+
+class _DepthQuantiles:
+    """The quantile-depth outputs of one image on the count-free routes: the buffers, and the one extra launch per chunk
+    (``full``) or per segment (``segment``, after ``begin`` has reset the chunk's state).  ``select`` = (column,
+    max_spread or None) adds "depth_selected" (``ops.eval_depth_quantiles``' ``depth_sel``) for the exporters."""
+
+    def __init__(self, qs, interpolate: bool, select, R: int, n: int, dev, segmented: bool):
+        self.taus = [ops.depth_tau(q) for q in qs]
+        self.interpolate = interpolate
+        self.sel, self.max_spread = (0, None) if select is None else (int(select[0]), select[1])
+        if select is not None and not 0 <= self.sel < len(qs):
+            raise ValueError(f"depth_select: column {self.sel} of {len(qs)} quantiles")
+        # the segment kernel leaves a ray without samples alone: there the image starts as what such a ray gets (0 / 0 / NaN), filled
+        # once per image; the one-launch kernel writes every ray
+        new = (lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)) if segmented else \
+            (lambda shape, dtype, fill: torch.empty(shape, dtype=dtype, device=dev))
+        self.depth_q = new((R, len(qs)), torch.float32, 0.0)
+        self.reached = new((R,), torch.uint8, 0)
+        self.selected = new((R,), torch.float32, float("nan")) if select is not None else None
+        self.state = torch.empty((n, 2), dtype=torch.float32, device=dev) if segmented else None      # carry and found mask
+
+    def _rows(self, lo: int, hi: int):
+        return self.depth_q[lo:hi], self.reached[lo:hi], None if self.selected is None else self.selected[lo:hi]
+
+    def _kw(self):
+        return dict(interpolate=self.interpolate, sel=self.sel, max_spread=self.max_spread)
+
+    def full(self, ts, te, sigma, packed, lo: int, hi: int) -> None:
+        ops.eval_depth_quantiles(ts, te, sigma, packed, self.taus, *self._rows(lo, hi), **self._kw())
+
+    def begin(self, lo: int, hi: int) -> None:
+        self.state[:hi - lo].zero_()
+
+    def segment(self, ts, te, sigma, packed, lo: int, hi: int) -> None:
+        ops.eval_depth_quantiles_segment(ts, te, sigma, packed, self.taus, self.state[:hi - lo], *self._rows(lo, hi), **self._kw())
+
+    def outputs(self) -> Dict[str, Tensor]:
+        out = {"depth_quantiles": self.depth_q, "depth_reached": self.reached[:, None]}
+        if self.selected is not None:
+            out["depth_selected"] = self.selected[:, None]
+        return out
+
+
+def _depth_quantiles_of(model, depth_select, R: int, n: int, dev, segmented: bool) -> Optional[_DepthQuantiles]:
+    qs, interpolate = depth_quantile_settings(model.config)
+    if not qs or model.training:
+        if depth_select is not None:
+            raise ValueError("depth_select needs eval_depth_quantiles and eval mode")
+        return None
+    return _DepthQuantiles(qs, interpolate, depth_select, R, n, dev, segmented)
+
+
+def _render_count_free(model, rb: RayBundle, chunk: int, check_overflow: bool = True, depth_select=None) -> Dict[str, Tensor]:
     cfg, fld = model.config, model.field
     R = len(rb)
     dev = rb.origins.device
+    quant = _depth_quantiles_of(model, depth_select, R, min(chunk, R), dev, segmented=False)
     rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
     acc = torch.empty(R, dtype=torch.float32, device=dev)
     depth = torch.empty(R, dtype=torch.float32, device=dev)
@@ -99,6 +173,8 @@ def _render_count_free(model, rb: RayBundle, chunk: int, check_overflow: bool = 
         sigma, _, _, head = fld.density_rgb_packed(rays_o, rays_d, ri, ts, te, packed, eidx, table, n_dev, features_out=feats)
         ops.eval_composite(ts, te, sigma, head, packed, rgb[lo:hi], acc[lo:hi], depth[lo:hi], nsamples[lo:hi],
                            nan_to_num=not linear, background=background, clamp=not linear, workspace=ws)
+        if quant is not None:
+            quant.full(ts, te, sigma, packed, lo, hi)
         if normals is not None:
             model.composite_normals(feats["x01"], feats["y"], ts, te, sigma, packed, rays_o, rays_d, normals[lo:hi], n_dev)
     if check_overflow:
@@ -106,6 +182,8 @@ def _render_count_free(model, rb: RayBundle, chunk: int, check_overflow: bool = 
     raw = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": nsamples}
     if normals is not None:
         raw["normals"] = normals
+    if quant is not None:
+        raw.update(quant.outputs())
     return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
 
 
@@ -140,7 +218,7 @@ def early_stop_settings(config) -> Tuple[float, int]:
     return eps, int(base)
 
 
-def _render_early_stop(model, rb: RayBundle, chunk: int, check_overflow: bool = True) -> Dict[str, Tensor]:
+def _render_early_stop(model, rb: RayBundle, chunk: int, check_overflow: bool = True, depth_select=None) -> Dict[str, Tensor]:
     """The count-free route with early ray termination: a chunk is marched as in ``_render_count_free`` but its samples stay in the
     marcher's per-ray slots; per segment of ``segment_schedule`` the live rays' samples are packed, the field evaluates them and
     ``lse_eval_composite_segment`` continues every ray from its saved state, finishing those whose optical depth has reached
@@ -152,6 +230,7 @@ def _render_early_stop(model, rb: RayBundle, chunk: int, check_overflow: bool = 
     R = len(rb)
     n = min(chunk, R)
     dev = rb.origins.device
+    quant = _depth_quantiles_of(model, depth_select, R, n, dev, segmented=True)
     cap = model.occupancy_grid._cap_per_ray(cfg.near_plane, cfg.far_plane, cfg.render_step_size, cfg.cone_angle)
     sched = segment_schedule(cap, base)
     longest = max(length for _, length in sched)
@@ -184,6 +263,8 @@ def _render_early_stop(model, rb: RayBundle, chunk: int, check_overflow: bool = 
         table, eidx = fld._eval_emb(m, dev) if fld.embedding_appearance is not None else (None, None)
         packed = seg_packed[:m]
         ops.eval_segment_begin(cnts, sched[0][1], state, seg_cnts[:m])
+        if quant is not None:
+            quant.begin(lo, hi)
         for k, (off, length) in enumerate(sched):
             ops.pack_info_from_counts(seg_cnts[:m], out=(packed, n_dev))
             C = m * length
@@ -192,6 +273,8 @@ def _render_early_stop(model, rb: RayBundle, chunk: int, check_overflow: bool = 
             if k == 0:           # nerfstudio's fake sample belongs to the chunk: a chunk without any sample gets it here
                 ops.fake_sample_if_empty(packed, n_dev, ri, ts, te)
             sigma, _, _, head = fld.density_rgb_packed(rays_o, rays_d, ri, ts, te, packed, eidx, table, n_dev)
+            if quant is not None:      # its own state and launch: the compositor's state is not read
+                quant.segment(ts, te, sigma, packed, lo, hi)
             next_len = sched[k + 1][1] if k + 1 < len(sched) else 0
             ops.eval_composite_segment(ts, te, sigma, head, packed, cnts, off + length, next_len, tau_stop, state,
                                        seg_cnts[:m] if next_len else None, nan_to_num=not linear)
@@ -200,27 +283,39 @@ def _render_early_stop(model, rb: RayBundle, chunk: int, check_overflow: bool = 
     if check_overflow:
         model.occupancy_grid.check_deferred_overflow()      # the one read-back, as on the full route
     raw = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": nsamples}
+    if quant is not None:
+        raw.update(quant.outputs())
     return {k: v for k, v in model.route_outputs(raw, rb).items() if torch.is_tensor(v)}
 
 
 @torch.no_grad()
-def render_flat(model, rb: RayBundle, check_overflow: bool = True) -> Dict[str, Tensor]:
+def render_flat(model, rb: RayBundle, check_overflow: bool = True, depth_select=None) -> Dict[str, Tensor]:
     """Outputs ``[R, ...]`` for the ``[R, ...]`` bundle ``rb``, chunked by ``config.eval_num_rays_per_chunk`` on every route (the
     chunking is observable: nerfstudio's fake sample is inserted per chunk).  ``check_overflow=False`` leaves out the count-free
     routes' ``check_deferred_overflow()`` behind the last chunk: the accumulator is sticky, so a caller that renders many images
-    (``eval_set.evaluate_set``) reads it once behind the last of them -- and MUST do so."""
+    (``eval_set.evaluate_set``) reads it once behind the last of them -- and MUST do so.  With ``config.eval_depth_quantiles`` the
+    count-free routes add "depth_quantiles" [R, n_q] and "depth_reached" [R, 1] (uint8, bit j: quantile j was reached), and with
+    ``depth_select = (column, max_spread or None)`` also "depth_selected" [R, 1]: that column, NaN where it was not reached or the
+    last column lies more than ``max_spread`` behind the first (what the exporters unproject and fuse).  The ``forward`` loop has no
+    quantile depths: with the setting on it is a ValueError."""
     chunk = int(model.config.eval_num_rays_per_chunk)
     if chunk <= 0:
         raise ValueError("eval_num_rays_per_chunk must be positive")
     eps, _ = early_stop_settings(model.config)
+    qs, _ = depth_quantile_settings(model.config)
     if len(rb) == 0:
         raise ValueError("empty ray bundle")
+    more = {} if depth_select is None else {"depth_select": depth_select}
     if uses_count_free_route(model, len(rb)):
         if eps > 0.0:
             if model.eval_normals_on():
                 raise ValueError("eval_normals is not built for the early-stop segment route: set eval_early_stop_eps = 0")
-            return _render_early_stop(model, rb, chunk, check_overflow)
-        return _render_count_free(model, rb, chunk, check_overflow)
+            return _render_early_stop(model, rb, chunk, check_overflow, **more)
+        return _render_count_free(model, rb, chunk, check_overflow, **more)
+    if qs or depth_select is not None:
+        raise ValueError("eval_depth_quantiles is built for the count-free eval routes only (eval mode, LSEField with the full-size "
+                         "base MLP, a chunk within deferred_max_slots): this render falls back to the forward loop -- set "
+                         "eval_depth_quantiles = ()")
     return _render_loop(model, rb, chunk)
 
 

@@ -104,6 +104,19 @@ class LSENeRFModelConfig:
     # normals.  Not built for the early-stop segment route: together with ``eval_early_stop_eps > 0`` it is a ValueError in
     # ``populate_modules``, and so is an unknown name.
     eval_normals: str = "off"
+    # --- quantile depths in the eval render: up to four values strictly inside (0, 1), ascending; () = off, every route and output
+    # as without it.  With it on, eval-mode renders on the count-free routes carry outputs["depth_quantiles"] [.., n_q] -- per q the
+    # depth at which the ray's accumulated weight crosses q (0.5: the median depth) -- and outputs["depth_reached"] [.., 1] (uint8,
+    # bit j: quantile j was crossed; where not, the depth is the last sample's mid-point, nerfstudio's clamp).  "depth" stays the
+    # expected depth.  The crossing is searched on the optical depth the compositor's scan carries (tau >= -ln(1 - q), include/
+    # lse_hip.h: lse_eval_depth_quantiles): one extra launch per chunk, or per segment on the early-stop route, where every q needs
+    # 1 - q >= eval_early_stop_eps.  The spread between two quantiles says how concentrated a ray's surface is.  The ``forward``
+    # loop (training mode, another field, the small-grid base MLP) has no quantile depths: ``render_flat`` raises there.  Checked
+    # in ``populate_modules`` and at render time (ValueError).
+    eval_depth_quantiles: Tuple[float, ...] = ()
+    # the quantile depth is the exact crossing inside the sample under piecewise-constant density, a + (tau_q - tau_front) / sigma
+    # clamped to the sample, instead of the sample's mid-point
+    eval_depth_interpolate: bool = False
 
     def __post_init__(self):   # R:lse_nerf/lsenerf.py:86-99
         if self.evs_mapping_method is None or str(self.evs_mapping_method).lower() == "none":
@@ -431,6 +444,7 @@ class LSENeRFModel(nn.Module):
         if cfg.eval_normals != "off" and cfg.eval_early_stop_eps > 0:
             raise ValueError("eval_normals is not built for the early-stop segment route: set eval_early_stop_eps = 0 "
                              f"(got eval_normals={cfg.eval_normals!r}, eval_early_stop_eps={cfg.eval_early_stop_eps})")
+        evaluation.depth_quantile_settings(cfg)
         scene_contraction = None if cfg.disable_scene_contraction else SceneContraction(order=float("inf"))
         self.field = LSEField(aabb=self.scene_aabb_2x3, num_images=self.num_train_data,
                               log2_hashmap_size=cfg.log2_hashmap_size, max_res=cfg.max_res,
@@ -643,14 +657,16 @@ class LSENeRFModel(nn.Module):
         """Triangle mesh of the surface ``views`` (an ``eval_set.EvalSet`` or ``(EdCameras, poses)``) see of the field: eval depth
         renders fused into a truncated signed distance volume, meshed without a surface against unobserved space
         (``lsenerf_amd.tsdf.export_tsdf_mesh``: image_indices, resolution, bounds, truncation, min_accumulation, carve, min_weight,
-        colors, normals, views_per_launch).  Runs without gradients in eval mode and restores the model's mode and eval settings."""
+        colors, normals, views_per_launch, depth, max_depth_spread).  ``depth="median"`` fuses the depth at which the accumulated
+        weight crosses one half instead of the expected depth.  Runs without gradients in eval mode and restores the model's mode and eval settings."""
         from . import tsdf as _tsdf
         return _tsdf.export_tsdf_mesh(self, views, **kwargs)
 
     def export_point_cloud(self, views, **kwargs):
         """Point cloud of what ``views`` (an ``eval_set.EvalSet`` or ray bundles) see of the field: unprojected eval renders, merged
         per voxel and filtered by neighbour support on request (``lsenerf_amd.pointcloud.export_point_cloud``: image_indices,
-        min_accumulation, bounds, voxel_size, min_support, normals, colors, max_points).  Runs without gradients in eval mode and
+        min_accumulation, bounds, voxel_size, min_support, normals, colors, max_points, depth, max_depth_spread).
+        ``depth="median"`` unprojects the depth at which the accumulated weight crosses one half.  Runs without gradients in eval mode and
         restores the model's mode and eval settings."""
         from . import pointcloud as _pointcloud
         return _pointcloud.export_point_cloud(self, views, **kwargs)

@@ -1492,6 +1492,65 @@ def eval_composite_finish(state, out_rgb, out_acc, out_depth, out_nsamples, back
               _f32(out_acc, "out_acc"), _f32(out_depth, "out_depth"), _chk(out_nsamples, torch.int64, "out_nsamples"), _stream())
 
 
+def depth_tau(q: float) -> float:
+    """The optical depth behind which a ray's accumulated weight has reached ``q``: float32(-ln(1 - q)), the logarithm taken in
+    double (``1 - exp(-tau) >= q``); ``q = 0.5`` is the median depth's.  ValueError unless ``0 < q < 1``."""
+    import math
+    import numpy as np
+    q = float(q)
+    if not (0.0 < q < 1.0):
+        raise ValueError(f"depth_tau: q must lie in (0, 1), got {q}")
+    return float(np.float32(-math.log1p(-q)))
+
+
+def _depth_quantile_args(who: str, n: int, tau_q, depth_q, reached, depth_sel, interpolate: bool, sel: int, max_spread):
+    taus = [float(v) for v in tau_q]
+    n_q = len(taus)
+    if tuple(depth_q.shape) != (n, n_q) or tuple(reached.shape) != (n,) or (depth_sel is not None and tuple(depth_sel.shape) != (n,)):
+        raise ValueError(f"{who}: depth_q [n, {n_q}], reached [n] and depth_sel [n] expected for n = {n} rays")
+    if not 0 <= int(sel) <= 3:
+        raise ValueError(f"{who}: sel {sel} outside 0..3")
+    flags = (_lib.LSE_DEPTH_INTERPOLATE if interpolate else 0) | (int(sel) << 8)
+    spread = float("inf") if max_spread is None else float(max_spread)
+    return n_q, (ctypes.c_float * max(n_q, 1))(*taus), flags, spread
+
+
+@torch.no_grad()
+def eval_depth_quantiles(t_starts, t_ends, sigmas, packed_info, tau_q, depth_q, reached, depth_sel=None, interpolate: bool = False,
+                         sel: int = 0, max_spread: Optional[float] = None):
+    """Quantile depths of an evaluation render (lse_eval_depth_quantiles; the definition is in include/lse_hip.h): per ray and per
+    ``tau_q[j]`` (``depth_tau(q_j)``, 1..4 strictly ascending values) the depth of the first sample behind which the optical depth
+    has reached it -- its mid-point, or with ``interpolate`` the crossing inside it -- into ``depth_q [n, n_q]``; bit j of
+    ``reached [n]`` (uint8) says whether it was reached (else the depth is the last sample's mid-point; a ray without samples gets
+    0).  ``depth_sel [n]`` (optional): column ``sel`` where it was reached and, with ``max_spread``, the last column was reached too
+    and lies at most ``max_spread`` behind the first; NaN elsewhere.  The outputs may be contiguous row blocks (views) of image
+    buffers; sample arrays may have capacity extent (``packed_info`` rows are authoritative)."""
+    n = packed_info.shape[0]
+    n_q, taus, flags, spread = _depth_quantile_args("eval_depth_quantiles", n, tau_q, depth_q, reached, depth_sel, interpolate, sel,
+                                                    max_spread)
+    _lib.call("lse_eval_depth_quantiles", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(sigmas, "sigmas"),
+              _chk(packed_info, torch.int64, "packed_info"), n, n_q, taus, flags, spread, _f32(depth_q, "depth_q"),
+              _chk(reached, torch.uint8, "reached"), _f32(depth_sel, "depth_sel", allow_none=True), _stream())
+
+
+@torch.no_grad()
+def eval_depth_quantiles_segment(t_starts, t_ends, sigmas, seg_packed, tau_q, state, depth_q, reached, depth_sel=None,
+                                 interpolate: bool = False, sel: int = 0, max_spread: Optional[float] = None):
+    """One segment of ``eval_depth_quantiles`` on the early-stop route (lse_eval_depth_quantiles_segment): every ray with a count in
+    ``seg_packed`` continues from ``state [n, 2]`` (float32: the carry and the found mask; zeros are the start) over this segment's
+    packed samples; other rays are left alone.  ``depth_q`` / ``reached`` / ``depth_sel`` persist between the segments and start as
+    0 / 0 / NaN; after the last segment they hold what ``eval_depth_quantiles`` gives over the samples walked, bit for bit."""
+    n = seg_packed.shape[0]
+    n_q, taus, flags, spread = _depth_quantile_args("eval_depth_quantiles_segment", n, tau_q, depth_q, reached, depth_sel,
+                                                    interpolate, sel, max_spread)
+    if tuple(state.shape) != (n, 2):
+        raise ValueError(f"eval_depth_quantiles_segment: state [n, 2] expected for n = {n} rays")
+    _lib.call("lse_eval_depth_quantiles_segment", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(sigmas, "sigmas"),
+              _chk(seg_packed, torch.int64, "seg_packed"), n, n_q, taus, flags, spread, _f32(state, "state"),
+              _f32(depth_q, "depth_q"), _chk(reached, torch.uint8, "reached"), _f32(depth_sel, "depth_sel", allow_none=True),
+              _stream())
+
+
 def ssim_window(size: int = 11, sigma: float = 1.5) -> torch.Tensor:
     """torchmetrics' 1-D Gaussian window in float32: exp(-(d / sigma)^2 / 2) for d = -(size-1)/2 .. (size-1)/2, normalised.  The
     image-metrics kernel takes these taps from the host (their outer product is the 2-D window), so kernel and test oracle share them."""

@@ -6,6 +6,7 @@ point per voxel (``ops.voxel_keys``, a stable sort, ``ops.voxel_merge``) and the
 reads are the occupancy grid's overflow check behind the last view and the final count that trims the arrays."""
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 from typing import Optional
 
@@ -23,6 +24,39 @@ class PointCloud:
     colors: Optional[Tensor] = None    # [n, 3] float32 in [0, 1]: the eval render's mapped rgb
     normals: Optional[Tensor] = None   # [n, 3] float32: unit vectors, zero where the density gradient is
     counts: Optional[Tensor] = None    # [n] int32: raw points merged into each point (with voxel_size only)
+
+
+DEPTH_MODES = ("expected", "median")
+MEDIAN_QUANTILES, MEDIAN_COLUMN = (0.25, 0.5, 0.75), 1      # what ``depth="median"`` renders, and the column it uses
+
+
+def depth_mode(depth: str, max_depth_spread: Optional[float]):
+    """(median?, max spread or None) of an exporter's ``depth`` / ``max_depth_spread`` arguments, validated."""
+    if depth not in DEPTH_MODES:
+        raise ValueError(f"depth {depth!r}: one of {DEPTH_MODES} expected")
+    if max_depth_spread is None:
+        return depth == "median", None
+    if depth != "median":
+        raise ValueError("max_depth_spread compares quantile depths: it needs depth='median'")
+    spread = float(max_depth_spread)
+    if not spread >= 0.0:
+        raise ValueError(f"max_depth_spread {max_depth_spread} is negative or NaN")
+    return True, spread
+
+
+@contextlib.contextmanager
+def median_settings(cfg, median: bool):
+    """``cfg.eval_depth_quantiles`` / ``eval_depth_interpolate`` as ``depth="median"`` renders, for the duration; both come back, also
+    behind an exception.  Without ``median`` the configuration is not written."""
+    if not median:
+        yield
+        return
+    saved = (cfg.eval_depth_quantiles, cfg.eval_depth_interpolate)
+    try:
+        cfg.eval_depth_quantiles, cfg.eval_depth_interpolate = MEDIAN_QUANTILES, True
+        yield
+    finally:
+        cfg.eval_depth_quantiles, cfg.eval_depth_interpolate = saved
 
 
 def _views(views, image_indices):
@@ -43,7 +77,8 @@ def _views(views, image_indices):
 
 def export_point_cloud(model, views, image_indices=None, min_accumulation: float = 0.9, bounds=None,
                        voxel_size: Optional[float] = None, min_support: int = 0, normals: bool = True, colors: bool = True,
-                       max_points: Optional[int] = None) -> PointCloud:
+                       max_points: Optional[int] = None, depth: str = "expected",
+                       max_depth_spread: Optional[float] = None) -> PointCloud:
     """Point cloud of ``model``'s field seen from ``views``: an ``eval_set.EvalSet`` (all images, or ``image_indices``) or an iterable
     of ray bundles of any leading shape.  A ray gives a point ``origin + direction * depth`` when its accumulation is at least
     ``min_accumulation``, its depth is positive and finite and the point lies inside ``bounds`` ([2, 3]; default: the field's aabb);
@@ -52,8 +87,13 @@ def export_point_cloud(model, views, image_indices=None, min_accumulation: float
     (needs ``voxel_size``): drop voxels whose 3 x 3 x 3 neighbourhood holds fewer raw points.  ``normals``: analytic world-space
     normals of the render -- ``config.eval_normals = "world"`` and ``config.eval_early_stop_eps = 0`` for the duration of the call
     (normals are not built for the segment route); ``colors``: the render's mapped rgb.  ``max_points``: capacity of the raw cloud
-    (default: every ray, so nothing can be dropped; beyond it rays are dropped in order).  Runs without gradients in eval mode and
-    puts the two settings and every module's mode back."""
+    (default: every ray, so nothing can be dropped; beyond it rays are dropped in order).  ``depth``: ``"expected"`` -- the render's
+    "depth", the mean of the weights -- or ``"median"`` -- the depth at which the accumulated weight crosses one half, interpolated
+    inside the sample (``config.eval_depth_quantiles = (0.25, 0.5, 0.75)`` and ``eval_depth_interpolate`` for the duration): on a
+    silhouette or behind a half-transparent floater the mean lies between two surfaces, the median on one of them; a ray whose
+    weights never reach one half gives no point.  ``max_depth_spread`` (median only): also drop rays whose quartile depths lie
+    further apart -- smeared surfaces.  Runs without gradients in eval mode and puts the settings and every module's mode back."""
+    median, spread = depth_mode(depth, max_depth_spread)
     lo, hi = _bounds(model.field, bounds)
     if voxel_size is not None:
         res = ops.voxel_lattice(lo, hi, voxel_size)
@@ -72,19 +112,23 @@ def export_point_cloud(model, views, image_indices=None, min_accumulation: float
     try:
         if normals:
             cfg.eval_normals, cfg.eval_early_stop_eps = "world", 0.0
-        with torch.no_grad():
+        with torch.no_grad(), median_settings(cfg, median):
             new3 = lambda on: torch.empty((cap, 3), dtype=torch.float32, device=dev) if on else None
             pts, col, nrm = new3(True), new3(colors), new3(normals)
             total = torch.zeros(1, dtype=torch.int64, device=dev)
             ws = None
             for bundle in bundles:
                 rb = evaluation._flatten_bundle(bundle, device=dev)
-                out = evaluation.render_flat(model, rb, check_overflow=False)
+                if median:
+                    out = evaluation.render_flat(model, rb, check_overflow=False, depth_select=(MEDIAN_COLUMN, spread))
+                else:
+                    out = evaluation.render_flat(model, rb, check_overflow=False)
                 if normals and "normals" not in out:
                     raise ValueError("this model's eval render has no normals (they need the count-free route): pass normals=False")
                 if ws is None or ws.numel() < ops.unproject_workspace_bytes(len(rb)):
                     ws = torch.empty(ops.unproject_workspace_bytes(len(rb)), dtype=torch.uint8, device=dev)
-                ops.unproject_append(rb.origins.contiguous(), rb.directions.contiguous(), out["depth"].reshape(-1).contiguous(),
+                ops.unproject_append(rb.origins.contiguous(), rb.directions.contiguous(),
+                                     out["depth_selected" if median else "depth"].reshape(-1).contiguous(),
                                      out["accumulation"].reshape(-1).contiguous(), lo, hi, min_accumulation, pts, total,
                                      colors=out["rgb"].contiguous() if colors else None,
                                      normals=out["normals"].contiguous() if normals else None, out_colors=col, out_normals=nrm,

@@ -98,7 +98,8 @@ def _views(views, image_indices):
 
 def export_tsdf_mesh(model, views, image_indices=None, resolution=256, bounds=None, truncation: Optional[float] = None,
                      min_accumulation: float = 0.5, carve: bool = True, min_weight: float = 1, colors: Optional[str] = "fused",
-                     normals: bool = True, views_per_launch: int = 8) -> _mesh.Mesh:
+                     normals: bool = True, views_per_launch: int = 8, depth: str = "expected",
+                     max_depth_spread: Optional[float] = None) -> _mesh.Mesh:
     """Mesh of the surface ``views`` see of ``model``'s field, by TSDF fusion of eval depth renders.  ``views``: an
     ``eval_set.EvalSet`` (its camera, pose table and the camera of every image) or a pair ``(EdCameras, poses [n, 3, 4])``;
     ``image_indices`` selects and orders the images / poses (order is part of the definition: views are folded one after the other).
@@ -110,10 +111,16 @@ def export_tsdf_mesh(model, views, image_indices=None, resolution=256, bounds=No
     lattice point, blended at the vertices (``render_flat``'s rgb has passed the model's output mapping already, so
     ``mesh.eval_colour_mapping`` is not applied again); ``"field"`` -- ``mesh.vertex_colors``, the field's colour seen against the
     normal; ``None``.  ``normals``: ``mesh.vertex_normals``.  ``views_per_launch``: views per integration launch; it does not change
-    a bit.  Runs without gradients in eval mode with ``config.eval_normals`` off, and puts the setting and every module's mode
-    back; an early-stop eval render is used as it is."""
+    a bit.  ``depth``: ``"expected"`` -- the render's "depth" -- or ``"median"`` -- the interpolated depth at which the accumulated
+    weight crosses one half (``pointcloud.export_point_cloud`` has the definition; ``config.eval_depth_quantiles`` and
+    ``eval_depth_interpolate`` are set for the duration): a pixel whose weights never reach one half, or -- with
+    ``max_depth_spread`` -- whose quartile depths lie further apart, has no usable depth and is skipped without carving.  Runs
+    without gradients in eval mode with ``config.eval_normals`` off, and puts the settings and every module's mode back; an
+    early-stop eval render is used as it is."""
     from .events import _camera_desc, _check_poses, _eval_no_grad
     from .eval_set import camera_bundle, pose_bundle
+    from .pointcloud import MEDIAN_COLUMN, depth_mode, median_settings
+    median, spread = depth_mode(depth, max_depth_spread)
     if colors not in COLOR_MODES:
         raise ValueError(f"colors {colors!r}: one of {COLOR_MODES} expected")
     vpl = int(views_per_launch)
@@ -142,7 +149,7 @@ def export_tsdf_mesh(model, views, image_indices=None, resolution=256, bounds=No
         app = torch.zeros(1, dtype=torch.int32, device=dev)
         rows = {k: v[0].to(dev) for k, v in (cameras.metadata or {}).items() if torch.is_tensor(v)}
     r2_max = border_r2_max(desc)
-    with _eval_no_grad(model):
+    with _eval_no_grad(model), median_settings(model.config, median):
         vol = TSDFVolume(res, lo, hi, truncation, dev, colors=colors == "fused")
         fuse = vol.cw is not None
         pose_b = torch.empty((vpl, 3, 4), dtype=torch.float32, device=dev)
@@ -156,9 +163,13 @@ def export_tsdf_mesh(model, views, image_indices=None, resolution=256, bounds=No
         k = 0
         for i, cam in zip(idx, cam_of):
             bundle = camera_bundle(es, i) if es is not None else pose_bundle(desc, table[cam], H, W, 0, app, None, rows)
-            out = evaluation.render_flat(model, evaluation._flatten_bundle(bundle, device=dev), check_overflow=False)
+            flat = evaluation._flatten_bundle(bundle, device=dev)
+            if median:
+                out = evaluation.render_flat(model, flat, check_overflow=False, depth_select=(MEDIAN_COLUMN, spread))
+            else:
+                out = evaluation.render_flat(model, flat, check_overflow=False)
             pose_b[k].copy_(table[cam])
-            depth_b[k].copy_(out["depth"].reshape(-1))
+            depth_b[k].copy_(out["depth_selected" if median else "depth"].reshape(-1))
             acc_b[k].copy_(out["accumulation"].reshape(-1))
             if fuse:
                 rgb_b[k].copy_(out["rgb"].reshape(-1, 3))

@@ -9,6 +9,7 @@ their poses and intrinsics only, so no image file is opened.
 
 usage: python tools/export_pointcloud.py CKPT_DIR SCENE_DIR OUT.ply [--step N] [--split val] [--images 0,4,8] [--min-accumulation 0.9]
            [--voxel-size 0.01] [--min-support 4] [--bounds x0,y0,z0,x1,y1,z1] [--no-colors] [--no-normals] [--max-points N]
+           [--depth expected|median] [--max-depth-spread D]
            [--scale-factor 1.0] [--scene-scale 1.0] [--config name=value ...]"""
 import argparse
 import os
@@ -46,6 +47,11 @@ def main(argv=None) -> None:
     ap.add_argument("--no-colors", action="store_true")
     ap.add_argument("--no-normals", action="store_true")
     ap.add_argument("--max-points", type=int, default=None)
+    ap.add_argument("--depth", default="expected", choices=("expected", "median"),
+                    help="the depth that is unprojected: the render's expected depth, or the depth at which the accumulated weight "
+                         "crosses one half")
+    ap.add_argument("--max-depth-spread", type=float, default=None,
+                    help="with --depth median: drop rays whose 0.25 and 0.75 quantile depths lie further apart (world units)")
     ap.add_argument("--scale-factor", type=float, default=1.0)
     ap.add_argument("--scene-scale", type=float, default=1.0, help="half extent of the scene box the model was built with")
     ap.add_argument("--num-train-data", type=int, default=None)
@@ -71,7 +77,8 @@ def main(argv=None) -> None:
     eval_set = scene_eval_set(args.scene, args.split, args.scale_factor, s)
     cloud = model.export_point_cloud(eval_set, image_indices=images, min_accumulation=args.min_accumulation, bounds=bounds,
                                      voxel_size=args.voxel_size, min_support=args.min_support, normals=not args.no_normals,
-                                     colors=not args.no_colors, max_points=args.max_points)
+                                     colors=not args.no_colors, max_points=args.max_points, depth=args.depth,
+                                     max_depth_spread=args.max_depth_spread)
     write_ply_points(args.output, cloud)
     views = len(eval_set) if images is None else len(images)
     print(f"step {info['step']}: {cloud.points.shape[0]} points from {views} views -> {args.output}")

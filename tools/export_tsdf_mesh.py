@@ -8,7 +8,8 @@ The checkpoint and configuration arguments are those of tools/export_mesh.py; th
 
 usage: python tools/export_tsdf_mesh.py CKPT_DIR SCENE_DIR OUT.ply [--step N] [--split val] [--images 0,4,8] [--resolution 256]
            [--truncation T] [--min-accumulation 0.5] [--no-carve] [--min-weight 1] [--colors fused|field|none] [--no-normals]
-           [--bounds x0,y0,z0,x1,y1,z1] [--views-per-launch 8] [--scale-factor 1.0] [--scene-scale 1.0] [--config name=value ...]"""
+           [--bounds x0,y0,z0,x1,y1,z1] [--views-per-launch 8] [--depth expected|median] [--max-depth-spread D]
+           [--scale-factor 1.0] [--scene-scale 1.0] [--config name=value ...]"""
 import argparse
 import os
 import sys
@@ -39,6 +40,10 @@ def main(argv=None) -> None:
     ap.add_argument("--no-normals", action="store_true")
     ap.add_argument("--bounds", default=None)
     ap.add_argument("--views-per-launch", type=int, default=8)
+    ap.add_argument("--depth", default="expected", choices=("expected", "median"),
+                    help="the depth that is fused: the render's expected depth, or the depth at which the accumulated weight crosses one half")
+    ap.add_argument("--max-depth-spread", type=float, default=None,
+                    help="with --depth median: skip pixels whose 0.25 and 0.75 quantile depths lie further apart (world units)")
     ap.add_argument("--scale-factor", type=float, default=1.0)
     ap.add_argument("--scene-scale", type=float, default=1.0, help="half extent of the scene box the model was built with")
     ap.add_argument("--num-train-data", type=int, default=None)
@@ -66,7 +71,8 @@ def main(argv=None) -> None:
     mesh = model.export_tsdf_mesh(eval_set, image_indices=images, resolution=res[0] if len(res) == 1 else tuple(res), bounds=bounds,
                                   truncation=args.truncation, min_accumulation=args.min_accumulation, carve=not args.no_carve,
                                   min_weight=args.min_weight, colors=None if args.colors == "none" else args.colors,
-                                  normals=not args.no_normals, views_per_launch=args.views_per_launch)
+                                  normals=not args.no_normals, views_per_launch=args.views_per_launch, depth=args.depth,
+                                  max_depth_spread=args.max_depth_spread)
     write_ply(args.output, mesh)
     views = len(eval_set) if images is None else len(images)
     print(f"step {info['step']}: {mesh.vertices.shape[0]} vertices, {mesh.triangles.shape[0]} triangles from {views} views -> {args.output}")
