@@ -406,6 +406,38 @@ int lse_render_weight_bwd(const float *t_starts, const float *t_ends, const floa
                           int32_t n_rays, const float *weights, const float *d_weights, float *d_sigmas,
                           lse_stream_t stream);
 
+/* Distortion loss of mip-NeRF 360 (nerfacc.losses.distortion) on the render weights of packed, ray-sorted samples (csrc/volrend.hip;
+ * ABI 6, additive).  One 64-lane wave per ray, no atomics, no LDS, no workspace, the same inputs give the same bits.  Per ray with
+ * samples [a_k, b_k), k = 0 .. n-1, mid-points non-decreasing (how the marcher emits them), weights w_k as lse_volrend_fwd /
+ * lse_volrend_depth_fwd / lse_render_weight_fwd wrote them, and the host scalar t_scale >= 0 (finite):
+ *   m_k = t_scale * ((a_k - a_0) + (b_k - b_0)) / 2   the scaled mid-point RELATIVE TO THE RAY'S FIRST -- L and dL/dw do not change
+ *                                                     under m -> m - c, and without the shift m_i W_<i - M_<i cancels at the size of t;
+ *   delta_k = t_scale * (b_k - a_k),   W_<i = sum_{j<i} w_j,   M_<i = sum_{j<i} w_j m_j   (W_>i, M_>i: the sums over j > i);
+ *   L       = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i  =  2 sum_i w_i (m_i W_<i - M_<i) + (1/3) sum_i w_i^2 delta_i
+ *   dL/dw_i = 2 [m_i (W_<i - W_>i) - (M_<i - M_>i)] + (2/3) w_i delta_i.
+ * lse_distortion_fwd: out_loss [n_rays] = L; out_totals [n_rays,2] (nullable) = (W_tot, M_tot) = (sum w, sum w m), what the backward
+ *   takes in place of a pass of its own.
+ *     a ray without samples: L = 0, totals (0, 0);  one sample: the second term alone, w_0^2 delta_0 / 3;
+ *     weights are in [0, 1] whatever the density (sigma = 3e38, +inf): every output is finite.
+ * lse_distortion_bwd: g = g_loss[r * g_stride] -- the upstream gradient per ray (g_stride 1) or one device scalar for all rays
+ *   (g_stride 0); totals: out_totals of the forward over the same inputs.
+ *     d_weights (nullable) [N]: g * dL/dw_i -- the generic route, the caller composites with the weights;
+ *     d_sigmas (nullable) [N]: that gradient through render_weight_from_density in the same launch, by the recurrence of
+ *        lse_volrend_bwd:  d_sigma_k = (b_k - a_k) (dw_k (T_end + W_>k) - sum_{i>k} dw_i w_i);
+ *     sigmas (nullable; read only for d_sigmas): the densities the weights came from.  Given, T_end = exp(-sum_k sigma_k (b_k - a_k));
+ *        null, T_end = 1 - W_tot, which on an opaque ray is 0 or +-2^-24 by the last bits of the forward's expf -- behind a surface
+ *        that leaves dw_k 2^-24 (b_k - a_k) where the true d_sigma is ~ 0, and this loss's dw grows with the distance from the ray's
+ *        centre of mass.  Pass them wherever they exist.  d_weights does not depend on them;
+ *     at least one of the two outputs is given; every sample a packed_info row covers is written, nothing else is (no zero-fill
+ *     needed; a ray without samples writes nothing).  t_starts / t_ends are not differentiated.
+ * Sample arrays may have capacity extent: packed_info [n_rays,2] = (start, count) int64 rows are authoritative.  t_scale negative,
+ * NaN or infinite, a g_stride other than 0 / 1 or a missing pointer: LSE_E_INVALID, checked before anything is launched. */
+int lse_distortion_fwd(const float *t_starts, const float *t_ends, const float *weights, const int64_t *packed_info, int32_t n_rays,
+                       float t_scale, float *out_loss, float *out_totals, lse_stream_t stream);
+int lse_distortion_bwd(const float *t_starts, const float *t_ends, const float *sigmas, const float *weights,
+                       const int64_t *packed_info, int32_t n_rays, float t_scale, const float *totals, const float *g_loss,
+                       int32_t g_stride, float *d_weights, float *d_sigmas, lse_stream_t stream);
+
 /* Forward-only compositing of an EVALUATION render (no autograd, nothing kept for a backward pass): the per-ray walk and summation
  * order of lse_volrend_depth_fwd, bit for bit, plus the renderer epilogue of LSENeRFModel.render_packed in the same call:
  *   flags & LSE_EVAL_NAN_TO_NUM: torch.nan_to_num of the three colour columns per sample (renderers other than LinearRenderer);

@@ -166,6 +166,8 @@ SIGNATURES = {
     "lse_volrend_fwd": [P, P, P, P, I32, P, I32, P, P, P, P, P],
     "lse_volrend_bwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P],
     "lse_volrend_depth_fwd": [P, P, P, P, I32, P, I32, P, P, P, P, P, P, P, P],
+    "lse_distortion_fwd": [P, P, P, P, I32, F32, P, P, P],
+    "lse_distortion_bwd": [P, P, P, P, P, I32, F32, P, P, I32, P, P, P],
     "lse_eval_composite": [P, P, P, P, I32, P, I32, I32, F32, P, P, P, P, P, P],
     "lse_eval_composite_normals": [P, P, P, P, P, I32, P, P, I32, P, I32, P, P],
     "lse_eval_segment_state_bytes": [I32, POINTER(c_int64)],

@@ -596,6 +596,138 @@ __global__ __launch_bounds__(256) void volrend_bwd_kernel(const float *__restric
     }
 }
 
+// Distortion loss of mip-NeRF 360 on the render weights (lse_distortion_fwd / lse_distortion_bwd; include/lse_hip.h has the
+// definition).  The mid-point of a sample is taken relative to the ray's first mid-point and formed from differences of the
+// interval ends, m = t_scale * ((a - a_0) + (b - b_0)) / 2: every rounding is then relative to the ray's extent, not to its distance
+// from the origin, and so are the products m W and the sums M whose difference the loss is.
+__device__ __forceinline__ float distortion_mid(float a, float b, float a0, float b0, float t_scale)
+{
+#pragma clang fp contract(off)
+    return t_scale * (((a - a0) + (b - b0)) * 0.5f);
+}
+
+// the exclusive prefix / suffix of an inclusive wave scan: the neighbour lane's value, never `incl - v`
+__device__ __forceinline__ float wave_exclusive_from(float incl, int lane)
+{
+    const float e = __shfl_up(incl, 1, 64);
+    return lane == 0 ? 0.f : e;
+}
+
+__device__ __forceinline__ float wave_exclusive_from_rev(float incl, int lane)
+{
+    const float e = __shfl_down(incl, 1, 64);
+    return lane == 63 ? 0.f : e;
+}
+
+// Forward: one walk from the ray's first sample to its last.  Per 64-sample group two inclusive wave scans (w, w * m) with scalar
+// carries give W_<i and M_<i; every lane adds its samples' terms 2 w (m W_< - M_<) + w^2 delta / 3 and one wave reduction ends the
+// ray.  The carries behind the last group are (W_tot, M_tot).  Each of t_starts, t_ends, weights is read once (12 bytes per sample,
+// and the ray's first interval once more); 4 (+ 8) bytes are written per ray.
+__global__ __launch_bounds__(256) void distortion_fwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                             const float *__restrict__ weights, const int64_t *__restrict__ packed,
+                                                             int n_rays, float t_scale, float *__restrict__ out_loss,
+                                                             float *__restrict__ out_totals)
+{
+#pragma clang fp contract(off)
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
+    float carry_w = 0.f, carry_m = 0.f, acc = 0.f;
+    if (cnt > 0) {
+        const float a0 = ts[s0], b0 = te[s0];
+        for (int64_t base = 0; base < cnt; base += 64) {
+            const int64_t i = s0 + base + lane;
+            const bool valid = base + lane < cnt;
+            float a = a0, b = b0, w = 0.f;
+            if (valid) { a = ts[i]; b = te[i]; w = weights[i]; }
+            const float m = distortion_mid(a, b, a0, b0, t_scale);
+            const float wm = w * m;
+            const float incl_w = lse::wave_inclusive_sum(w), incl_m = lse::wave_inclusive_sum(wm);
+            const float w_lt = wave_exclusive_from(incl_w, lane) + carry_w;      // W_<i
+            const float m_lt = wave_exclusive_from(incl_m, lane) + carry_m;      // M_<i
+            const float delta = t_scale * (b - a);
+            acc = acc + ((2.f * w) * (m * w_lt - m_lt) + (w * w) * delta * (1.f / 3.f));      // (an invalid lane has w = 0)
+            carry_w = carry_w + __shfl(incl_w, 63, 64);
+            carry_m = carry_m + __shfl(incl_m, 63, 64);
+        }
+        acc = lse::wave_sum(acc);
+    }
+    if (lane == 0) {
+        out_loss[ray] = acc;
+        if (out_totals) { out_totals[2 * ray] = carry_w; out_totals[2 * ray + 1] = carry_m; }
+    }
+}
+
+// Backward: one walk from the ray's last sample to its first.  The suffix scans of w and w * m give W_>i and M_>i; with the
+// forward's totals W_<i = W_tot - W_>i - w_i and M_<i = M_tot - M_>i - w_i m_i, so
+//     dw_i = g (2 [m_i (W_<i - W_>i) - (M_<i - M_>i)] + (2/3) w_i delta_i)
+// is complete on the lane that holds sample i, and the same walk is the recurrence of volrend_bwd_kernel,
+//     d_sigma_k = dt_k (dw_k (T_end + W_>k) - sum_{i>k} dw_i w_i),
+// with W_>k shared and a third suffix scan for dw w.  (The subtraction from the totals is harmless where it cancels: W_<i and M_<i
+// are small at the ray's start, where m_i is small too, and the error is an ulp of the total against a dw of the total's size.)
+// T_end is another matter.  1 - W_tot is 0 or +-2^-24 on an opaque ray, by the last bits of the forward's expf, and here dw is not
+// one value per ray as under a gradient on the accumulation: it grows with the distance from the ray's centre of mass, so behind a
+// surface dw_k 2^-24 dt_k stands against a true d_sigma of ~ 0 -- 2.3e-2 of the per-ray scale on long cone-step rays
+// (tests/test_distortion_cpu.py).  With `sigma` given, T_end = exp(-sum sigma dt) from a pass over the densities in front of the
+// walk: a relative error, and every term of the recurrence is then as accurate as the weights are.
+// Reads: weights once; t_starts and t_ends once, or twice with `sigma` (the second time out of the cache: a ray's intervals are
+// 8 KB at 1024 samples); sigma once or never; the first interval and the two totals once per ray -- 12 bytes per sample from
+// memory without sigma, 16 with it.  4 bytes are written per sample and output.
+__global__ __launch_bounds__(256) void distortion_bwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
+                                                             const float *__restrict__ sigma,
+                                                             const float *__restrict__ weights, const int64_t *__restrict__ packed,
+                                                             int n_rays, float t_scale, const float *__restrict__ totals,
+                                                             const float *__restrict__ g_loss, int g_stride,
+                                                             float *__restrict__ d_weights, float *__restrict__ d_sigma)
+{
+#pragma clang fp contract(off)
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t s0 = packed[2 * ray], cnt = packed[2 * ray + 1];
+    if (cnt == 0) return;
+    const float g = g_loss[(int64_t)ray * g_stride];
+    const float w_tot = totals[2 * ray], m_tot = totals[2 * ray + 1];
+    float t_end = 1.f - w_tot;
+    if (sigma && d_sigma) {
+        float tau = 0.f;
+        for (int64_t base = 0; base < cnt; base += 64) {
+            const int64_t i = s0 + base + lane;
+            if (base + lane < cnt) tau = tau + sigma[i] * (te[i] - ts[i]);
+        }
+        t_end = expf(-lse::wave_sum(tau));
+    }
+    const float a0 = ts[s0], b0 = te[s0];
+    float carry_w = 0.f, carry_m = 0.f, carry_g = 0.f;
+    const int64_t n_chunks = (cnt + 63) / 64;
+    for (int64_t ch = n_chunks - 1; ch >= 0; --ch) {
+        const int64_t base = ch * 64;
+        const int64_t i = s0 + base + lane;
+        const bool valid = base + lane < cnt;
+        float a = a0, b = b0, w = 0.f;
+        if (valid) { a = ts[i]; b = te[i]; w = weights[i]; }
+        const float m = distortion_mid(a, b, a0, b0, t_scale);
+        const float wm = w * m;
+        const float incl_w = wave_inclusive_sum_rev(w), incl_m = wave_inclusive_sum_rev(wm);
+        const float w_gt = wave_exclusive_from_rev(incl_w, lane) + carry_w;      // W_>i
+        const float m_gt = wave_exclusive_from_rev(incl_m, lane) + carry_m;      // M_>i
+        const float w_lt = (w_tot - w_gt) - w, m_lt = (m_tot - m_gt) - wm;
+        const float delta = t_scale * (b - a);
+        const float dw = g * (2.f * (m * (w_lt - w_gt) - (m_lt - m_gt)) + (2.f / 3.f) * w * delta);
+        if (valid && d_weights) d_weights[i] = dw;
+        carry_w = carry_w + __shfl(incl_w, 0, 64);
+        carry_m = carry_m + __shfl(incl_m, 0, 64);
+        if (d_sigma) {                       // (the same on every lane)
+            const float gw = valid ? dw * w : 0.f;
+            const float incl_g = wave_inclusive_sum_rev(gw);
+            const float sg = wave_exclusive_from_rev(incl_g, lane) + carry_g;    // sum_{i>k} dw_i w_i
+            if (valid) d_sigma[i] = (dw * (t_end + w_gt) - sg) * (b - a);
+            carry_g = carry_g + __shfl(incl_g, 0, 64);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void visibility_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                          const float *__restrict__ sigma,
                                                          const int64_t *__restrict__ packed, int n_rays, float eps,
@@ -954,6 +1086,33 @@ extern "C" int lse_volrend_bwd(const float *t_starts, const float *t_ends, const
                        sigmas, rgb, rgb_stride, packed_info, n_rays, weights, d_out_rgb, d_out_acc, d_out_depth_num,
                        d_sigmas, d_rgb, (const float *)nullptr);
     return lse::check_launch("lse_volrend_bwd");
+}
+
+extern "C" int lse_distortion_fwd(const float *t_starts, const float *t_ends, const float *weights, const int64_t *packed_info,
+                                  int32_t n_rays, float t_scale, float *out_loss, float *out_totals, lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_distortion_fwd: n_rays < 0");
+    LSE_REQUIRE(t_scale >= 0.f && t_scale < INFINITY, "lse_distortion_fwd: t_scale %g is negative or not finite", (double)t_scale);
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(t_starts && t_ends && weights && packed_info && out_loss, "lse_distortion_fwd: null pointer");
+    hipLaunchKernelGGL(distortion_fwd_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), t_starts, t_ends, weights,
+                       packed_info, n_rays, t_scale, out_loss, out_totals);
+    return lse::check_launch("lse_distortion_fwd");
+}
+
+extern "C" int lse_distortion_bwd(const float *t_starts, const float *t_ends, const float *sigmas, const float *weights,
+                                  const int64_t *packed_info, int32_t n_rays, float t_scale, const float *totals, const float *g_loss,
+                                  int32_t g_stride, float *d_weights, float *d_sigmas, lse_stream_t stream)
+{
+    LSE_REQUIRE(n_rays >= 0, "lse_distortion_bwd: n_rays < 0");
+    LSE_REQUIRE(t_scale >= 0.f && t_scale < INFINITY, "lse_distortion_bwd: t_scale %g is negative or not finite", (double)t_scale);
+    LSE_REQUIRE(g_stride == 0 || g_stride == 1, "lse_distortion_bwd: g_stride %d is neither 0 nor 1", g_stride);
+    if (n_rays == 0) return LSE_OK;
+    LSE_REQUIRE(t_starts && t_ends && weights && packed_info && totals && g_loss, "lse_distortion_bwd: null pointer");
+    LSE_REQUIRE(d_weights || d_sigmas, "lse_distortion_bwd: null pointer (neither d_weights nor d_sigmas)");
+    hipLaunchKernelGGL(distortion_bwd_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, lse::as_stream(stream), t_starts, t_ends, sigmas,
+                       weights, packed_info, n_rays, t_scale, totals, g_loss, g_stride, d_weights, d_sigmas);
+    return lse::check_launch("lse_distortion_bwd");
 }
 
 extern "C" int lse_visibility_mask(const float *t_starts, const float *t_ends, const float *sigmas,

@@ -117,6 +117,21 @@ class LSENeRFModelConfig:
     # the quantile depth is the exact crossing inside the sample under piecewise-constant density, a + (tau_q - tau_front) / sigma
     # clamped to the sample, instead of the sample's mid-point
     eval_depth_interpolate: bool = False
+    # --- distortion loss of mip-NeRF 360 in the training step (nerfacc.losses.distortion; the reference has none, so 0 = off: no
+    # loss key, no launch, every value as without these two fields).  With a multiplier > 0 a training-mode ``render_packed`` adds
+    # outputs["distortion"] [R, 1] -- per ray sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 delta_i over the render weights and the
+    # interval mid-points (include/lse_hip.h: lse_distortion_fwd) -- and ``train_step_bundles`` adds
+    # loss_dict["distortion_loss"] = mult * its mean over all packed rays (colour, previous and next).  Two launches per step, one
+    # forward and one backward that goes straight to d_sigma; both replay inside ``GraphedTrainStep``.  Not computed in eval mode,
+    # nor while ``freeze_field`` is in effect (regularising a frozen field would only push the cameras around).  Negative or
+    # non-finite values are a ValueError in ``populate_modules``.  Measured on one MI355X (tools/bench_distortion.py, the bench
+    # workload of 4096 rays x 1024 samples, profiles/distortion_loss.txt): lse_distortion_fwd 0.018 ms against lse_volrend_fwd's
+    # 0.029 ms, lse_distortion_bwd 0.036 ms against lse_volrend_bwd's 0.042 ms; the captured step 5.40 .. 5.42 ms with the
+    # multiplier at 0.01 against 5.33 ms at 0 (+0.07 .. 0.10 ms, 1.3 .. 1.8 %).  What the term does to a trained scene, and at which multiplier, is not measured:
+    # no scene ships with the repository (nerfstudio's nerfacto uses 0.002 on normalised distances).
+    distortion_loss_mult: float = 0.0
+    # the loss is taken on t_scale * t: it scales as t_scale (1 / the scene's extent along a ray makes it independent of the units)
+    distortion_t_scale: float = 1.0
 
     def __post_init__(self):   # R:lse_nerf/lsenerf.py:86-99
         if self.evs_mapping_method is None or str(self.evs_mapping_method).lower() == "none":
@@ -445,6 +460,10 @@ class LSENeRFModel(nn.Module):
             raise ValueError("eval_normals is not built for the early-stop segment route: set eval_early_stop_eps = 0 "
                              f"(got eval_normals={cfg.eval_normals!r}, eval_early_stop_eps={cfg.eval_early_stop_eps})")
         evaluation.depth_quantile_settings(cfg)
+        for name in ("distortion_loss_mult", "distortion_t_scale"):
+            v = getattr(cfg, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= v < float("inf")):
+                raise ValueError(f"{name} {v!r}: a finite number >= 0")
         scene_contraction = None if cfg.disable_scene_contraction else SceneContraction(order=float("inf"))
         self.field = LSEField(aabb=self.scene_aabb_2x3, num_images=self.num_train_data,
                               log2_hashmap_size=cfg.log2_hashmap_size, max_res=cfg.max_res,
@@ -758,10 +777,16 @@ class LSENeRFModel(nn.Module):
         if not (self.training or linear):
             rgb = torch.clamp(rgb, 0.0, 1.0)
         out = {"rgb": rgb, "accumulation": acc[:, None], "depth": depth[:, None], "num_samples_per_ray": packed_info[:, 1]}
+        if self.distortion_on():
+            out["distortion"] = ops.distortion_loss(t_starts, t_ends, sigma, weights, packed_info, self.config.distortion_t_scale)[:, None]
         if feats is not None:
             out["normals"] = torch.empty((num_rays, 3), dtype=torch.float32, device=rays_o.device)
             self.composite_normals(feats["x01"], feats["y"], t_starts, t_ends, sigma, packed_info, rays_o, rays_d, out["normals"], n_dev)
         return out
+
+    def distortion_on(self) -> bool:
+        """Whether this render carries "distortion": ``config.distortion_loss_mult`` > 0, training mode, and the field not frozen."""
+        return self.config.distortion_loss_mult > 0 and self.training and self.__dict__.get("_frozen_flags") is None
 
     def eval_normals_on(self) -> bool:
         """Whether this render carries "normals": ``config.eval_normals`` is on and the model is in eval mode."""
@@ -919,6 +944,9 @@ class LSENeRFModel(nn.Module):
             out_dict[k] = {key: val[lo:hi] for key, val in raw.items()}
             lo = hi
         loss_dict = self.fused_loss_dict(out_dict, batch, packed_rgb=raw["rgb"])
+        if "distortion" in raw:        # (distortion_on: one term over all rays of the packed pass, whichever route the other two took)
+            # mult * mean, as a sum: its backward hands lse_distortion_bwd ONE broadcast scalar (g_stride 0), no [R] gradient is formed
+            loss_dict["distortion_loss"] = raw["distortion"].sum() * (self.config.distortion_loss_mult / raw["distortion"].shape[0])
         metrics_dict: Dict[str, object] = {}
         if with_metrics and out_dict["col_out"] is not None:
             with torch.no_grad():

@@ -7,6 +7,7 @@ R:lse_nerf/lse_grid_estimator.py:120-138 run unchanged:
   * ``render_weight_from_density(t_starts, t_ends, sigmas, ...)``    R:lse_nerf/lsenerf.py:301-306
   * ``render_visibility_from_density`` / ``render_visibility_from_alpha``   R:lse_nerf/lse_grid_estimator.py:120-138
   * ``accumulate_along_rays``                                        (what nerfstudio's renderers call)
+  * ``distortion(weights, t_starts, t_ends, ...)``                   (``nerfacc.losses.distortion``; the reference does not call it)
 
 Samples must be ray-sorted (they are: the sampler emits them packed).  This is the generic composition route; the
 model's fast path (``LSENeRFModel.render_packed``) fuses weights + all three renderers into one kernel.
@@ -47,6 +48,15 @@ def render_weight_from_density(t_starts: Tensor, t_ends: Tensor, sigmas: Tensor,
     assert prefix_trans is None, "prefix_trans is not used by the reference and not implemented"
     return ops.render_weight_from_density(t_starts.reshape(-1), t_ends.reshape(-1), sigmas.reshape(-1),
                                           _packed(packed_info, ray_indices, n_rays))
+
+
+def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Optional[Tensor] = None,
+               n_rays: Optional[int] = None, packed_info: Optional[Tensor] = None) -> Tensor:
+    """``nerfacc.losses.distortion`` (the distortion loss of mip-NeRF 360), with nerfacc's argument order: per ray
+    ``sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 (t_end_i - t_start_i)`` over the interval mid-points ``m``, ``[n_rays]``,
+    differentiable with respect to ``weights``.  Samples are packed and ray-sorted with non-decreasing mid-points."""
+    return ops.distortion_from_weights(weights.reshape(-1), t_starts.reshape(-1), t_ends.reshape(-1),
+                                       _packed(packed_info, ray_indices, n_rays))
 
 
 @torch.no_grad()

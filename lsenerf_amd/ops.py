@@ -1341,6 +1341,85 @@ def render_weight_from_density(t_starts, t_ends, sigmas, packed_info):
     return _RenderWeightFn.apply(_c(t_starts), _c(t_ends), _c(sigmas), packed_info)
 
 
+def _distortion_t_scale(t_scale) -> float:
+    t_scale = float(t_scale)
+    if not (0.0 <= t_scale < float("inf")):
+        raise ValueError(f"distortion: t_scale {t_scale} is negative or not finite")
+    return t_scale
+
+
+def _distortion_fwd(t_starts, t_ends, weights, packed_info, t_scale: float):
+    """(loss [R], totals [R,2]) of lse_distortion_fwd."""
+    R = packed_info.shape[0]
+    loss = torch.empty(R, dtype=torch.float32, device=weights.device)
+    totals = torch.empty((R, 2), dtype=torch.float32, device=weights.device)
+    _lib.call("lse_distortion_fwd", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(weights, "weights"),
+              _chk(packed_info, torch.int64, "packed_info"), R, t_scale, ctypes.c_void_p(loss.data_ptr()),
+              ctypes.c_void_p(totals.data_ptr()), _stream())
+    return loss, totals
+
+
+def _distortion_bwd(t_starts, t_ends, sigmas, weights, packed_info, t_scale: float, totals, g):
+    """lse_distortion_bwd into a fresh d_sigmas buffer (``sigmas`` given: the densities the weights came from) or d_weights buffer
+    (None).  ``g``: the upstream gradient [R]; a broadcast one (what the backward of a sum hands over) goes to the kernel as the
+    single scalar it is."""
+    to_sigma = sigmas is not None
+    R = packed_info.shape[0]
+    stride = 1
+    if R > 0 and (g.numel() == 1 or g.stride(0) == 0):
+        g, stride = g.as_strided((1,), (1,)), 0
+    else:
+        g = _c(g)
+    out = torch.empty_like(weights)         # every sample a ray covers is written: no zero-fill (padding behind n_dev is never read)
+    ptr = ctypes.c_void_p(out.data_ptr())
+    _lib.call("lse_distortion_bwd", _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends"), _f32(sigmas, "sigmas", True), _f32(weights, "weights"),
+              _chk(packed_info, torch.int64, "packed_info"), R, t_scale, _f32(totals, "totals"), _f32(g, "g_loss"), stride,
+              None if to_sigma else ptr, ptr if to_sigma else None, _stream())
+    return out
+
+
+class _DistortionFn(torch.autograd.Function):
+    """Distortion loss per ray with its gradient sent to the densities (``to_sigma``: through render_weight_from_density inside
+    the backward kernel) or to the weights themselves."""
+
+    @staticmethod
+    def forward(ctx, t_starts, t_ends, diff, weights, packed_info, t_scale: float, to_sigma: bool):
+        loss, totals = _distortion_fwd(t_starts, t_ends, weights, packed_info, t_scale)
+        ctx.save_for_backward(t_starts, t_ends, diff if to_sigma else None, weights, packed_info, totals)
+        ctx.t_scale = t_scale
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        t_starts, t_ends, sigmas, weights, packed_info, totals = ctx.saved_tensors
+        d = _distortion_bwd(t_starts, t_ends, sigmas, weights, packed_info, ctx.t_scale, totals, g)
+        return None, None, d, None, None, None, None
+
+
+def distortion_loss(t_starts, t_ends, sigmas, weights, packed_info, t_scale: float = 1.0):
+    """Distortion loss of mip-NeRF 360 per ray, [R] (include/lse_hip.h: lse_distortion_fwd), differentiable with respect to
+    ``sigmas`` only.  ``weights``: the non-differentiable fourth output of ``volume_render`` / ``volume_render_depth`` on the same
+    samples; the backward is ONE launch that goes from the loss straight to d_sigma (lse_distortion_bwd), and autograd adds it
+    to the d_sigma of the render (it reads ``sigmas`` for the transmittance behind the ray, exp(-sum sigma dt): 1 - sum w is
+    0 or +-2^-24 on an opaque ray).  The interval ends are not differentiated.  Sample arrays may have capacity extent."""
+    t_scale = _distortion_t_scale(t_scale)
+    if t_starts.shape[0] == 0:
+        return torch.zeros(packed_info.shape[0], dtype=torch.float32, device=sigmas.device)
+    if sigmas.shape != weights.shape:
+        raise ValueError(f"distortion_loss: sigmas {tuple(sigmas.shape)} and weights {tuple(weights.shape)} differ in shape")
+    return _DistortionFn.apply(_c(t_starts), _c(t_ends), _c(sigmas), _c(weights.detach()), packed_info, t_scale, True)
+
+
+def distortion_from_weights(weights, t_starts, t_ends, packed_info, t_scale: float = 1.0):
+    """The same loss per ray, [R], differentiable with respect to ``weights`` (the generic route: the weights come from
+    ``render_weight_from_density`` and the caller composites with them).  Zero samples: zeros, no launch."""
+    t_scale = _distortion_t_scale(t_scale)
+    if t_starts.shape[0] == 0:
+        return torch.zeros(packed_info.shape[0], dtype=torch.float32, device=weights.device)
+    w = _c(weights)
+    return _DistortionFn.apply(_c(t_starts), _c(t_ends), w, w.detach(), packed_info, t_scale, False)
+
+
 def _rgb_ptr(rgb):
     if rgb is None:
         return None
