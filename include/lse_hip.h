@@ -548,17 +548,20 @@ int lse_image_metrics(const float *preds, const float *target, int32_t B, int32_
  *      [H * W, 3] f32 the rendered image.  Writes the contiguous [3, H, W] f32 planes gt_planes = value * msk and pred_planes =
  *      rgb * msk (no multiplication without a mask): R:lse_nerf/lsenerf.py:477-530's `image * msk` / `rgb * msk` after moveaxis.
  *      flags & LSE_PREP_EVENT_STATS: also the moments of the event-only metric (R:lse_nerf/lse_pipeline.py:149-164 over
- *      R:lse_nerf/utils.py:99-135) into `stats`: per pixel y = logf(gray + 1e-6f), gray = (0.2989 r + 0.5870 g) + 0.1140 b of the
- *      MASKED ground truth, and x = logf((r + g) + 1e-6f) of the UNMASKED prediction (the reference zeroes blue and sums the
- *      channels of the image dictionary's halves, of which only the ground truth is masked); per workgroup the sums of x, x^2, y,
- *      x y in double, in a fixed order, no atomics.  stats: lse_log_scale_correct_workspace bytes, 8-byte aligned.
+ *      R:lse_nerf/utils.py:99-135) into `stats`: per pixel y = log(gray + 1e-6), gray = (0.2989 r + 0.5870 g) + 0.1140 b of the
+ *      MASKED ground truth, and x = log((r + g) + 1e-6) of the UNMASKED prediction (the reference zeroes blue and sums the
+ *      channels of the image dictionary's halves, of which only the ground truth is masked), sums and logarithms in double from
+ *      the f32 pixels (the reference's are f32: with a prediction whose spread is 1e-3 of its level, f32 logarithms alone move the
+ *      fitted slope by 5e-3); per workgroup the sums of x, x^2, y, x y in double, in a fixed order, no atomics.  stats:
+ *      lse_log_scale_correct_workspace bytes, 8-byte aligned.
  *   lse_log_scale_correct: one launch.  Sums the partials in a fixed order and solves the normal equations of y ~ a x + b in double,
  *      N = H * W: det = N Sxx - Sx^2, a = (N Sxy - Sx Sy) / det, b = (Sxx Sy - Sx Sxy) / det.  A NaN a or b becomes 5/255 (the
  *      reference's rule); a det that is not finite, or zero to within the rounding of its two terms (|det| <= 2^-40 N Sxx), counts
  *      as NaN for both -- there the reference's torch.linalg.inv raises, or inverts rounding noise.  Writes coef[2] = (a, b) as
  *      f32, corrected[H * W] = expf((float)(a x + b)) and gray[H * W] (the grey masked ground truth): two [1, H, W] planes for
  *      lse_image_metrics with C = 1 (the reference feeds three identical channels, whose mean over C is this one's value).
- *      x and gray are recomputed from gt_planes / rgb with the arithmetic of the prep launch.  Two calls are bit-identical. */
+ *      x is recomputed from rgb with the arithmetic of the prep launch; the gray PLANE is f32 with single roundings.  Two calls
+ *      are bit-identical. */
 #define LSE_PREP_EVENT_STATS 1
 int lse_eval_image_prep(const void *gt, int32_t gt_type, const void *msk, int32_t msk_type, const float *rgb, int32_t H, int32_t W,
                         int32_t flags, float *gt_planes, float *pred_planes, void *stats, int64_t stats_bytes, lse_stream_t stream);

@@ -15,12 +15,15 @@
 // In front of them, for a whole eval set (lsenerf_amd/eval_set.py):
 //   eval_prep_kernel: one launch per image -- resident ground truth (uint8 / 255.0f, a division, or f32) and rendered rgb, times the
 //      optional mask, as the two [3, H, W] planes above; optionally the per-workgroup double sums of x, x^2, y, x y of the event-only
-//      metric (R:lse_nerf/lse_pipeline.py:149-164): y = logf(gray(masked gt) + 1e-6f), x = logf((pred_r + pred_g) + 1e-6f) of the
-//      UNMASKED prediction -- the reference passes the image dictionary's halves, of which only the ground truth is masked;
+//      metric (R:lse_nerf/lse_pipeline.py:149-164): y = log(gray(masked gt) + 1e-6), x = log((pred_r + pred_g) + 1e-6) of the
+//      UNMASKED prediction, both formed in double from the float32 pixels (below) -- the reference passes the image dictionary's halves, of which only the ground truth is masked;
 //   log_scale_correct_kernel: the reference's correct_img_scale / solve_normal_equations (R:lse_nerf/utils.py:109-135) -- every
 //      workgroup sums the partials in the same order, solves y ~ a x + b in double (NaN -> 5/255; a singular system, where the
 //      reference's torch.linalg.inv raises, counts as NaN) and writes expf(a x + b) and the grey ground truth as [1, H, W] planes.
-// logf / expf are the accurate library functions; the grey sum is written with single roundings (no contraction).
+// The fit's x and y are double logarithms of double sums: the reference takes them in float32, and where the prediction's spread is
+// small against its level (1e-3 of it) float32 logarithms alone move the slope of the exact fit by 5e-3 (the reference's own float32
+// normal equations: by 2).  In double the result is the float64 least-squares fit of the float32 images whatever the conditioning.
+// expf is the accurate library function; the grey PLANE is float32, its sum written with single roundings (no contraction).
 #include "common.h"
 
 namespace {
@@ -196,9 +199,15 @@ __global__ __launch_bounds__(kFinalThreads) void metrics_final_kernel(const doub
 constexpr int kPrepThreads = 256;
 
 // log of the prediction's R + G (its blue channel zeroed, then summed over the channels), unmasked
-__device__ __forceinline__ float log_pred(const float *__restrict__ rgb, int64_t p)
+__device__ __forceinline__ double log_pred(const float *__restrict__ rgb, int64_t p)
 {
-    return logf((rgb[3 * p] + rgb[3 * p + 1]) + 1e-6f);
+    return log(((double)rgb[3 * p] + (double)rgb[3 * p + 1]) + 1e-6);
+}
+
+// log of the grey level of a (masked) ground-truth pixel
+__device__ __forceinline__ double log_gray(float r, float g, float b)
+{
+    return log((((double)r * 0.2989 + (double)g * 0.5870) + (double)b * 0.1140) + 1e-6);
 }
 
 // partials (doubles): [sum x G][sum x^2 G][sum y G][sum x y G]; part == nullptr: planes only
@@ -233,7 +242,7 @@ __global__ __launch_bounds__(kPrepThreads) void eval_prep_kernel(const void *__r
         }
         if (part != nullptr) {
             const double x = log_pred(rgb, p);
-            const double y = logf(gray3(v[0], v[1], v[2]) + 1e-6f);
+            const double y = log_gray(v[0], v[1], v[2]);
             acc[0] += x; acc[1] += x * x; acc[2] += y; acc[3] += x * y;
         }
     }
