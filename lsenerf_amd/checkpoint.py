@@ -48,6 +48,28 @@ def local_to_reference_key(key: str) -> str:
     return "_model." + key
 
 
+# the data manager's camera optimisers (R:lse_nerf/lse_datamanager.py:297: ``col_train_camera_optimizer`` / ``evs_train_camera_optimizer``;
+# one shared spline is registered under both names and so saved twice)
+CAMERA_SETS = ("col", "evs")
+_CAMERA_RE = re.compile(r"^datamanager\.(col|evs)_train_camera_optimizer\.(.+)$")
+
+
+def camera_key_to_local(key: str) -> Optional[Tuple[str, str]]:
+    """Pipeline key of one of the data manager's camera optimisers -> ``(set, name)``: ``set`` is "col" or "evs", ``name`` the key
+    in that module's own state dict (``pose_adjustment``, ``ctrl_tangents``, ``scale``, ``dM``, ``ctrl_ts``, ``orig_cam_ts``;
+    ``prev_optim.pose_adjustment`` / ``next_optim.pose_adjustment`` of a ``PrevNextCamOptimizer``).  None for every other key."""
+    if key.startswith("module."):
+        key = key[len("module."):]
+    m = _CAMERA_RE.match(key)
+    return (m.group(1), m.group(2)) if m else None
+
+
+def local_to_camera_key(which: str, name: str) -> str:
+    if which not in CAMERA_SETS:
+        raise ValueError(f"camera optimisers are saved as {CAMERA_SETS}, got {which!r}")
+    return f"datamanager.{which}_train_camera_optimizer.{name}"
+
+
 def checkpoint_path(directory: str, step: int) -> str:
     return os.path.join(directory, f"step-{step:09d}.ckpt")
 
@@ -131,13 +153,24 @@ def reference_optimizer_index_map(pipeline_state: Dict[str, torch.Tensor], model
 
 def load_nerfstudio_checkpoint(path: str, model: torch.nn.Module, load_step: Optional[int] = None,
                                drop_camera_optimizer: bool = False,
-                               optimizers: Optional[Dict[str, object]] = None) -> Dict[str, object]:
+                               optimizers: Optional[Dict[str, object]] = None,
+                               camera_optimizers: Optional[Dict[str, torch.nn.Module]] = None) -> Dict[str, object]:
     """Load a reference checkpoint into ``model`` (and, when given, the optimizer states by param-group name into
-    objects with ``load_state_dict`` -- e.g. ``{"fields": FlatAdam}`` -- so that training resumes with its Adam moments
-    and learning-rate schedule position).  ``path`` is a ``.ckpt`` file or a ``nerfstudio_models`` directory
-    (then ``load_step`` or the latest step is taken).  ``drop_camera_optimizer`` mirrors the reference's eval mode
-    (R:lse_nerf/lse_trainer.py:68-82).  Returns {"step", "missing", "unexpected", "dropped"}; like the reference's
-    ``strict=False`` load nothing is raised for missing / unexpected names, but shape mismatches are errors."""
+    objects with ``load_state_dict`` -- e.g. ``{"fields": FlatAdam, "camera_opt": FlatAdam}`` -- so that training resumes
+    with its Adam moments and learning-rate schedule position).  ``path`` is a ``.ckpt`` file or a ``nerfstudio_models``
+    directory (then ``load_step`` or the latest step is taken).
+    ``camera_optimizers = {"col": module, "evs": module}`` (either may be absent): the data manager's camera optimisers
+    (``CameraOptimizer``, ``PrevNextCamOptimizer``, ``SplineCameraOptimizer``), which live outside the model; the file's
+    ``datamanager.{col,evs}_train_camera_optimizer.*`` entries are copied into them IN PLACE (parameters that ``FlatParams``
+    re-pointed stay views of their flat buffer).  One spline shared by both camera sets is stored under both names
+    (R:lse_nerf/lse_datamanager.py:297); pass the one module under both keys, or under either.  Entries of a set no module was
+    given for are listed in "dropped", and so are all of them under ``drop_camera_optimizer``, which mirrors the reference's
+    eval mode (R:lse_nerf/lse_trainer.py:68-82; the reference restores them on resume, :104,117-118); the "camera_opt"
+    entry of ``optimizers`` is then skipped as well.
+    Returns {"step", "missing", "unexpected", "dropped"} (camera entries by their pipeline keys); like the reference's
+    ``strict=False`` load nothing is raised for missing / unexpected names, but shape mismatches are errors.
+    What the file does not carry: the composer's draw position -- training continues at ``step + 1``
+    (R:lse_nerf/lse_trainer.py:98), ``BatchComposer.set_step(step + 1)`` -- and the jitter stream (INTEGRATION.md "checkpoint")."""
     if os.path.isdir(path):
         step = latest_step(path) if load_step is None else int(load_step)
         path = checkpoint_path(path, step)
@@ -155,13 +188,37 @@ def load_nerfstudio_checkpoint(path: str, model: torch.nn.Module, load_step: Opt
     for k, v in state.items():
         if k in own and tuple(own[k].shape) != tuple(v.shape):
             raise ValueError(f"shape mismatch for {k}: checkpoint {tuple(v.shape)} vs model {tuple(own[k].shape)}")
+    # the data manager's camera optimisers: taken back out of `dropped` for the sets a module was given for
+    camera_state: Dict[str, Dict[str, torch.Tensor]] = {}
+    modules = {} if drop_camera_optimizer else dict(camera_optimizers or {})
+    for which in modules:
+        if which not in CAMERA_SETS:
+            raise ValueError(f"camera_optimizers takes the keys {CAMERA_SETS}, got {which!r}")
+    for k in list(dropped):
+        ck = camera_key_to_local(k)
+        if ck is not None and ck[0] in modules:
+            camera_state.setdefault(ck[0], {})[ck[1]] = loaded["pipeline"][k]
+            dropped.remove(k)
+    for which, sub in camera_state.items():
+        own_cam = modules[which].state_dict()
+        for k, v in sub.items():
+            if k in own_cam and tuple(own_cam[k].shape) != tuple(v.shape):
+                raise ValueError(f"shape mismatch for {local_to_camera_key(which, k)}: checkpoint {tuple(v.shape)} vs module "
+                                 f"{tuple(own_cam[k].shape)}")
     res = model.load_state_dict(state, strict=False)
+    missing, unexpected = list(res.missing_keys), list(res.unexpected_keys)
+    for which, mod in modules.items():    # (a shared spline given under both names is written twice, with the same numbers)
+        r = mod.load_state_dict(camera_state.get(which, {}), strict=False)
+        missing += [local_to_camera_key(which, k) for k in r.missing_keys]
+        unexpected += [local_to_camera_key(which, k) for k in r.unexpected_keys]
     # the estimator caches a host copy of occs.mean(); a loaded grid invalidates it
     for mod in model.modules():
         if hasattr(mod, "_occ_mean_host"):
             mod._occ_mean_host = None
     if optimizers:   # resume: Adam moments + step count (the lr schedule continues from there)
         for name, o in optimizers.items():
+            if drop_camera_optimizer and name == "camera_opt":      # (R:lse_nerf/lse_trainer.py:81-82)
+                continue
             if name in loaded.get("optimizers", {}):
                 sd = loaded["optimizers"][name]
                 flat = getattr(o, "flat", None)
@@ -171,17 +228,23 @@ def load_nerfstudio_checkpoint(path: str, model: torch.nn.Module, load_step: Opt
                     o.load_state_dict(sd, index_map=imap, names=names)
                 else:
                     o.load_state_dict(sd)
-    return {"step": int(loaded["step"]), "missing": list(res.missing_keys), "unexpected": list(res.unexpected_keys),
-            "dropped": list(dropped)}
+    return {"step": int(loaded["step"]), "missing": missing, "unexpected": unexpected, "dropped": list(dropped)}
 
 
 def save_nerfstudio_checkpoint(directory: str, model: torch.nn.Module, step: int,
-                               optimizers: Optional[Dict[str, object]] = None, keep_only_latest: bool = False) -> str:
+                               optimizers: Optional[Dict[str, object]] = None, keep_only_latest: bool = False,
+                               camera_optimizers: Optional[Dict[str, torch.nn.Module]] = None) -> str:
     """Write ``step-%09d.ckpt`` with the reference's layout and key names, so that R:lse_nerf/lse_trainer.py:85-122 can
-    read it.  ``optimizers`` maps a param-group name ("fields", "camera_opt") to an object with ``state_dict()`` or to a
-    plain dict of tensors."""
+    read it.  ``step`` is the last step TAKEN (the reference resumes at ``step + 1``, :98).  ``optimizers`` maps a param-group
+    name ("fields", "camera_opt") to an object with ``state_dict()`` or to a plain dict of tensors.  ``camera_optimizers =
+    {"col": module, "evs": module}``: the data manager's camera optimisers, written as
+    ``datamanager.{col,evs}_train_camera_optimizer.<name>`` (one shared spline goes under both keys, as the reference
+    stores it).  Without it a resumed run starts its camera poses from zero around a field trained with the moved ones."""
     os.makedirs(directory, exist_ok=True)
     pipeline = {local_to_reference_key(k): v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    for which, mod in (camera_optimizers or {}).items():
+        for k, v in mod.state_dict().items():
+            pipeline[local_to_camera_key(which, k)] = v.detach().cpu().clone()
     opt_state = {}
     for name, o in (optimizers or {}).items():
         if hasattr(o, "state_dict"):

@@ -359,6 +359,19 @@ class BatchComposer:
                                  metadata={k: fixed[k] for k in ("directions_norm", "appearance_id", "cam_type", "coords")}))
         return tuple(out)
 
+    # -- the draw position
+    @torch.no_grad()
+    def set_step(self, step: int) -> None:
+        """Set the draw position: the next ``compose()`` -- eager, or the replay of a step captured with ``composer=`` -- draws what
+        ``indices_host(step)`` lists, the one after it ``step + 1``.  A fill of ``step_dev`` in stream order (no synchronisation,
+        like ``FlatAdam.prepare_step``): replays queued earlier keep their positions.  A checkpoint does not carry the position;
+        a run resumed from one written after step ``s`` continues with ``set_step(s + 1)``, before or after the step is captured
+        (a capture puts back the position it found)."""
+        step = int(step)
+        if not 0 <= step < 2 ** 63:
+            raise ValueError(f"the draw position is a step number, got {step}")
+        self.step_dev.fill_(step)
+
     # -- poses
     @torch.no_grad()
     def set_poses(self, col: Optional[Tensor] = None, prev: Optional[Tensor] = None, nxt: Optional[Tensor] = None) -> None:

@@ -189,3 +189,162 @@ def test_reference_written_optimizer_state_is_matched_by_name_not_by_position(tm
     pipe2["_model.field.mlp_transient.tcnn_encoding.params"] = torch.zeros(5)
     with pytest.raises(ValueError, match="mlp_transient"):
         ck.reference_optimizer_index_map(pipe2, m, flat.params)
+
+
+# ---------------------------------------------------------------------------------------------------- camera optimisers of the data manager
+def _camera_modules(seed=4):
+    """A per-camera colour optimiser and a prev / next event optimiser away from zero."""
+    from lsenerf_amd import cameras as cam
+    g = torch.Generator().manual_seed(seed)
+    col = cam.CameraOptimizer(cam.CameraOptimizerConfig(mode="SE3"), 5)
+    evs = cam.CameraOptimizerConfig(mode="SO3xR3", optim_type="prevnext").setup(num_cameras=7)
+    with torch.no_grad():
+        for o in (col, evs.prev_optim, evs.next_optim):
+            o.pose_adjustment.copy_(torch.randn(o.pose_adjustment.shape, generator=g) * 0.05)
+    return col, evs
+
+
+def _spline(shift=0.0):
+    from tests.spline_fixtures import _synthetic_spline
+    return _synthetic_spline([[0.3 + shift, -0.2, 0.1, 0.0, 0.0, 0.3], [0.5, 0.1 - shift, -0.3, 0.0, 0.0, -0.3], [-0.4, 0.6, 0.2 + shift, 0.0, 0.0, 0.0]])
+
+
+def test_camera_key_mapping_both_ways():
+    from lsenerf_amd import checkpoint as ck
+    names = ("pose_adjustment", "ctrl_tangents", "scale", "dM", "ctrl_ts", "orig_cam_ts", "prev_optim.pose_adjustment")
+    for which in ("col", "evs"):
+        for name in names:
+            key = f"datamanager.{which}_train_camera_optimizer.{name}"
+            assert ck.local_to_camera_key(which, name) == key
+            assert ck.camera_key_to_local(key) == (which, name) and ck.camera_key_to_local("module." + key) == (which, name)
+            assert ck.reference_to_local_key(key) is None                 # no entry of the model
+    for other in ("datamanager.train_camera_optimizer.pose_adjustment", "_model.camera_optimizer.pose_adjustment",
+                  "datamanager.col_train_camera_optimizer", "_model.field.mlp_head.tcnn_encoding.params",
+                  "datamanager.col_eval_camera_optimizer.pose_adjustment"):
+        assert ck.camera_key_to_local(other) is None, other
+    with pytest.raises(ValueError):
+        ck.local_to_camera_key("train", "pose_adjustment")
+
+
+def test_reference_style_file_with_camera_optimizers_and_their_adam(tmp_path):
+    """What the reference writes in BASELINE config 4: DDP ``module.`` prefix, both ``datamanager.*_train_camera_optimizer`` entries
+    and a "camera_opt" optimizer group (torch.optim.Adam over the camera parameters).  A resumed run takes all of it
+    (R:lse_nerf/lse_trainer.py:104,117-118), an eval run none (:68-82)."""
+    from lsenerf_amd import checkpoint as ck
+    from lsenerf_amd.optim import FlatAdam, FlatParams
+    m = _model()
+    col, evs = _camera_modules()
+    cam_params = [col.pose_adjustment, evs.prev_optim.pose_adjustment, evs.next_optim.pose_adjustment]
+    g = torch.Generator().manual_seed(8)
+    pipe = {"module." + ck.local_to_reference_key(k): v.clone() for k, v in m.state_dict().items()}
+    for which, mod in (("col", col), ("evs", evs)):
+        for k, v in mod.state_dict().items():
+            pipe[f"module.datamanager.{which}_train_camera_optimizer.{k}"] = v.clone()
+    state = {i: {"step": torch.tensor(19.0), "exp_avg": torch.randn(p.shape, generator=g), "exp_avg_sq": torch.rand(p.shape, generator=g)}
+             for i, p in enumerate(cam_params)}
+    cam_sd = {"state": state, "param_groups": [{"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-15, "params": [0, 1, 2]}]}
+    f = str(tmp_path / "step-000000018.ckpt")
+    torch.save({"step": 18, "pipeline": pipe, "optimizers": {"camera_opt": cam_sd}, "scalers": {}}, f)
+
+    def fresh():
+        c, e = _camera_modules(seed=99)
+        flat = FlatParams([c.pose_adjustment, e.prev_optim.pose_adjustment, e.next_optim.pose_adjustment])   # FlatParams first
+        return c, e, FlatAdam(flat, lr=1e-3, eps=1e-15)
+    # resume
+    c, e, opt = fresh()
+    info = ck.load_nerfstudio_checkpoint(f, m, optimizers={"camera_opt": opt}, camera_optimizers={"col": c, "evs": e})
+    assert info["step"] == 18 and info["dropped"] == [] and info["missing"] == [] and info["unexpected"] == []
+    for got, want in zip((c.pose_adjustment, e.prev_optim.pose_adjustment, e.next_optim.pose_adjustment), cam_params):
+        assert torch.equal(got, want)
+    assert opt.step_count == 19
+    for i, (p, o) in enumerate(zip(opt.flat.params, opt.flat.offsets)):
+        assert p.data_ptr() == opt.flat.data.data_ptr() + 4 * o                     # loaded through the views
+        assert torch.equal(opt.flat.data[o:o + p.numel()].view(p.shape), cam_params[i])
+        assert torch.equal(opt.exp_avg[o:o + p.numel()].view(p.shape), state[i]["exp_avg"])
+        assert torch.equal(opt.exp_avg_sq[o:o + p.numel()].view(p.shape), state[i]["exp_avg_sq"])
+    # eval mode: neither the modules nor their Adam
+    c, e, opt = fresh()
+    before = opt.flat.data.clone()
+    info = ck.load_nerfstudio_checkpoint(f, m, drop_camera_optimizer=True, optimizers={"camera_opt": opt},
+                                         camera_optimizers={"col": c, "evs": e})
+    assert sorted(info["dropped"]) == sorted(k for k in pipe if "camera_optimizer" in k) and len(info["dropped"]) == 3
+    assert torch.equal(opt.flat.data, before) and opt.step_count == 0 and float(opt.exp_avg.abs().max()) == 0.0
+    # a module of another shape is refused loudly, like a model tensor
+    from lsenerf_amd import cameras as cam
+    with pytest.raises(ValueError, match="shape mismatch for datamanager.col_train_camera_optimizer.pose_adjustment"):
+        ck.load_nerfstudio_checkpoint(f, m, camera_optimizers={"col": cam.CameraOptimizer(cam.CameraOptimizerConfig(mode="SE3"), 6)})
+    with pytest.raises(ValueError, match="camera_optimizers takes the keys"):
+        ck.load_nerfstudio_checkpoint(f, m, camera_optimizers={"train": c})
+
+
+def test_camera_optimizers_round_trip_and_dropped_lists_what_no_module_took(tmp_path):
+    from lsenerf_amd import checkpoint as ck
+    m = _model()
+    col, evs = _camera_modules()
+    p = ck.save_nerfstudio_checkpoint(str(tmp_path), m, step=4, camera_optimizers={"col": col, "evs": evs})
+    saved = torch.load(p, weights_only=True)["pipeline"]
+    cam_keys = ["datamanager.col_train_camera_optimizer.pose_adjustment", "datamanager.evs_train_camera_optimizer.next_optim.pose_adjustment",
+                "datamanager.evs_train_camera_optimizer.prev_optim.pose_adjustment"]
+    assert sorted(k for k in saved if k.startswith("datamanager.")) == cam_keys
+    # no module given: every entry is reported, nothing is loaded
+    info = ck.load_nerfstudio_checkpoint(p, m)
+    assert sorted(info["dropped"]) == cam_keys
+    # one module given: the other set's entries are reported
+    c2, e2 = _camera_modules(seed=99)
+    info = ck.load_nerfstudio_checkpoint(p, m, camera_optimizers={"evs": e2})
+    assert info["dropped"] == cam_keys[:1]
+    assert torch.equal(e2.prev_optim.pose_adjustment, evs.prev_optim.pose_adjustment)
+    assert torch.equal(e2.next_optim.pose_adjustment, evs.next_optim.pose_adjustment)
+    assert not torch.equal(c2.pose_adjustment, col.pose_adjustment)
+    # a module the file has nothing for: its keys are missing, by their pipeline names
+    p2 = ck.save_nerfstudio_checkpoint(str(tmp_path / "b"), m, step=4, camera_optimizers={"evs": evs})
+    info = ck.load_nerfstudio_checkpoint(p2, m, camera_optimizers={"col": c2, "evs": e2})
+    assert info["missing"] == cam_keys[:1] and info["dropped"] == []
+
+
+def test_a_shared_spline_is_stored_under_both_names_and_loads_from_either(tmp_path):
+    """R:lse_nerf/lse_datamanager.py:297: with a spline the colour and the event set share ONE module, registered under both names,
+    so the file carries its tensors twice."""
+    from lsenerf_amd import checkpoint as ck
+    m = _model()
+    spl = _spline()
+    p = ck.save_nerfstudio_checkpoint(str(tmp_path), m, step=9, camera_optimizers={"col": spl, "evs": spl})
+    saved = torch.load(p, weights_only=True)["pipeline"]
+    names = ("ctrl_tangents", "scale", "dM", "ctrl_ts", "orig_cam_ts")
+    for name in names:
+        a, b = (saved[f"datamanager.{w}_train_camera_optimizer.{name}"] for w in ("col", "evs"))
+        assert torch.equal(a, b) and torch.equal(a, spl.state_dict()[name])
+    for given in ({"col": 0, "evs": 0}, {"col": 0}, {"evs": 0}):
+        other = _spline(shift=0.25)
+        with torch.no_grad():
+            other.scale.fill_(3.0)
+        assert not torch.equal(other.ctrl_tangents, spl.ctrl_tangents)
+        info = ck.load_nerfstudio_checkpoint(p, m, camera_optimizers={k: other for k in given})
+        assert info["missing"] == [] and info["unexpected"] == []
+        assert len(info["dropped"]) == (2 - len(given)) * len(names)
+        for name in names:
+            assert torch.equal(other.state_dict()[name], spl.state_dict()[name]), name
+
+
+def test_parameters_stay_views_of_the_flat_buffer_through_a_load(tmp_path):
+    """``FlatParams`` re-points every parameter's ``.data`` into one buffer; Adam and the captured step work on the buffer.  A load
+    must go THROUGH the views: afterwards every parameter still starts at its offset and the buffer holds the loaded numbers."""
+    from lsenerf_amd import checkpoint as ck
+    from lsenerf_amd.optim import FlatAdam, FlatParams
+    a, b = _model(), _model()
+    with torch.no_grad():
+        for p in a.parameters():
+            p.add_(torch.randn_like(p) * 0.1)
+    path = ck.save_nerfstudio_checkpoint(str(tmp_path), a, step=1)
+    flat = FlatParams(b.get_param_groups()["fields"])
+    opt = FlatAdam(flat)
+    before = flat.data.clone()
+    ck.load_nerfstudio_checkpoint(path, b, optimizers={"fields": opt})
+    assert not torch.equal(flat.data, before)
+    by_name = dict(a.named_parameters())
+    listed = [p for p in b.get_param_groups()["fields"] if p.requires_grad]
+    assert len(listed) == len(flat.params)
+    name_of = {id(p): n for n, p in b.named_parameters()}
+    for p, fp, o in zip(listed, flat.params, flat.offsets):
+        assert p is fp and p.data_ptr() == flat.data.data_ptr() + 4 * o and p.grad.data_ptr() == flat.grad.data_ptr() + 4 * o
+        assert torch.equal(flat.data[o:o + p.numel()].view(p.shape), by_name[name_of[id(p)]])
