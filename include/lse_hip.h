@@ -993,6 +993,34 @@ int lse_compose_rays_bwd(const lse_compose_desc *desc, const lse_compose_scene *
                          const float *d_origins, const float *d_directions, float *d_col_pose, float *d_prev_pose,
                          float *d_next_pose, lse_stream_t stream);
 
+/* ---- weighted pixel draw (csrc/pixel_draw.hip; ABI 6, additive): the composer's pixels by integer weight instead of uniformly ----
+ * Pixel x of image row r = c * H + y of one camera set has the integer weight
+ *   w(r, x) = 0                        where msk != NULL and (float)msk[r, x] == 0,
+ *             w_idle                   where images == NULL (a set whose pixels differ only by the mask: needs w_active == w_idle),
+ *             w_active or w_idle       by (float)images[r, x] != 0 or == 0 (-0.0f and a net-zero frame pixel are idle, NaN is active),
+ * with the float conversions of the composer's gather.  images: [n_images, H, W] of pix_type (one channel: event frames); msk:
+ * [n_images, H, W] of msk_type (LSE_PIX_U8 | LSE_PIX_F32), or NULL with LSE_PIX_NONE.  Weights lie in [0, 255], not both zero.
+ *   lse_pixel_rows_build  row_off int64 [rows + 1], rows = n_images * H: the exclusive prefix sums of the row sums, row_off[rows] =
+ *      the total weight.  One wave per row, then one block scans; once per scene (and again after the images or masks were edited).
+ *   lse_pixel_draw  pixel i < n at step s (*step_dev when step_dev != NULL, else `step`), all integers:
+ *        (w0, w1, ., .) = Philox4x32-10(counter (s & 0xffffffff, i, stream_id, 0), key (seed & 0xffffffff, seed >> 32))
+ *        t = mulhi64((w0 << 32) | w1, total)                       0 <= t < total
+ *        r = #{r' in [0, rows) : row_off[r'] <= t} - 1             v = t - row_off[r]
+ *        x = #{x' in [0, W) : sum_{j < x'} w(r, j) <= v} - 1       c = r / H,  y = r % H
+ *      writes indices[i] = (c, y, x) (int32 [n, 3], the col_indices_in / evs_indices_in of lse_compose_batch) and weights[i] =
+ *      w(r, x) (int32 [n]).  Rows and pixels of weight zero are never drawn, wherever they sit.  One wave per pixel: a 64-ary
+ *      search of row_off, then a walk of the row 64 pixels at a time.  No atomics, no LDS, no workspace; the grid depends on n only,
+ *      so the launch can be captured, and it reads *step_dev like lse_compose_batch: launch it in front of that call's advance.
+ *      A total of zero is the caller's to refuse (it is row_off[rows]); the kernel then still writes pixels inside the images.
+ * LSE_E_INVALID before any launch: a type code outside the lists above, n_images, H or W < 1, n_images * H > INT32_MAX, W >
+ * INT32_MAX / 255, a weight outside [0, 255] or both zero, images == NULL with unequal weights, n < 0, stream_id outside {0, 1},
+ * step < 0 without step_dev, a null or misaligned row_off, a null output.  n == 0: no launch. */
+int lse_pixel_rows_build(const void *images, int32_t pix_type, const void *msk, int32_t msk_type, int32_t n_images, int32_t H,
+                         int32_t W, int32_t w_active, int32_t w_idle, int64_t *row_off, lse_stream_t stream);
+int lse_pixel_draw(const void *images, int32_t pix_type, const void *msk, int32_t msk_type, int32_t n_images, int32_t H, int32_t W,
+                   int32_t w_active, int32_t w_idle, const int64_t *row_off, uint64_t seed, int32_t stream_id,
+                   const int64_t *step_dev, int64_t step, int32_t n, int32_t *indices, int32_t *weights, lse_stream_t stream);
+
 /* ---- whole-image rays of one camera (the eval set): the composer's ray arithmetic over a row-major pixel range -------------
  * Pixel p = first + i (y = p / W, x = p % W) of an H x W camera with the pose pose[3, 4] (device, f32; one row of a pose table)
  * writes row i of origins / directions [n, 3] and pixel_area / directions_norm [n]: the device functions of lse_compose_batch, so

@@ -224,6 +224,8 @@ SIGNATURES = {
     "lse_adam_schedule_dev": [P, P, P, P],
     "lse_compose_batch": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, I64, I32, P, P, P],
     "lse_compose_rays_bwd": [POINTER(ComposeDesc), POINTER(ComposeScene), POINTER(ComposeOut), P, P, P, P, P, P],
+    "lse_pixel_rows_build": [P, I32, P, I32, I32, I32, I32, I32, I32, P, P],
+    "lse_pixel_draw": [P, I32, P, I32, I32, I32, I32, I32, I32, P, c_uint64, I32, P, I64, I32, P, P, P],
     "lse_camera_rays": [POINTER(CameraDesc), P, I64, I64, P, P, P, P, P],
     "lse_tsdf_integrate": [P, P, I32, I32, I32, P, P, POINTER(CameraDesc), P, I32, P, P, P, F32, F32, I32, F32, P],
     "lse_tsdf_vertex_colors": [P, I32, I32, I32, P, P, P, I64, P, P, P],

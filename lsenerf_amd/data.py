@@ -14,6 +14,8 @@ Sampling convention (this package's own; the docs say so): pixel ``i`` of a stre
 ``c = mulhi32(w0, n_images)``, ``y = mulhi32(w1, H)``, ``x = mulhi32(w2, W)`` -- uniform i.i.d. over images x pixels like
 nerfstudio's ``floor(rand * [n, h, w])`` that ``EvPixelSampler`` inherits, with no bit parity to ``torch.rand``.
 ``draw_indices_host`` is the same integer arithmetic in numpy (exact), the twin the tests compare the device draw with.
+With ``sampling=PixelSampling(...)`` pixels are drawn by integer weight instead -- masked pixels never, event pixels by whether
+their frame value is non-zero -- by ``lse_pixel_draw`` in front of the compose launch (``PixelSampling``; opt-in).
 
 The composer reads poses from POSE TABLES in device memory (``pose_tables``), never from an optimiser: the helpers at the end of
 this module build the tables from what ``cameras.py`` has (plain ``camera_to_worlds``, ``CameraOptimizer``, the spline) as
@@ -27,6 +29,7 @@ The outputs of ``compose`` ARE the composer's static buffers (row blocks of one 
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -74,6 +77,102 @@ def draw_indices_host(seed: int, step: int, stream_id: int, n_pixels: int, n_ima
     w = philox4x32_10(ctr, (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)).astype(np.uint64)
     lim = np.array([n_images, height, width], dtype=np.uint64)
     return ((w[:, :3] * lim[None]) >> np.uint64(32)).astype(np.int64)
+
+
+@dataclass
+class PixelSampling:
+    """Weighted pixel sampling of a ``BatchComposer`` (``sampling=``; None, the default, is the uniform draw above).
+
+    Every pixel of a stream has an integer weight and is drawn with a probability proportional to it:
+      colour pixel   1, or 0 where ``respect_mask`` and the set's ``msk`` is 0
+      event pixel    ``evs_active_weight`` where the frame's value is != 0, ``evs_idle_weight`` where it is == 0, or 0 where
+                     ``respect_mask`` and the set's ``msk`` is 0
+    "Active" compares the STORED frame value, converted to float32 the way the gather converts it, with zero: ``-0.0`` is idle, a
+    pixel whose events cancelled to a net 0 is idle, NaN is active.  ``respect_mask`` does nothing for a set without ``msk``.  The
+    weights are integers in [0, 255], not both zero; a weight of 0 means such pixels are never drawn.
+
+    Unequal event weights CHANGE THE OBJECTIVE -- the loss becomes a weighted mean over the pixels, as with the negative sampling
+    of EventNeRF -- and so does a mask.  ``BatchComposer.draw_weights`` holds the weight of every drawn pixel: a caller who wants the
+    uniform objective back reweights each ray's loss by ``1 / weight`` (times ``sampling_totals / pixels`` for the same scale).
+
+    The draw (include/lse_hip.h, "weighted pixel draw"; integers only, ``BatchComposer.indices_host`` is its host twin): with
+    ``row_off`` the exclusive prefix sums of the image rows' summed weights, the Philox call of the uniform draw gives
+    ``t = mulhi64((w0 << 32) | w1, total)``, the row is the last ``r`` with ``row_off[r] <= t``, the pixel the last ``x`` of that row
+    whose exclusive prefix sum is ``<= t - row_off[r]``.  A stream takes this route whenever ``sampling`` is set, also where its
+    weights end up all equal: which pixels a step draws depends on the setting, never on the data."""
+    respect_mask: bool = True
+    evs_active_weight: int = 1
+    evs_idle_weight: int = 1
+
+    def __post_init__(self):
+        for name in ("evs_active_weight", "evs_idle_weight"):
+            w = getattr(self, name)
+            if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 0 <= int(w) <= 255:
+                raise ValueError(f"PixelSampling.{name} must be an integer in [0, 255], got {w!r}")
+            setattr(self, name, int(w))
+        if self.evs_active_weight == 0 and self.evs_idle_weight == 0:
+            raise ValueError("PixelSampling: evs_active_weight and evs_idle_weight are both zero")
+        self.respect_mask = bool(self.respect_mask)
+
+
+class _WeightedStream:
+    """One stream of a composer with ``sampling``: what ``ops.pixel_rows_build`` / ``ops.pixel_draw`` take, the row table (8 bytes
+    per image row -- the whole state of the feature) and the static outputs of the draw."""
+
+    def __init__(self, data: "CameraSetData", stream_id: int, n: int, images: Optional[Tensor], w_active: int, w_idle: int,
+                 respect_mask: bool, device):
+        self.data, self.stream_id, self.n = data, stream_id, n
+        self.images, self.msk = images, (data.msk if respect_mask else None)
+        self.shape = (data.n_images, data.H, data.W)
+        self.w_active, self.w_idle = w_active, w_idle
+        self.row_off = torch.zeros(data.n_images * data.H + 1, dtype=torch.int64, device=device)
+        self.indices = torch.zeros(n, 3, dtype=torch.int32, device=device)
+        self.weights = torch.zeros(n, dtype=torch.int32, device=device)
+        self.total = 0
+
+    def build(self) -> int:
+        from . import ops
+        ops.pixel_rows_build(self.images, self.msk, self.shape, self.w_active, self.w_idle, row_off=self.row_off)
+        self.total = int(self.row_off[-1])          # the one host read, at set-up
+        return self.total
+
+    def draw(self, step: Optional[int], step_dev: Tensor, seed: int) -> None:
+        from . import ops
+        ops.pixel_draw(self.images, self.msk, self.shape, self.w_active, self.w_idle, self.row_off, seed, self.stream_id, self.n,
+                       step=step, step_dev=step_dev if step is None else None, indices=self.indices, weights=self.weights)
+
+    def row_weights(self, rows: np.ndarray) -> np.ndarray:
+        """int64 [len(rows), W]: the weights of the given image rows, computed on the device from the resident data."""
+        _, H, W = self.shape
+        r = torch.as_tensor(rows, dtype=torch.int64, device=self.row_off.device)
+        if self.images is None:
+            w = torch.full((len(rows), W), self.w_idle, dtype=torch.int64, device=r.device)
+        else:
+            active = self.images.reshape(-1, W)[r].to(torch.float32) != 0
+            w = torch.where(active, self.w_active, self.w_idle).to(torch.int64)
+        if self.msk is not None:
+            w = torch.where(self.msk.reshape(-1, W)[r].to(torch.float32) == 0, torch.zeros_like(w), w)
+        return w.cpu().numpy()
+
+    def draw_host(self, seed: int, step: int) -> Tuple[np.ndarray, np.ndarray]:
+        """``(indices int64 [n, 3], weights int64 [n])``: the draw in Python integers and numpy (exact)."""
+        _, H, W = self.shape
+        ctr = np.zeros((self.n, 4), dtype=np.uint32)
+        ctr[:, 0] = int(step) & 0xFFFFFFFF
+        ctr[:, 1] = np.arange(self.n, dtype=np.uint32)
+        ctr[:, 2] = self.stream_id
+        p = philox4x32_10(ctr, (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF))
+        row_off = self.row_off.cpu().numpy()
+        total = int(row_off[-1])
+        t = np.array([(((int(a) << 32) | int(b)) * total) >> 64 for a, b in p[:, :2]], dtype=np.int64)
+        r = np.searchsorted(row_off[:-1], t, side="right") - 1
+        v = t - row_off[r]
+        uniq, inv = np.unique(r, return_inverse=True)
+        w = self.row_weights(uniq)[inv] if self.n else np.zeros((0, W), np.int64)
+        excl = np.cumsum(w, axis=1) - w
+        x = (excl <= v[:, None]).sum(1) - 1
+        idx = np.stack([r // H, r % H, x], axis=1).astype(np.int64)
+        return idx, (w[np.arange(self.n), x] if self.n else np.zeros(0, np.int64))
 
 
 def find_closest_idxs(ref: Tensor, srch: Tensor) -> Tensor:
@@ -248,13 +347,21 @@ class BatchComposer:
 
     ``event_pairing``: "consec" (``ConsecRayGenerator``: ONE table over the event set's cameras, read at ``c`` and ``c + 1``;
     ``pose_tables[2]`` is None) or "prevnext" (``PrevNextRayGenerator``: two tables, both read at ``c``).
-    ``num_embd``: the clip bound of the deblur appearance offsets (R:lse_nerf/utils.py:170-178); default: largest colour id + 1."""
+    ``num_embd``: the clip bound of the deblur appearance offsets (R:lse_nerf/utils.py:170-178); default: largest colour id + 1.
+    ``sampling``: a ``PixelSampling`` -- pixels are drawn by integer weight (masked pixels never, event pixels by activity) by one
+    ``lse_pixel_draw`` launch per stream in front of the compose launch, which then takes the drawn pixels as given indices.
+    ``draw_weights`` = ``(col, evs)`` int32 [n] static tensors: the weight of every pixel of the last draw (a stream whose pixels
+    came from ``compose(indices=...)`` keeps those of its last draw); ``sampling_totals`` = ``(col, evs)`` the streams' total
+    weights, read once here, ValueError where one is 0; ``rebuild_sampling()`` after the resident images or masks were edited in
+    place.  Both are None with ``sampling=None``, which launches and allocates exactly what it did without this argument."""
 
     def __init__(self, scene: DeviceScene, n_col_pixels: int, n_evs_pixels: int, deblur: bool = False, seed: int = 0,
-                 event_pairing: str = "consec", num_embd: Optional[int] = None):
+                 event_pairing: str = "consec", num_embd: Optional[int] = None, sampling: Optional[PixelSampling] = None):
         assert event_pairing in ("consec", "prevnext"), event_pairing
         if not 0 <= int(seed) < 2 ** 64:
             raise ValueError("seed must fit 64 unsigned bits")
+        if sampling is not None and not isinstance(sampling, PixelSampling):
+            raise ValueError(f"sampling= takes a PixelSampling or None, got {type(sampling).__name__}")
         self.scene, self.seed = scene, int(seed)
         self.n_col = int(n_col_pixels) if scene.col is not None else 0
         self.n_evs = int(n_evs_pixels) if scene.evs is not None else 0
@@ -338,6 +445,33 @@ class BatchComposer:
             o.evs_image, o.evs_msk, o.evs_e_thresh = _ptr(b["image"]), _ptr(b.get("msk")), _ptr(b["e_thresh"])
             o.evs_indices, o.evs_batch_appearance_id = _ptr(b["indices"]), _ptr(b["appearance_id"])
         self._out_desc = o
+        # weighted sampling: per stream a row table and the static outputs of the draw (nothing at all with sampling=None)
+        self.sampling = sampling
+        self._weighted: Tuple[Optional[_WeightedStream], Optional[_WeightedStream]] = (None, None)
+        self.draw_weights = self.sampling_totals = None
+        if sampling is not None:
+            self._weighted = (
+                _WeightedStream(col, 0, nc, None, 1, 1, sampling.respect_mask, dev) if nc else None,
+                _WeightedStream(evs, 1, ne, evs.images, sampling.evs_active_weight, sampling.evs_idle_weight, sampling.respect_mask,
+                                dev) if ne else None)
+            self.draw_weights = tuple(None if w is None else w.weights for w in self._weighted)
+            self.rebuild_sampling()
+
+    # -- weighted sampling
+    def rebuild_sampling(self) -> Tuple[Optional[int], Optional[int]]:
+        """Build the row tables of the weighted draw again from the resident images and masks -- after a caller edited them in place
+        -- and read the streams' total weights (one host read per stream; ValueError where a total is 0, as at construction).
+        Returns ``sampling_totals``."""
+        if self.sampling is None:
+            raise ValueError("this composer draws uniformly (sampling=None): there are no tables to rebuild")
+        totals = []
+        for name, w in zip(("colour", "event"), self._weighted):
+            totals.append(None if w is None else w.build())
+            if totals[-1] == 0:
+                raise ValueError(f"weighted sampling: the {name} stream has a total weight of 0 -- every pixel is masked out or has "
+                                 f"a weight of 0, nothing can be drawn")
+        self.sampling_totals = tuple(totals)
+        return self.sampling_totals
 
     # -- buffers as bundles
     def _make_bundles(self, origins: Tensor, directions: Tensor) -> Tuple[Optional[RayBundle], ...]:
@@ -525,6 +659,14 @@ class BatchComposer:
     def _launch(self, step: Optional[int], indices) -> None:
         col_i, evs_i = self._given(indices)
         own = step is None
+        if self.sampling is not None:          # the weighted draw of every stream no pixels were given for, in front of the advance
+            drawn = []
+            for w, given in zip(self._weighted, (col_i, evs_i)):
+                if w is not None and given is None:
+                    w.draw(step, self.step_dev, self.seed)
+                    given = w.indices
+                drawn.append(given)
+            col_i, evs_i = drawn
         _lib.call("lse_compose_batch", ctypes.byref(self._desc), ctypes.byref(self._scene_desc), ctypes.byref(self._out_desc),
                   _ptr(self.step_dev) if own else None, 0 if own else int(step), int(own), _ptr(col_i), _ptr(evs_i), _stream())
 
@@ -583,8 +725,12 @@ class BatchComposer:
         return self._rays_bwd(d_o.contiguous(), d_d.contiguous())
 
     def indices_host(self, step: int) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
-        """``(col, evs)`` int64 [n, 3] = (c, y, x): what the device draws at ``step`` (``draw_indices_host``)."""
+        """``(col, evs)`` int64 [n, 3] = (c, y, x): what the device draws at ``step`` (``draw_indices_host``; with ``sampling`` the
+        weighted draw in host integers, over the row tables and the image rows it needs copied from the device -- a test and resume
+        helper, not for the training loop)."""
         col, evs = self.scene.col, self.scene.evs
+        if self.sampling is not None:
+            return tuple(None if w is None else w.draw_host(self.seed, step)[0] for w in self._weighted)
         return (draw_indices_host(self.seed, step, 0, self.n_col, col.n_images, col.H, col.W) if self.n_col else None,
                 draw_indices_host(self.seed, step, 1, self.n_evs, evs.n_images, evs.H, evs.W) if self.n_evs else None)
 

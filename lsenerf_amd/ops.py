@@ -2762,3 +2762,88 @@ def event_accumulate(x: torch.Tensor, y: torch.Tensor, t: torch.Tensor, p: torch
     a = _ev(acc, torch.int32, (F, H, W), "acc")
     _lib.call("lse_event_accumulate", *args, n, nd, b, F, H, W, a, _stream())
     return acc
+
+
+# ---- weighted pixel draw (csrc/pixel_draw.hip; driven by lsenerf_amd.data.BatchComposer) ----
+PIXEL_MAX_WEIGHT = 255
+_PIXEL_TYPE = {torch.int8: _lib.LSE_PIX_I8, torch.uint8: _lib.LSE_PIX_U8, torch.int16: _lib.LSE_PIX_I16, torch.int32: _lib.LSE_PIX_I32,
+               torch.float32: _lib.LSE_PIX_F32}
+
+
+def _px_weights(w_active: int, w_idle: int) -> Tuple[int, int]:
+    ok = all(isinstance(w, int) and not isinstance(w, bool) and 0 <= w <= PIXEL_MAX_WEIGHT for w in (w_active, w_idle))
+    if not ok or w_active + w_idle == 0:
+        raise ValueError(f"pixel weights are integers in [0, {PIXEL_MAX_WEIGHT}], not both zero; got {w_active!r} and {w_idle!r}")
+    return w_active, w_idle
+
+
+def _px_planes(t: Optional[torch.Tensor], shape, name: str, dtypes):
+    """(pointer, LSE_PIX_* code) of an optional resident [n_images, H, W] tensor."""
+    if t is None:
+        return None, _lib.LSE_PIX_NONE
+    if not torch.is_tensor(t) or t.dtype not in dtypes:
+        raise ValueError(f"{name}: a tensor of one of {[str(d) for d in dtypes]} expected, got {getattr(t, 'dtype', type(t))}")
+    return _ev(t, t.dtype, shape, name), _PIXEL_TYPE[t.dtype]
+
+
+def _px_set(images, msk, shape, w_active, w_idle):
+    n_images, H, W = (int(s) for s in shape)
+    if min(n_images, H, W) < 1:
+        raise ValueError(f"a camera set of {n_images} images of {H} x {W}: every extent must be at least 1")
+    w_active, w_idle = _px_weights(w_active, w_idle)
+    im, pix_type = _px_planes(images, (n_images, H, W), "images", tuple(_PIXEL_TYPE))
+    mk, msk_type = _px_planes(msk, (n_images, H, W), "msk", (torch.uint8, torch.float32))
+    if images is None:
+        if w_active != w_idle:
+            raise ValueError("without images every pixel weighs the same: w_active must equal w_idle")
+        pix_type = _lib.LSE_PIX_U8
+    return (im, pix_type, mk, msk_type, n_images, H, W, w_active, w_idle), n_images * H
+
+
+@torch.no_grad()
+def pixel_rows_build(images: Optional[torch.Tensor], msk: Optional[torch.Tensor], shape, w_active: int, w_idle: int,
+                     row_off: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``row_off`` int64 [n_images * H + 1] of a resident camera set of ``shape = (n_images, H, W)``: the exclusive prefix sums of the
+    rows' summed pixel weights and, last, the total -- lse_pixel_rows_build (include/lse_hip.h, "weighted pixel draw": the weight of a
+    pixel is 0 where ``msk`` is 0, else ``w_active`` / ``w_idle`` by ``images != 0``; ``images=None``: ``w_idle`` everywhere).
+    No host read."""
+    args, rows = _px_set(images, msk, shape, w_active, w_idle)
+    if row_off is None:
+        ref = images if images is not None else msk
+        if ref is None:
+            raise ValueError("pixel_rows_build: without images and a mask, pass row_off (it names the device)")
+        row_off = torch.empty(rows + 1, dtype=torch.int64, device=ref.device)
+    ro = _ev(row_off, torch.int64, (rows + 1,), "row_off")
+    _lib.call("lse_pixel_rows_build", *args, ro, _stream())
+    return row_off
+
+
+@torch.no_grad()
+def pixel_draw(images: Optional[torch.Tensor], msk: Optional[torch.Tensor], shape, w_active: int, w_idle: int, row_off: torch.Tensor,
+               seed: int, stream_id: int, n: int, step: Optional[int] = None, step_dev: Optional[torch.Tensor] = None,
+               indices: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
+    """``n`` pixels of the set drawn by weight at ``step`` (an int) or at ``step_dev[0]`` (int64 [1] on the device; exactly one of the
+    two): ``(indices int32 [n, 3] = (c, y, x), weights int32 [n])`` -- lse_pixel_draw over the ``row_off`` of ``pixel_rows_build`` with
+    the same images, mask and weights.  One launch whose grid depends on ``n`` only; no host read."""
+    args, rows = _px_set(images, msk, shape, w_active, w_idle)
+    n, seed, stream_id = int(n), int(seed), int(stream_id)
+    if n < 0:
+        raise ValueError("pixel_draw: n < 0")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must fit 64 unsigned bits")
+    if stream_id not in (0, 1):
+        raise ValueError("stream_id is 0 (colour) or 1 (events)")
+    if (step is None) == (step_dev is None):
+        raise ValueError("pixel_draw: give step or step_dev")
+    if step is not None and not 0 <= int(step) < 2 ** 63:
+        raise ValueError(f"the draw position is a step number, got {step}")
+    ro = _ev(row_off, torch.int64, (rows + 1,), "row_off")
+    sd = _ev(step_dev, torch.int64, (1,), "step_dev", True)
+    dev = row_off.device
+    if indices is None:
+        indices = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    if weights is None:
+        weights = torch.empty(n, dtype=torch.int32, device=dev)
+    ix, wt = _ev(indices, torch.int32, (n, 3), "indices"), _ev(weights, torch.int32, (n,), "weights")
+    _lib.call("lse_pixel_draw", *args, ro, seed, stream_id, sd, 0 if step is None else int(step), n, ix, wt, _stream())
+    return indices, weights
